@@ -37,13 +37,22 @@ Workloads (--workload):
            (sharding.refit_split_services), parents are gathered at the end.  Strong scaling; bit-identical to the
            unsplit run (--verify 1 checks it on rank 0).
 
-`python bench.py --gpus N` with N > 1 and no --workload prints the media line (weak scaling) and, under `scale_regimes`, the two
+`python bench.py --gpus N --full` with N > 1 and no --workload prints the media line (weak scaling) and, under `scale_regimes`, the two
 sharded modes north_star names -- `alibaba` and `alibaba-full`, each with --verify 1 (`sharded_equals_single_gpu`).
 
 N > 1: `python bench.py --gpus N` starts N ranks itself (re-exec under torch.distributed.run on 127.0.0.1); when the
 driver has already started the ranks (RANK / WORLD_SIZE in the environment) --gpus must equal WORLD_SIZE.  One process
 per GPU, rank r -> device LOCAL_RANK; the media / nodejs workloads have no data-path collective (units are
 independent), the only collectives are the timing barrier / max-reduce.
+
+A plain run only sets up, warms up, times the --steps steps, writes --dump-outputs if asked and prints the result line.
+Everything else moves behind --full: the harder single-GPU regimes, the CPU baseline, the ingest / end-to-end / load-level
+/ shipped-corpora legs, the measured HBM peak, the host cross-check of the device accuracy reduction, the sharded modes of
+`--gpus N > 1` without --workload and the detail file (unless --detail-file names one).
+
+--dump-outputs DIR writes what the last timed step computed (pass 2's parent arrays, a seeded sample of them when the
+batch is larger, and the per-unit accuracies; see dump_outputs) as .npy files, so that two builds can be compared output
+for output: with the same arguments the inputs are the same seed-fixed synthetic batch.
 """
 import argparse
 import json
@@ -71,8 +80,8 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=["media", "nodejs", "alibaba", "alibaba-full", "media-split"],
-                    help="default: media -- and with --gpus N > 1 also the two sharded modes (alibaba, alibaba-full, each with --verify 1) under `scale_regimes`")
-    ap.add_argument("--scale-regimes", type=int, default=1, help="--gpus N > 1 without --workload: also run the sharded modes (0 = only the media line)")
+                    help="default: media -- and with --full and --gpus N > 1 also the two sharded modes (alibaba, alibaba-full, each with --verify 1) under `scale_regimes`")
+    ap.add_argument("--scale-regimes", type=int, default=1, help="--full, --gpus N > 1 without --workload: also run the sharded modes (0 = only the media line)")
     ap.add_argument("--levels", default="1,200,1000,4000,10000,15000",
                     help="alibaba-full: the --compress_factor values every call graph is solved at (exps/exp5/run_experiment.sh:60-156)")
     ap.add_argument("--n-in", type=int, default=100000, help="requests per service unit (media / nodejs)")
@@ -85,14 +94,14 @@ def parse_args():
     ap.add_argument("--total-spans", type=int, default=1000000, help="engine spans of the Alibaba-shape slice (whole job)")
     ap.add_argument("--verify", type=int, default=0, help="alibaba: rank 0 also solves the whole slice alone and compares the gathered parents")
     ap.add_argument("--fit", default="device", choices=["device", "sklearn"], help="mixture refit between the passes")
-    ap.add_argument("--cpu-sample", type=int, default=40000, help="requests per service in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=40000, help="--full: requests per service in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-procs", type=int, default=32, help="CPU baseline: also the sample in min(this, usable cores) processes at once (1 = skip)")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--regimes", type=int, default=1,
-                    help="default workload at N = 1 only: after the timed step loop, 3 steps each of the harder single-GPU regimes "
+                    help="--full, default workload at N = 1 only: after the timed step loop, 3 steps each of the harder single-GPU regimes "
                          "(config 3 shape, the config 4 slice on one GPU, media shape at concurrency 4 and 8) on the same engine, "
                          "reported under `regimes` with their own roofline blocks")
-    ap.add_argument("--end-to-end", type=int, default=1, help="also time JSON -> ingest -> H2D -> two passes -> parents on the host (rank 0, N = 1)")
+    ap.add_argument("--end-to-end", type=int, default=1, help="--full: also time JSON -> ingest -> H2D -> two passes -> parents on the host (rank 0, N = 1)")
     ap.add_argument("--host-traces", default="20000,15000", help="traces of the hotel- and the Alibaba-shape JSON corpus of the ingest / end-to-end legs")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL; gloo lets several ranks share one GPU for testing)")
@@ -100,9 +109,14 @@ def parse_args():
                     help="torch: torch.cuda.synchronize() around the timed region (the bench contract).  engine (N = 1 only): no torch "
                          "import -- every C-ABI call returns with its stream synchronised; what profiles/collect.sh uses, so that its "
                          "rocprofv3 passes do not spend a minute each importing torch on a fresh box")
-    ap.add_argument("--detail-file", default=None, help="where the full record goes (default: gpurun_out/bench_detail_n<N>.json); the last stdout line is the compact one")
+    ap.add_argument("--detail-file", default=None, help="where the full record goes (written by default only with --full, see write_detail); the last stdout line is the compact one")
     ap.add_argument("--lib", default=None, help="TESTING ONLY: path of an alternative build of libtwgpu (the host-emulation "
                                                 "library of tests/hostemu); no GPU is touched then")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: regimes, CPU baseline, host legs, measured HBM "
+                         "peak, host cross-check of the accuracy, the sharded modes of --gpus N > 1, the detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     args.default_line = args.workload is None   # the driver's line: media, plus the sharded modes when N > 1 (main)
     if args.default_line:
@@ -515,6 +529,27 @@ def profile_traffic(dominant, spans_rank):
     return g["fetch_bytes_x2"] + g["write_bytes"], os.path.basename(tpaths[-1])
 
 
+DUMP_SAMPLE = 1 << 21   # parent entries --dump-outputs writes at most (2 x 16 MB as float64)
+
+
+def dump_outputs(directory, parents, res):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in `directory`:
+    parent.npy (float64) pass 2's parent arrays of every unit ([E, n_in] each, flattened and concatenated in unit order; -1 =
+    unassigned) -- all of them up to DUMP_SAMPLE entries, beyond that a fixed sample drawn with seed 0 -- and
+    parent_index.npy (float64) the positions of those entries in the concatenation; accuracy.npy / topk_accuracy.npy
+    (float64) the per-unit figures of the device reduction (of this rank's units)."""
+    flat = np.concatenate([np.asarray(p, dtype=np.int64).ravel() for p in parents])
+    if len(flat) > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(len(flat), DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(len(flat))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "parent.npy"), flat[idx].astype(np.float64))
+    np.save(os.path.join(directory, "parent_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "accuracy.npy"), np.array([r["accuracy"] for r in res], dtype=np.float64))
+    np.save(os.path.join(directory, "topk_accuracy.npy"), np.array([r["topk_accuracy"] for r in res], dtype=np.float64))
+
+
 class Ctx(object):
     """What every workload of one bench process shares: the rank's place in the job, its device, the collectives."""
 
@@ -728,12 +763,17 @@ def run_workload(args, c, primary=True):
             lv = tl.cpu().numpy()
         acc_levels = [float(a / max(b, 1)) for a, b in lv]
     acc = float(np.mean([r["accuracy"] for r in res])) if not strong else float(acc_sum[0] / max(acc_sum[1], 1))
-    host = eng.results(2, fields=("parent",))          # cross-check of the device reduction, outside the timed region
+    host = None
+    if args.full or strong or args.dump_outputs:
+        host = eng.results(2, fields=("parent",))      # outside the timed region
     from traceweaver_amd import synth
 
-    if not full:   # (a scaled table is re-sorted on the device together with its ground truth: the host's copy is in upload order)
+    if args.full and not full:   # cross-check of the device reduction (a scaled table is re-sorted on the device together with its ground truth: the host's copy is in upload order)
         host_acc = [synth.accuracy(r["parent"], tp) for r, tp in zip(host, truth)]
         assert all(abs(a - r["accuracy"]) < 1e-12 for a, r in zip(host_acc, res)), "device accuracy reduction differs from the host's"
+    if args.dump_outputs and rank == 0:   # before --verify below reloads the engine
+        whole = strong and gathered is not None and all(g is not None for g in gathered)
+        dump_outputs(args.dump_outputs, gathered if whole else [r["parent"] for r in host], res)
     verified = None
     if strong and gathered is not None:
         for k, p in zip(mine, host):
@@ -790,11 +830,11 @@ def run_workload(args, c, primary=True):
         }
         if verified is not None:
             out["sharded_equals_single_gpu"] = bool(verified)
-        if primary and not emulated and world == 1:
+        if args.full and primary and not emulated and world == 1:
             out["roofline"]["peak_measured"] = eng.hbm_copy_gbps()
-        if primary and args.regimes and world == 1 and not emulated and args.workload == "media" and args.concurrency is None:
+        if args.full and primary and args.regimes and world == 1 and not emulated and args.workload == "media" and args.concurrency is None:
             out["regimes"] = run_regimes(args, eng)
-        if primary and args.cpu_sample > 0 and world == 1:
+        if args.full and primary and args.cpu_sample > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, 1000)
             import tempfile
 
@@ -895,7 +935,7 @@ def main():
         sys.exit(launch_ranks(args))
     c = setup(args)
     out = run_workload(args, c, primary=True)
-    if args.default_line and c.world > 1 and args.scale_regimes:
+    if args.full and args.default_line and c.world > 1 and args.scale_regimes:
         # the driver's multi-GPU line: next to the weak-scaling media workload (no data-path collective) the two sharded modes
         # north_star names -- strong scaling, every step ends with the all-gather of the parent arrays (RCCL on the engine's
         # device buffers with backend nccl), each verified on rank 0 against the single-GPU result
@@ -917,7 +957,7 @@ def main():
     if c.rank == 0:
         # the full record (regimes with their roofline blocks, the reference's per-shape timings, host legs) goes to a file; the LAST
         # stdout line is the compact record the driver parses (round 4's 20 KB line did not fit the driver's 8 KB tail)
-        path = write_detail(args, out)
+        path = write_detail(args, out) if (args.full or args.detail_file) else None
         print(json.dumps(compact_line(out, path), separators=(",", ":")))
     if c.world > 1:
         c.dist.barrier()

@@ -16,6 +16,11 @@ GOLDEN = sorted(glob.glob(os.path.join(REPO, "tests", "golden", "ref_*.npz"))) +
     sorted(glob.glob(os.path.join(REPO, "tests", "golden", "refsyn_*.npz")))
 
 
+# the shipped corpora the frozen runs were made from, as the reference's data directory holds them (trace files only; media_load75's
+# 1500 files in two archives): unpacked by the `reference_root` fixture
+CORPORA = sorted(glob.glob(os.path.join(REPO, "tests", "golden", "corpus_*.tar.xz")))
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
@@ -30,6 +35,19 @@ def oracle():
 
     tw_oracle.lib()
     return tw_oracle
+
+
+@pytest.fixture(scope="session")
+def reference_root(tmp_path_factory):
+    """A tree root laid out like the reference's (data/<application>/<corpus>/*.json) with the 24 shipped corpora, unpacked from
+    tests/golden/corpus_<application>__<corpus>[.part2].tar.xz once per session."""
+    import tarfile
+
+    root = tmp_path_factory.mktemp("reference_root")
+    for f in CORPORA:
+        with tarfile.open(f, "r:xz") as t:
+            t.extractall(str(root / "data"))
+    return str(root)
 
 
 @pytest.fixture(scope="session")

@@ -1,16 +1,17 @@
-"""Baseline predictors (traceweaver_amd/baselines.py) against the reference's own classes, imported from
-/root/reference (CPU tier, this container only): same inputs -> identical assignments."""
+"""Baseline predictors (traceweaver_amd/baselines.py) against the reference's own classes: same inputs -> identical
+assignments.  What the reference's FCFS, ArrivalOrder, vPath and WAP5 returned for every input below is stored in
+tests/golden/baseline_refs.npz (tests/golden/make_baseline_refs.py runs the reference's classes on the same inputs)."""
 import os
 import sys
 
 import numpy as np
 import pytest
 
+from conftest import REPO
 from traceweaver_amd import baselines, synth
 from traceweaver_amd.ingest import Corpus, REFERENCE_FIX
 
-REF_PY = "/root/reference/src/trace_reconstructor/ports/python"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_PY), reason="the reference tree is not present")
+REF_OUT = os.path.join(REPO, "tests", "golden", "baseline_refs.npz")
 
 
 class Span(object):
@@ -25,16 +26,18 @@ class Span(object):
         return (self.trace_id, self.sid)
 
 
-def reference_classes():
+def reference_classes(ref_py):
+    """FCFS, ArrivalOrder, vPath, WAP5 of the reference tree's python port (tests/golden/make_baseline_refs.py only)."""
     saved = list(sys.path)
-    sys.path.insert(0, REF_PY)
+    sys.path.insert(0, ref_py)
     try:
         from algorithms.arrival_order import ArrivalOrder
         from algorithms.fcfs import FCFS
         from algorithms.vpath import vPath
+        from algorithms.wap5 import WAP5
     finally:
         sys.path[:] = saved
-    return FCFS, ArrivalOrder, vPath
+    return FCFS, ArrivalOrder, vPath, WAP5
 
 
 def protocol_inputs(u, trace_of_in, trace_of_out):
@@ -67,84 +70,117 @@ def to_parent(u, asg, in_parts, parts):
     return out
 
 
-def check_units(units):
-    FCFS, ArrivalOrder, vPath = reference_classes()
-    for u in units:
-        a = u.arrays
-        trace_in = ["t%d" % k for k in u.in_trace]
+def _unit_traces(u, wap5):
+    a = u.arrays
+    trace_in = ["t%d" % k for k in u.in_trace]
+    if wap5:
+        trace_out = [["x%d_%d" % (e, j) for j in range(int(a.out_off[e + 1] - a.out_off[e]))] for e in range(a.E)]
+    else:
         trace_out = [["t%d" % u.in_trace[np.flatnonzero(u.true_parent[e] == j)[0]] if (u.true_parent[e] == j).any() else "x%d_%d" % (e, j)
                       for j in range(int(a.out_off[e + 1] - a.out_off[e]))] for e in range(a.E)]
-        in_parts, parts, truth = protocol_inputs(u, trace_in, trace_out)
-        for name, cls, mine in (("FCFS", FCFS, baselines.fcfs(a)), ("ArrivalOrder", ArrivalOrder, baselines.arrival_order(a)),
-                                ("vPath", vPath, baselines.vpath(a, u.true_parent))):
-            import copy
-            ref = cls({}, {}).FindAssignments(name, u.service, copy.deepcopy(in_parts), copy.deepcopy(parts), False, [], truth)
-            assert np.array_equal(to_parent(u, ref, in_parts, parts), mine), (u.service, name)
+    return trace_in, trace_out
 
 
-def check_wap5(units):
-    """One reference instance and one of ours, fed the services in the same order (state leaks between services)."""
+def run_reference(units, classes, parents=True, wap5=True):
+    """The reference's classes on the units, in the protocol the executor uses: {key: array} as stored in baseline_refs.npz --
+    "<k>/<name>" the parent array [E, n_in] of FCFS / ArrivalOrder / vPath for unit k, "<k>/WAP5/<e>/calls" and "<k>/WAP5/<e>/off"
+    the calls WAP5 gave every request of endpoint e (one WAP5 instance fed the units in order: state leaks between services)."""
     import copy
 
-    saved = list(sys.path)
-    sys.path.insert(0, REF_PY)
-    try:
-        from algorithms.wap5 import WAP5
-    finally:
-        sys.path[:] = saved
-    ref, mine = WAP5({}, {}), baselines.WAP5()
-    for u in units:
-        a = u.arrays
-        trace_in = ["t%d" % k for k in u.in_trace]
-        trace_out = [["x%d_%d" % (e, j) for j in range(int(a.out_off[e + 1] - a.out_off[e]))] for e in range(a.E)]
-        in_parts, parts, truth = protocol_inputs(u, trace_in, trace_out)
-        got = ref.FindAssignments("WAP5", u.service, copy.deepcopy(in_parts), copy.deepcopy(parts), False, [], truth)
-        options = mine.assign(a, u.out_eps)
+    FCFS, ArrivalOrder, vPath, WAP5 = classes
+    out, w = {}, WAP5({}, {})
+    for k, u in enumerate(units):
+        in_parts, parts, truth = protocol_inputs(u, *_unit_traces(u, False))
+        for name, cls in (("FCFS", FCFS), ("ArrivalOrder", ArrivalOrder), ("vPath", vPath)) if parents else ():
+            ref = cls({}, {}).FindAssignments(name, u.service, copy.deepcopy(in_parts), copy.deepcopy(parts), False, [], truth)
+            out["%d/%s" % (k, name)] = to_parent(u, ref, in_parts, parts)
+        if not wap5:
+            continue
+        in_parts, parts, truth = protocol_inputs(u, *_unit_traces(u, True))
+        got = w.FindAssignments("WAP5", u.service, copy.deepcopy(in_parts), copy.deepcopy(parts), False, [], truth)
         in_spans = list(in_parts.values())[0]
         for e, ep in enumerate(u.out_eps):
             pos = {s.GetId(): j for j, s in enumerate(parts[ep])}
-            for i, s in enumerate(in_spans):
-                want = [pos[x] for x in got[ep][s.GetId()] if tuple(x) != ("NA", "NA")]
-                assert options[e][i] == want, (u.service, ep, i)
+            calls = [[pos[x] for x in got[ep][s.GetId()] if tuple(x) != ("NA", "NA")] for s in in_spans]
+            out["%d/WAP5/%d/calls" % (k, e)] = np.array([j for c in calls for j in c], dtype=np.int32)
+            out["%d/WAP5/%d/off" % (k, e)] = np.cumsum([0] + [len(c) for c in calls]).astype(np.int32)
+    return out
+
+
+def stored(case):
+    with np.load(REF_OUT) as d:
+        return {k[len(case) + 1:]: d[k] for k in d.files if k.startswith(case + "/")}
+
+
+def check_units(units, case):
+    ref = stored(case)
+    assert ref, case
+    for k, u in enumerate(units):
+        a = u.arrays
+        for name, mine in (("FCFS", baselines.fcfs(a)), ("ArrivalOrder", baselines.arrival_order(a)), ("vPath", baselines.vpath(a, u.true_parent))):
+            assert np.array_equal(ref["%d/%s" % (k, name)], mine), (u.service, name)
+
+
+def check_wap5(units, case):
+    """One reference instance and one of ours, fed the services in the same order (state leaks between services)."""
+    ref, mine = stored(case), baselines.WAP5()
+    assert ref, case
+    for k, u in enumerate(units):
+        options = mine.assign(u.arrays, u.out_eps)
+        for e, ep in enumerate(u.out_eps):
+            calls, off = ref["%d/WAP5/%d/calls" % (k, e)], ref["%d/WAP5/%d/off" % (k, e)]
+            assert len(off) == u.arrays.n_in + 1, (u.service, ep)
+            for i in range(u.arrays.n_in):
+                assert options[e][i] == calls[off[i]:off[i + 1]].tolist(), (u.service, ep, i)
+
+
+# the inputs: (case, how its units are made) -- shared with tests/golden/make_baseline_refs.py
+def generated_units(lib, directory, app, seed, traces, concurrency):
+    synth.write_jaeger_corpus(str(directory), seed, traces, app=app, concurrency=concurrency)
+    c = Corpus(lib_path=lib)
+    c.add_directory(str(directory), first_span=app["root_op"], max_traces=0)
+    units = c.units()[0]
+    c.close()
+    return units
+
+
+def corpus_units(lib, root, rel, fix):
+    first, surgery = REFERENCE_FIX[fix]
+    c = Corpus(lib_path=lib)
+    c.add_directory(os.path.join(root, "data", rel), first_span=first, max_traces=1001, fix=surgery)
+    units = c.units()[0]
+    c.close()
+    return units
+
+
+GENERATED = [("gen_wap5", synth.HOTEL_APP, 23, 300, 2.0), ("gen_hotel", synth.HOTEL_APP, 21, 250, 2.5), ("gen_fanout", synth.FANOUT_APP, 21, 250, 1.6)]
+WAP5_CORPORA = [("hotel_reservation/hotel_load100", 2), ("nodejs_microservices/node_load150", 0)]
+BASELINE_CORPORA = [("hotel_reservation/hotel_load150", 2), ("nodejs_microservices_with_arbitrary_file_io/node_1", 0),
+                    ("media_microservices/media_load100", 1)]
+SCALED = [3, 7]
+
+
+def _gen(case):
+    return next(g for g in GENERATED if g[0] == case)[1:]
 
 
 def test_wap5_on_generated_corpora(emu_lib, tmp_path):
-    synth.write_jaeger_corpus(str(tmp_path), 23, 300, app=synth.HOTEL_APP, concurrency=2.0)
-    c = Corpus(lib_path=emu_lib)
-    c.add_directory(str(tmp_path), first_span="HTTP GET /hotels", max_traces=0)
-    check_wap5(c.units()[0])
-    c.close()
+    check_wap5(generated_units(emu_lib, tmp_path, *_gen("gen_wap5")), "gen_wap5")
 
 
-@pytest.mark.parametrize("rel,fix", [("hotel_reservation/hotel_load100", 2), ("nodejs_microservices/node_load150", 0)])
-def test_wap5_on_reference_corpora(emu_lib, rel, fix):
-    first, surgery = REFERENCE_FIX[fix]
-    c = Corpus(lib_path=emu_lib)
-    c.add_directory("/root/reference/data/" + rel, first_span=first, max_traces=1001, fix=surgery)
-    check_wap5(c.units()[0])
-    c.close()
+@pytest.mark.parametrize("rel,fix", WAP5_CORPORA)
+def test_wap5_on_reference_corpora(emu_lib, reference_root, rel, fix):
+    check_wap5(corpus_units(emu_lib, reference_root, rel, fix), rel)
 
 
 def test_baselines_on_generated_corpora(emu_lib, tmp_path):
-    for app, conc in ((synth.HOTEL_APP, 2.5), (synth.FANOUT_APP, 1.6)):
-        d = tmp_path / app["root"]
-        synth.write_jaeger_corpus(str(d), 21, 250, app=app, concurrency=conc)
-        c = Corpus(lib_path=emu_lib)
-        c.add_directory(str(d), first_span=app["root_op"], max_traces=0)
-        units, _, _ = c.units()
-        check_units(units)
-        c.close()
+    for case in ("gen_hotel", "gen_fanout"):
+        check_units(generated_units(emu_lib, tmp_path / case, *_gen(case)), case)
 
 
-@pytest.mark.parametrize("rel,fix", [("hotel_reservation/hotel_load150", 2), ("nodejs_microservices_with_arbitrary_file_io/node_1", 0),
-                                     ("media_microservices/media_load100", 1)])
-def test_baselines_on_reference_corpora(emu_lib, rel, fix):
-    first, surgery = REFERENCE_FIX[fix]
-    c = Corpus(lib_path=emu_lib)
-    c.add_directory("/root/reference/data/" + rel, first_span=first, max_traces=1001, fix=surgery)
-    units, _, _ = c.units()
-    check_units(units)
-    c.close()
+@pytest.mark.parametrize("rel,fix", BASELINE_CORPORA)
+def test_baselines_on_reference_corpora(emu_lib, reference_root, rel, fix):
+    check_units(corpus_units(emu_lib, reference_root, rel, fix), rel)
 
 
 def _scaled(units, factor):
@@ -160,14 +196,14 @@ def _scaled(units, factor):
     return out
 
 
-@pytest.mark.parametrize("factor", [3, 7])
+def scaled_units(lib, directory, factor):
+    return _scaled(generated_units(lib, directory, synth.HOTEL_APP, 29, 300, 1.2), factor)
+
+
+@pytest.mark.parametrize("factor", SCALED)
 def test_baselines_on_load_scaled_units(emu_lib, tmp_path, factor):
     """--compress_factor > 1 hands the reference's classes float timestamps; ours read the exact integer image of them."""
-    synth.write_jaeger_corpus(str(tmp_path), 29, 300, app=synth.HOTEL_APP, concurrency=1.2)
-    c = Corpus(lib_path=emu_lib)
-    c.add_directory(str(tmp_path), first_span="HTTP GET /hotels", max_traces=0)
-    units = _scaled(c.units()[0], factor)
+    units = scaled_units(emu_lib, tmp_path, factor)
     assert all(u.arrays.time_scale < 1.0 for u in units)
-    check_units(units)
-    check_wap5(units)
-    c.close()
+    check_units(units, "scaled_%d" % factor)
+    check_wap5(units, "scaled_%d" % factor)

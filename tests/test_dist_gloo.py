@@ -275,7 +275,7 @@ def test_bench_alibaba_full_matrix_over_two_ranks_equals_one(emu_lib):
 
 
 def test_bench_default_line_with_two_ranks_carries_the_sharded_modes(emu_lib):
-    """`bench.py --gpus 2` without --workload (what the driver runs for its scaling record): the weak-scaling media line and,
+    """`bench.py --gpus 2 --full` without --workload (what the driver runs for its scaling record): the weak-scaling media line and,
     under `scale_regimes`, BASELINE configs 4 and 5 -- sharded per service, parents all-gathered every step, each verified
     against the single-GPU result on rank 0."""
     import json
@@ -283,7 +283,7 @@ def test_bench_default_line_with_two_ranks_carries_the_sharded_modes(emu_lib):
 
     detail = os.path.join(tempfile.mkdtemp(), "detail.json")
     r = _run_bench(emu_lib, "--gpus", "2", "--backend", "gloo", "--n-in", "600", "--replicas", "1", "--total-spans", "20000", "--levels", "1,4000",
-                   "--detail-file", detail)
+                   "--detail-file", detail, "--full")
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and "media" in r["config"]["workload"]
     # the full record of the same run: who ran (the process group's world size and backend, every rank's device) ...
     full = json.load(open(detail))
@@ -351,6 +351,43 @@ def test_bench_sync_engine_needs_no_torch(emu_lib):
     env = dict(os.environ, TW_TILE="1", TW_COOP_THREADS="1")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(emu_lib, tmp_path):
+    """--dump-outputs DIR: what the last timed step computed (pass 2's parents, the per-unit accuracies) as float .npy files; the
+    same arguments give the same inputs and so the same files, whatever the number of steps."""
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    ra = _run_bench(emu_lib, "--n-in", "600", "--replicas", "1", "--dump-outputs", a)
+    rb = _run_bench(emu_lib, "--n-in", "600", "--replicas", "1", "--steps", "2", "--dump-outputs", b)
+    assert ra["steps"] == 1 and rb["steps"] == 2 and rb["ms_per_step"] > 0
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) == ["accuracy.npy", "parent.npy", "parent_index.npy", "topk_accuracy.npy"]
+    for n in names:
+        x, y = np.load(os.path.join(a, n)), np.load(os.path.join(b, n))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    parent, index = np.load(os.path.join(a, "parent.npy")), np.load(os.path.join(a, "parent_index.npy"))
+    assert len(parent) == len(index) == ra["config"]["spans_total"] - 6 * 600   # every outgoing span has one parent entry
+    assert np.array_equal(index, np.arange(len(index))) and parent.min() >= -1
+    assert abs(np.load(os.path.join(a, "accuracy.npy")).mean() - ra["accuracy"]) < 1e-5
+
+
+def test_bench_plain_run_is_lean_and_full_carries_the_extras(emu_lib, tmp_path):
+    """A plain run times the steps and prints the line; the CPU baseline, the host legs and the detail file come with --full."""
+    import json
+
+    plain = _run_bench(emu_lib, "--n-in", "600", "--replicas", "1", "--cpu-sample", "300")
+    for k in ("cpu_baseline", "regimes_spans_per_s", "host_legs_spans_per_s", "detail"):
+        assert k not in plain, k
+    detail = str(tmp_path / "detail.json")
+    full = _run_bench(emu_lib, "--n-in", "600", "--replicas", "1", "--cpu-sample", "300", "--cpu-procs", "1", "--host-traces", "300,200",
+                      "--end-to-end", "0", "--detail-file", detail, "--full")
+    assert full["cpu_baseline"]["cores"] == 1 and full["cpu_baseline"]["value"] > 0
+    with open(detail) as f:
+        rec = json.load(f)
+    assert rec["ingest"]["value"] > 0 and rec["ingest_alibaba"]["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "accuracy", "windows"):
+        assert plain[k] == full[k], k
+    assert plain["ms_per_step"] > 0 and full["ms_per_step"] > 0
 
 
 def test_bench_default_batch_is_sixteen_replicas():

@@ -12,9 +12,6 @@ import pytest
 
 from conftest import GOLDEN
 
-REF = "/root/reference"
-
-
 def e2e_band(name, traces=1000):
     """Allowed distance of an end-to-end accuracy (percent) from the frozen reference run of corpus `name` -- a listed rule, no
     band: a trace may differ from the frozen run only through a request that lies in a window whose optimum is PROVEN not unique
@@ -32,22 +29,21 @@ def e2e_band(name, traces=1000):
     return 100.0 * ties / traces + (0.1 if rows else 0.0) + 1e-9
 
 
-def run_cli(tmp_path, emu_lib, rel, fix, name):
+def run_cli(tmp_path, emu_lib, rel, fix, name, root):
     from traceweaver_amd import executor
 
     out = str(tmp_path) + "/"
     argv = ["--relative_path", rel, "--compressed", "0", "--cache_rate", "0", "--fix", str(fix), "--test_name", name,
             "--load_level", "100", "--compress_factor", "1", "--repeat_factor", "1", "--execute_parallel", "0",
             "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "10",
-            "--project_root", REF, "--engine_library", emu_lib, "--fit", "device"]
+            "--project_root", root, "--engine_library", emu_lib, "--fit", "device"]
     executor.main(argv)
     suffix = "_%s_100_1_1_0.0.pickle" % name
     return {k: pickle.load(open(out + k + suffix, "rb")) for k in ("accuracy", "process_acc", "confidence_scores", "bin_acc", "e2e")}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
-def test_hotel_run_matches_the_frozen_reference_run(emu_lib, tmp_path):
-    got = run_cli(tmp_path, emu_lib, "data/hotel_reservation/hotel_load100/", 2, "hotel_test")
+def test_hotel_run_matches_the_frozen_reference_run(emu_lib, reference_root, tmp_path):
+    got = run_cli(tmp_path, emu_lib, "data/hotel_reservation/hotel_load100/", 2, "hotel_test", reference_root)
     gold = {str(np.load(p)["process"]): np.load(p) for p in GOLDEN if "hotel_load100__" in p}
     method = "MaxScoreBatchSubsetWithSkips"
     assert set(got["accuracy"]) == {method, method + "TopK"}
@@ -66,13 +62,12 @@ def test_hotel_run_matches_the_frozen_reference_run(emu_lib, tmp_path):
     assert len(spans) == 5 and all(s[0] == tid for s in spans)      # frontend: 3 calls, search: 2 calls per request
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("name,rel,fix,n_services", [("media_load100", "data/media_microservices/media_load100/", 1, 6),
                                                      ("nodeio_1", "data/nodejs_microservices_with_arbitrary_file_io/node_1/", 0, 4)])
-def test_corpora_that_need_span_surgery(emu_lib, tmp_path, name, rel, fix, n_services):
+def test_corpora_that_need_span_surgery(emu_lib, reference_root, tmp_path, name, rel, fix, n_services):
     """FixSpans2 (media) / FixSpans (nodejs) corpora through the command line: same services as the frozen reference
     run, per-service accuracy within the reference's run-to-run spread of its own figure."""
-    got = run_cli(tmp_path, emu_lib, rel, fix, name)
+    got = run_cli(tmp_path, emu_lib, rel, fix, name, reference_root)
     gold = {str(np.load(p)["process"]): np.load(p) for p in GOLDEN if "ref_%s__" % name in p}
     assert set(got["confidence_scores"]) == set(gold) and len(gold) == n_services
     for svc, (acc, not_best, n) in got["confidence_scores"].items():
@@ -83,8 +78,7 @@ def test_corpora_that_need_span_surgery(emu_lib, tmp_path, name, rel, fix, n_ser
     assert abs(got["accuracy"]["MaxScoreBatchSubsetWithSkips"] - ref_e2e) <= e2e_band(name)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
-def test_media_load75_directory_ends_where_the_reference_ends(emu_lib, tmp_path):
+def test_media_load75_directory_ends_where_the_reference_ends(emu_lib, reference_root, tmp_path):
     """The one shipped corpus the reference cannot finish from its directory: it keeps the first 1001 of media_load75's 1500 traces in
     time order (executor.py:873), and a service of 1001 requests leaves a last parameter block of ONE sample -- std = NaN, the
     reference aborts in its solver (SURVEY.md hazard H3).  The command line loads the same 1001 traces and stops with the status that
@@ -92,7 +86,7 @@ def test_media_load75_directory_ends_where_the_reference_ends(emu_lib, tmp_path)
     from traceweaver_amd.engine import EngineError
 
     with pytest.raises(EngineError) as err:
-        run_cli(tmp_path, emu_lib, "data/media_microservices/media_load75/", 1, "media_load75")
+        run_cli(tmp_path, emu_lib, "data/media_microservices/media_load75/", 1, "media_load75", reference_root)
     assert err.value.code == -7 and "TW_ERR_NAN_PARAMS" in str(err.value)
     assert not [f for f in os.listdir(str(tmp_path)) if f.endswith(".pickle")]
 
@@ -104,10 +98,9 @@ def _all_corpora():
     return [c for c in REFERENCE_CORPORA if c[0] != "media_load75"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("name,rel,fix", _all_corpora(), ids=[c[0] for c in _all_corpora()])
-def test_end_to_end_accuracy_tracks_the_reference_on_every_corpus(emu_lib, tmp_path, name, rel, fix):
-    got = run_cli(tmp_path, emu_lib, "data/" + rel + "/", fix, name)
+def test_end_to_end_accuracy_tracks_the_reference_on_every_corpus(emu_lib, reference_root, tmp_path, name, rel, fix):
+    got = run_cli(tmp_path, emu_lib, "data/" + rel + "/", fix, name, reference_root)
     g = np.load([p for p in GOLDEN if "ref_%s__" % name in p][0])
     method = "MaxScoreBatchSubsetWithSkips"
     assert int(g["seed"]) == 10   # run_cli's default --seed
@@ -115,11 +108,10 @@ def test_end_to_end_accuracy_tracks_the_reference_on_every_corpus(emu_lib, tmp_p
     assert abs(got["accuracy"][method + "TopK"] - float(g["e2e_topk_accuracy"])) <= 0.1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("name,rel,fix", [c for c in _all_corpora() if c[0] in ("hotel_load100", "hotel_load150", "media_load100", "node_load150",
                                                                                 "nodeio_0.2", "nodeio_1")],
                          ids=["hotel_load100", "hotel_load150", "media_load100", "node_load150", "nodeio_0.2", "nodeio_1"])
-def test_fit_sklearn_reproduces_the_seeded_reference_run(emu_lib, tmp_path, name, rel, fix):
+def test_fit_sklearn_reproduces_the_seeded_reference_run(emu_lib, reference_root, tmp_path, name, rel, fix):
     """--fit sklearn --seed 10 (the cross-check of the default): scikit-learn itself on the host where the device refit
     runs otherwise, the RNG stream replayed service by service -- the command line reproduces the frozen reference run
     (np.random.seed(10)) of the corpus: per-service accuracy to within the few requests whose window optimum is not unique,
@@ -129,7 +121,7 @@ def test_fit_sklearn_reproduces_the_seeded_reference_run(emu_lib, tmp_path, name
     out = str(tmp_path) + "/"
     executor.main(["--relative_path", "data/" + rel + "/", "--compressed", "0", "--cache_rate", "0", "--fix", str(fix), "--test_name", name,
                    "--load_level", "100", "--compress_factor", "1", "--repeat_factor", "1", "--execute_parallel", "0", "--results_directory", out,
-                   "--clear_cache", "1", "--predictor_indices", "10", "--project_root", REF, "--engine_library", emu_lib, "--fit", "sklearn",
+                   "--clear_cache", "1", "--predictor_indices", "10", "--project_root", reference_root, "--engine_library", emu_lib, "--fit", "sklearn",
                    "--seed", "10"])
     suffix = "_%s_100_1_1_0.0.pickle" % name
     acc = pickle.load(open(out + "accuracy" + suffix, "rb"))
@@ -151,10 +143,9 @@ def _band():
     return json.load(open(os.path.join(os.path.dirname(GOLDEN[0]), "ref_accuracy_band.json")))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("name,seed_pos", [("hotel_load100", 3), ("nodeio_1", 2), ("nodeio_1", 1), ("node_load150", 3), ("media_load125", 4),
                                            ("media_load150", 0), ("media_load150", 3)])
-def test_seeded_runs_sit_in_the_references_multi_seed_band(emu_lib, tmp_path, name, seed_pos):
+def test_seeded_runs_sit_in_the_references_multi_seed_band(emu_lib, reference_root, tmp_path, name, seed_pos):
     """tests/golden/ref_accuracy_band.json holds the end-to-end accuracy of the unmodified reference for five values of
     np.random.seed per corpus (oracle/refrun/gen_golden.py --band): its refit draws from the global RNG (hazard H9), so its
     own figure moves by up to 4 pp between seeds.  The command line with the same seed lands on the same figure (the
@@ -169,7 +160,7 @@ def test_seeded_runs_sit_in_the_references_multi_seed_band(emu_lib, tmp_path, na
         os.makedirs(out)
         executor.main(["--relative_path", "data/" + rel + "/", "--compressed", "0", "--cache_rate", "0", "--fix", str(fix), "--test_name", name,
                        "--load_level", "100", "--compress_factor", "1", "--repeat_factor", "1", "--execute_parallel", "0",
-                       "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "10", "--project_root", REF,
+                       "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "10", "--project_root", reference_root,
                        "--engine_library", emu_lib, "--fit", fit, "--seed", str(seed)])
         return pickle.load(open(out + "accuracy_%s_100_1_1_0.0.pickle" % name, "rb"))
 
@@ -194,9 +185,8 @@ def test_unsupported_settings_are_refused(emu_lib, tmp_path):
         assert "not supported here" in str(ei.value)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("rate", ["0.1", "0.3"])
-def test_cache_hit_runs_of_exp2(emu_lib, tmp_path, rate):
+def test_cache_hit_runs_of_exp2(emu_lib, reference_root, tmp_path, rate):
     """exps/exp2/run_experiment.sh: hotel_load150 with --cache_rate R and predictors "3,4,10": cache hits are injected into
     `frontend` (skip mode, one pass with skip spans), `search` runs the two passes; the figures against the reference run
     with the same rate (tests/golden/refskip_*)."""
@@ -207,7 +197,7 @@ def test_cache_hit_runs_of_exp2(emu_lib, tmp_path, rate):
     out = str(tmp_path) + "/"
     executor.main(["--relative_path", "data/hotel_reservation/hotel_load150/", "--compressed", "0", "--cache_rate", rate, "--fix", "2",
                    "--test_name", "x", "--load_level", "150", "--compress_factor", "1", "--repeat_factor", "1", "--execute_parallel", "0",
-                   "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "3,4,10", "--project_root", REF,
+                   "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "3,4,10", "--project_root", reference_root,
                    "--engine_library", emu_lib])
     suffix = "_x_150_1_1_%s.pickle" % float(rate)
     acc = pickle.load(open(out + "accuracy" + suffix, "rb"))
@@ -224,15 +214,14 @@ def test_cache_hit_runs_of_exp2(emu_lib, tmp_path, rate):
     assert acc["FCFS"] < acc[method] and acc["WAP5"] < acc[method]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
-def test_baseline_columns(emu_lib, tmp_path):
+def test_baseline_columns(emu_lib, reference_root, tmp_path):
     """--predictor_indices "3,4,7,10" (what exps/exp1 asks for): WAP5, FCFS and vPath columns next to the accelerated
     predictor, one set of files."""
     from traceweaver_amd import executor
 
     out = str(tmp_path) + "/"
     executor.main(["--relative_path", "data/hotel_reservation/hotel_load100/", "--cache_rate", "0", "--fix", "2", "--test_name", "b",
-                   "--load_level", "100", "--results_directory", out, "--predictor_indices", "3,4,7,10", "--project_root", REF,
+                   "--load_level", "100", "--results_directory", out, "--predictor_indices", "3,4,7,10", "--project_root", reference_root,
                    "--engine_library", emu_lib])   # exps/exp1/run_experiment.sh:40
     acc = pickle.load(open(out + "accuracy_b_100_1_1_0.0.pickle", "rb"))
     proc = pickle.load(open(out + "process_acc_b_100_1_1_0.0.pickle", "rb"))
@@ -241,8 +230,7 @@ def test_baseline_columns(emu_lib, tmp_path):
     assert {k[0] for k in proc} == {"WAP5", "FCFS", "vPath", "MaxScoreBatchSubsetWithSkips"} and len(proc) == 8
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
-def test_load_scaling_through_the_command_line(emu_lib, tmp_path):
+def test_load_scaling_through_the_command_line(emu_lib, reference_root, tmp_path):
     """--compress_factor 2 on hotel_load50 with one replica per service: the units the engine solves are the inputs the
     reference's predictor saw in the frozen run of the same command (tests/golden/refcmp_hotel_load50_x2__*), pass 1
     agrees with it request for request, and the end result stays at the pass-1 level -- the reference's own second pass
@@ -258,7 +246,7 @@ def test_load_scaling_through_the_command_line(emu_lib, tmp_path):
         pickle.dump({"frontend": [0], "search": [0]}, f)
     argv = ["--relative_path", "data/hotel_reservation/hotel_load50/", "--compressed", "0", "--cache_rate", "0", "--fix", "2",
             "--test_name", "hotel_x2", "--load_level", "50", "--compress_factor", "2", "--repeat_factor", "1", "--execute_parallel", "0",
-            "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "10", "--project_root", REF,
+            "--results_directory", out, "--clear_cache", "1", "--predictor_indices", "10", "--project_root", reference_root,
             "--engine_library", emu_lib, "--replicas_file", replicas]
     executor.main(argv)
     acc = pickle.load(open(out + "accuracy_hotel_x2_50_2_1_0.0.pickle", "rb"))
@@ -319,8 +307,7 @@ def test_generated_corpus_end_to_end(emu_lib, tmp_path):
     assert acc["MaxScoreBatchSubsetWithSkips"] > 85.0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/data"), reason="the reference's data directory is not present")
-def test_reference_path_shim(emu_lib, tmp_path):
+def test_reference_path_shim(emu_lib, reference_root, tmp_path):
     """The path and the argument list exps/exp1/run_experiment.sh uses (lines 5-18, 40-46), as a subprocess."""
     import subprocess
     import sys
@@ -328,7 +315,7 @@ def test_reference_path_shim(emu_lib, tmp_path):
     from conftest import REPO
 
     out = str(tmp_path) + "/"
-    env = dict(os.environ, TRACEWEAVER_ROOT=REF, TW_TILE="1", TW_COOP_THREADS="1")
+    env = dict(os.environ, TRACEWEAVER_ROOT=reference_root, TW_TILE="1", TW_COOP_THREADS="1")
     cmd = [sys.executable, os.path.join(REPO, "src/trace_reconstructor/ports/python/executor.py"),
            "--relative_path", "data/hotel_reservation/hotel_load25/", "--compressed", "0", "--cache_rate", "0", "--fix", "2",
            "--test_name", "hotel_test", "--load_level", "25", "--compress_factor", "1", "--repeat_factor", "1",

@@ -1,7 +1,7 @@
 """Native Jaeger-JSON ingest (csrc/tw_ingest.cpp) against (a) a plain-Python restatement of what
 the reference's executor does between reading a directory and calling the predictor (executor.py:287-339,
 755-849,1080-1135; helpers/utils.py:22-32) on generated corpora, and (b) the inputs frozen from the reference
-itself for every shipped corpus (tests/golden/ref_*; needs /root/reference for the JSON files)."""
+itself for every shipped corpus (tests/golden/ref_*; the JSON files from tests/golden/corpus_*.tar.xz)."""
 import glob
 import json
 import os
@@ -13,9 +13,6 @@ from conftest import GOLDEN
 from traceweaver_amd import synth
 from traceweaver_amd.engine import Engine
 from traceweaver_amd.ingest import Corpus
-
-REF_DATA = "/root/reference/data/hotel_reservation"   # (its parent holds all corpora)
-
 
 def python_pipeline(paths, first_span, max_traces=1001):
     """The reference's loader restated with dicts and lists (no span rewriting)."""
@@ -157,16 +154,15 @@ def reference_files(directory, max_files=1000):
     return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(".json"))[:max_files]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's data directory is not present")
 @pytest.mark.parametrize("name,rel,fix", REFERENCE_CORPORA, ids=[c[0] for c in REFERENCE_CORPORA])
-def test_native_ingest_reproduces_the_reference_inputs(emu_lib, name, rel, fix):
+def test_native_ingest_reproduces_the_reference_inputs(emu_lib, reference_root, name, rel, fix):
     """The arrays the native loader hands the engine == the arrays the reference's executor handed TraceWeaverV3 in
     the frozen runs (tests/golden/ref_*): plain Jaeger (hotel), FixSpans2 (media), FixSpans (nodejs)."""
     from traceweaver_amd.ingest import REFERENCE_FIX
 
     first_span, surgery = REFERENCE_FIX[fix]
     c = Corpus(lib_path=emu_lib)
-    counts = c.add_files(reference_files(os.path.join(os.path.dirname(REF_DATA), rel)), first_span=first_span, max_traces=1001, fix=surgery)
+    counts = c.add_files(reference_files(os.path.join(reference_root, "data", rel)), first_span=first_span, max_traces=1001, fix=surgery)
     assert counts["traces"] == 1000 and counts["files_rejected"] == 0 and counts["traces_filtered"] == 0
     units, skipped, _ = c.units()
     golden = {os.path.basename(p)[len("ref_%s__" % name):-4]: p for p in GOLDEN if os.path.basename(p).startswith("ref_%s__" % name)}

@@ -242,7 +242,11 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * ms[3] window construction, ms[4] claim/detect/repair kernels, ms[5] parameter kernels (sort + block
  * sums), ms[6] last tw_fit_mixtures call, ms[7] (a count, not a time) rounds of the span-consumption fixed point,
  * ms[8] / ms[9] host wall clock the last pass spent submitting its first enumeration / in the whole call (a pass of a small
- * batch is bound by that, not by the kernels). */
+ * batch is bound by that, not by the kernels).
+ * Appended: the last tw_stitch_traces (HIP events; with truth set the true forest is built first and is not in these figures):
+ * ms[10] links to grouped trees on the device (without the copies to the host), ms[11] link table, ms[12] pointer-doubling
+ * rounds (incl. the host's one-word read per round), ms[13] rows per root + scan + scatter, ms[14] per-tree order and figures,
+ * ms[15] (a count) doubling rounds. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -302,6 +306,62 @@ int tw_wap5_parents(tw_engine *e, const double *mean, int32_t *parent_out, int32
  * the trace is wrong (exact / top-5) -- combine across ranks with a MAX all-reduce; e2e[2] (may be NULL) = traces
  * right under the exact / the top-5 criterion on this engine alone. */
 int tw_evaluate(tw_engine *e, int64_t *per_unit, uint8_t *trace_flags, int64_t *e2e);
+
+/* ---- from parent arrays to traces (traceweaver_amd/csrc/tw_stitch.h) ---------------------------------------------
+ *
+ * Replaces: ConstructEndToEndTraces (helpers/utils.py:216-252), which files every predicted span under the TRUE trace id
+ * of its request, and the join across services a caller without ground truth otherwise writes on top of the per-service
+ * parent arrays.  A trace is made of two kinds of hop over the rows of the span table (tw_corpus_span_table):
+ *   server row -> client row of the same RPC   observed: row_link (the table's `parent` column)
+ *   client row -> the request that made it     predicted: parent[e][i] = x  =>  link[out_row(e, x)] = in_row(i)
+ * The union is a forest; its trees are the reconstructed traces.  A client row that no unit of the batch covers, a call no
+ * request took and a skip span are holes, and a hole stays a hole: the rows below it form a tree of their own (a fragment).
+ * Ground truth is never used to fill one.
+ *
+ * tw_set_span_rows hands over, after tw_load_batch: in_row / out_row = span-table row of every incoming / outgoing span of
+ * the loaded batch (layouts of in_start / out_start; tw_unit_set has them) and the table itself: n_rows rows with
+ *   row_link  >= 0: for a server row the client row of the same RPC; for a client row it is not read (it may hold the true
+ *             parent).  -1: the row is a root of the table.  -2: the observed caller is not in the table (a server row whose
+ *             client side was deleted): no link, and not a whole trace either
+ *   row_kind  1 server, 2 client, 0 absent (a row that takes part in nothing: a tree of its own)
+ *   row_start / row_end  microseconds.
+ * Checked on the host: ranges, in_row names distinct server rows, out_row distinct client rows, a server row links to a
+ * client row, no row links to itself (TW_ERR_ARG).  tw_load_batch and tw_scale_load drop the maps (after load scaling the
+ * caller permutes in_row / out_row with the permutations tw_scale_load returns and sets them again).
+ *
+ * tw_stitch_traces stitches the assignment of pass `pass` (1 or 2; it must be the resident one, as for tw_get_results) or,
+ * with use_truth != 0, the true assignment of tw_set_truth (`pass` is not read): the comparison object, not a fallback.
+ * Caller-allocated outputs, any may be NULL; trees are numbered in ascending order of their root row:
+ *   root, depth    [n_rows]  root row of the row's tree, links between the row and that root
+ *   tree_off       [n_rows + 1] capacity, n_trees + 1 entries written: tree k owns tree_rows[tree_off[k] .. tree_off[k + 1])
+ *   tree_rows      [n_rows]  rows grouped by tree, ordered by (start, row) inside a tree
+ *   tree_root, tree_latency, tree_flags   [n_rows] capacity, n_trees entries written: root row; latest end of the tree's
+ *                  rows less the start of its root; bit 0 the root is a root of the table (a whole trace -- every other tree
+ *                  is a fragment), bit 1 some request of the tree has an endpoint left unassigned (parent -1; -2, a skip
+ *                  span, is an answer), bit 2 (only after tw_set_truth) the tree is whole and its row set is that of the
+ *                  tree the true assignment gives
+ * counts4 (may be NULL) = whole traces, fragments, trees with an unassigned endpoint, trees with bit 2 (-1 without truth).
+ * Only the selected assignment is stitched (not the top-5 alternatives), and one engine's batch: a sharded run gathers the
+ * parent arrays first (traceweaver_amd/sharding.py) and stitches on one rank.
+ * pass 0 = an assignment handed over with tw_set_parents (layout of tw_results.parent; checked on the host: indices inside
+ * the endpoint's list, no call given to two requests): parent arrays that were not produced by this engine's last pass --
+ * services solved one after the other, or gathered from the ranks of a sharded run.  Dropped like the row maps.
+ * TW_ERR_STATE: before tw_set_span_rows, before the pass named, use_truth without tw_set_truth.  TW_ERR_ARG: the links
+ * hold a cycle -- impossible for a table that passes the checks above with valid parent arrays; a malformed one ends
+ * here (pointer doubling is capped at 32 rounds), never in a hang.  Timing: tw_get_timing slots 10..15. */
+int tw_set_parents(tw_engine *e, const int32_t *parent);
+int tw_set_span_rows(tw_engine *e, int64_t n_rows, const int32_t *in_row, const int32_t *out_row, const int32_t *row_link,
+                     const uint8_t *row_kind, const int64_t *row_start, const int64_t *row_end);
+typedef struct {
+    int32_t *root;
+    int32_t *depth;
+    int64_t *tree_off;
+    int32_t *tree_rows;
+    int32_t *tree_root;
+    int64_t *tree_latency;
+    uint8_t *tree_flags;
+} tw_stitched;
+int tw_stitch_traces(tw_engine *e, int pass, int use_truth, const tw_stitched *out, int64_t *n_trees, int64_t *counts4);
 
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,

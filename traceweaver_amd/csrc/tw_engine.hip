@@ -22,6 +22,7 @@
 #include "tw_skip.h"
 #include "tw_load.h"
 #include "tw_baselines.h"
+#include "tw_stitch.h"
 
 using namespace tw;
 
@@ -177,6 +178,15 @@ struct tw_engine {
     bool scaled_upload = false;             // the batch was uploaded with unit_time_scale (already load-scaled by the caller)
     hipEvent_t ev[EV_COUNT] = {};
     double ms[6] = {0, 0, 0, 0, 0, 0};
+    // tw_set_span_rows / tw_stitch_traces (tw_stitch.h): the row maps of the loaded batch and the scratch of a stitch; dropped by
+    // tw_load_batch (freed with the batch) and tw_scale_load (the lists are re-sorted: the caller permutes the maps and sets them again)
+    StitchDev S{};
+    int32_t* given_parent = nullptr;        // tw_set_parents: an assignment handed over by the caller (stitched as pass 0)
+    bool parents_given = false;
+    bool rows_set = false;
+    int64_t rows_cap = 0;
+    hipEvent_t st_ev[6] = {};
+    double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
 };
 
@@ -238,6 +248,7 @@ void free_all(tw_engine* e) {
     e->allocs.clear();
     e->orig_is = e->orig_ie = e->orig_os = e->orig_oe = nullptr; e->orig_truth = e->orig_trace = nullptr;
     e->truth = nullptr; e->in_trace = nullptr; e->trace_bad = nullptr; e->eval_counts = nullptr; e->n_traces = 0; e->trace_cap = 0;
+    e->S = StitchDev{}; e->rows_set = false; e->rows_cap = 0; e->given_parent = nullptr; e->parents_given = false;
     e->state = ST_EMPTY;
 }
 
@@ -915,6 +926,8 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     HIPCHK(hipMemcpyAsync(const_cast<UnitDev*>(P.units), e->units.data(), sizeof(UnitDev) * e->units.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->state = ST_LOADED; e->pass1_done = false;
+    e->parents_given = false;
+    e->rows_set = false;   // every list was re-sorted: in_row / out_row no longer name the spans at these positions
     for (int E = 0; E <= kMaxEp; E++) { e->wide_pass1[E] = -1; e->hard_pass1[E] = -1; e->split_pass1[E] = -1; }
     return TW_OK;
 }
@@ -1011,6 +1024,8 @@ void tw_destroy(tw_engine* e) {
         for (int j = 0; j < 3; j++)
             if (e->post_join[i][j]) (void)hipEventDestroy(e->post_join[i][j]);
     }
+    for (int i = 0; i < 6; i++)
+        if (e->st_ev[i]) (void)hipEventDestroy(e->st_ev[i]);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1738,6 +1753,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 7) ms[7] = (double)e->rounds;
     if (n > 8) ms[8] = e->host_ms[0];
     if (n > 9) ms[9] = e->host_ms[1];
+    for (int i = 0; i < 6 && 10 + i < n; i++) ms[10 + i] = e->st_ms[i];   // the last tw_stitch_traces
     return TW_OK;
 }
 
@@ -1882,6 +1898,192 @@ int tw_evaluate(tw_engine* e, int64_t* per_unit, uint8_t* trace_flags, int64_t* 
         per_unit[u * 4 + 3] = (int64_t)h[(size_t)u * 4 + 3];
     }
     if (e2e != nullptr) { e2e[0] = (int64_t)h[(size_t)nc - 2]; e2e[1] = (int64_t)h[(size_t)nc - 1]; }
+    return TW_OK;
+}
+
+/* ---- from parent arrays to traces (tw_stitch.h) ------------------------------------------------------------------- */
+int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const int32_t* out_row, const int32_t* row_link,
+                     const uint8_t* row_kind, const int64_t* row_start, const int64_t* row_end) {
+    if (e == nullptr || !in_row || !out_row || !row_link || !row_kind || !row_start || !row_end) return TW_ERR_ARG;
+    if (e->state < ST_LOADED) return fail(e, TW_ERR_STATE, "tw_set_span_rows before tw_load_batch");
+    if (n_rows < 1 || n_rows > 0x7ffffff0ll) return fail(e, TW_ERR_ARG, "tw_set_span_rows: n_rows outside [1, 2^31 - 16]");
+    HIPCHK(hipSetDevice(e->device));
+    const Dev& P = e->P;
+    // the kernels index the row arrays with these values: range, kind and uniqueness are checked here, once, on the host
+    for (int64_t r = 0; r < n_rows; r++) {
+        if (row_kind[r] > 2) return fail(e, TW_ERR_ARG, "tw_set_span_rows: row_kind outside {0 absent, 1 server, 2 client}");
+        const int32_t l = row_link[r];
+        if (l < -2 || l >= n_rows || l == r) return fail(e, TW_ERR_ARG, "tw_set_span_rows: row_link outside [-2, n_rows) or a row linked to itself");
+        if (row_kind[r] == 1 && l >= 0 && row_kind[l] != 2)
+            return fail(e, TW_ERR_ARG, "tw_set_span_rows: a server row's link must name a client row (the caller's side of the same RPC)");
+    }
+    std::vector<uint8_t> seen((size_t)n_rows, 0);
+    for (int64_t k = 0; k < P.n_in_total + P.n_out_total; k++) {
+        const bool in = k < P.n_in_total;
+        const int32_t r = in ? in_row[k] : out_row[k - P.n_in_total];
+        if (r < 0 || r >= n_rows || row_kind[r] != (in ? 1 : 2) || seen[(size_t)r])
+            return fail(e, TW_ERR_ARG, in ? "tw_set_span_rows: in_row must name distinct server rows of the table" : "tw_set_span_rows: out_row must name distinct client rows of the table");
+        seen[(size_t)r] = 1;
+    }
+    StitchDev& S = e->S;
+    int rc;
+#define SALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
+    if (S.link == nullptr || n_rows > e->rows_cap) {   // (freed with the batch)
+        int32_t *in_d, *out_d, *link_d; uint8_t* kind_d; int64_t *start_d, *end_d;
+        SALLOC(in_d, P.n_in_total); SALLOC(out_d, P.n_out_total); SALLOC(link_d, n_rows); SALLOC(kind_d, n_rows); SALLOC(start_d, n_rows); SALLOC(end_d, n_rows);
+        S.in_row = in_d; S.out_row = out_d; S.row_link = link_d; S.row_kind = kind_d; S.row_start = start_d; S.row_end = end_d;
+        SALLOC(S.link, n_rows); SALLOC(S.state_a, n_rows); SALLOC(S.state_b, n_rows);
+        SALLOC(S.root, n_rows); SALLOC(S.depth, n_rows); SALLOC(S.true_root, n_rows); SALLOC(S.una, n_rows); SALLOC(S.bad, n_rows);
+        SALLOC(S.cursor, n_rows); SALLOC(S.chunk_sum, n_rows / kStitchScanItems + 2);
+        SALLOC(S.rows_tmp, n_rows); SALLOC(S.tree_rows, n_rows); SALLOC(S.tree_root, n_rows);
+        SALLOC(S.tree_off, n_rows + 1); SALLOC(S.tree_latency, n_rows); SALLOC(S.tree_flags, n_rows);
+        SALLOC(S.totals, 4); SALLOC(S.changed, kStitchMaxRounds); SALLOC(S.err, 1);
+        e->rows_cap = n_rows;
+    }
+#undef SALLOC
+    S.n_rows = n_rows;
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(S.in_row), in_row, sizeof(int32_t) * (size_t)P.n_in_total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(S.out_row), out_row, sizeof(int32_t) * (size_t)P.n_out_total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(S.row_link), row_link, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<uint8_t*>(S.row_kind), row_kind, (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(S.row_start), row_start, sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(S.row_end), row_end, sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 6; i++)
+        if (e->st_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->st_ev[i]));
+    e->rows_set = true;
+    return TW_OK;
+}
+
+int tw_set_parents(tw_engine* e, const int32_t* parent) {
+    if (e == nullptr || parent == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED) return fail(e, TW_ERR_STATE, "tw_set_parents before tw_load_batch");
+    HIPCHK(hipSetDevice(e->device));
+    // k_stitch_links indexes out_row with these values and relies on a call being given to one request at most
+    std::vector<uint8_t> taken;
+    for (const UnitDev& U : e->units)
+        for (int ep = 0; ep < U.E; ep++) {
+            const int64_t len = U.ep_off[ep + 1] - U.ep_off[ep];
+            taken.assign((size_t)len, 0);
+            const int32_t* p = parent + U.ie_off + (int64_t)ep * U.n_in;
+            for (int64_t i = 0; i < U.n_in; i++) {
+                if (p[i] < -2 || p[i] >= len) return fail(e, TW_ERR_ARG, "tw_set_parents: parent outside [-2, spans of the endpoint)");
+                if (p[i] >= 0 && taken[(size_t)p[i]]++) return fail(e, TW_ERR_ARG, "tw_set_parents: a call is given to two requests");
+            }
+        }
+    if (e->given_parent == nullptr) { const int rc = dev_alloc(e, &e->given_parent, e->n_ie); if (rc != TW_OK) return rc; }
+    HIPCHK(hipMemcpyAsync(e->given_parent, parent, sizeof(int32_t) * (size_t)e->n_ie, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->parents_given = true;
+    return TW_OK;
+}
+
+namespace {
+
+// link table of `src` (parent arrays of a pass, or the true ones) -> root of every row in root_out (and its depth); `final`: the
+// forest that is grouped afterwards (rows per root are counted, trees compared with true_root if given).  *rounds = jump rounds run.
+int stitch_forest(tw_engine* e, const int32_t* src, int32_t* root_out, int32_t* depth_out, bool final, const int32_t* true_root, int* rounds) {
+    const Dev& P = e->P;
+    const StitchDev& S = e->S;
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 rows((unsigned)((S.n_rows + threads - 1) / threads)), tb(threads);
+    HIPCHK(hipMemsetAsync(S.changed, 0, sizeof(int32_t) * kStitchMaxRounds, e->stream));
+    hipLaunchKernelGGL(k_stitch_init, rows, tb, 0, e->stream, S);
+    int max_e = 1;
+    for (const UnitDev& U : e->units) max_e = std::max(max_e, (int)U.E);
+    hipLaunchKernelGGL(k_stitch_links, dim3((unsigned)P.n_tiles, (unsigned)max_e), dim3((unsigned)e->tile), 0, e->stream, P, S, src);
+    HIPCHK(hipGetLastError());
+    if (final) HIPCHK(hipEventRecord(e->st_ev[1], e->stream));
+    unsigned long long *a = S.state_a, *b = S.state_b;
+    int round = 0;
+    for (;; round++) {
+        if (round == kStitchMaxRounds)
+            return fail(e, TW_ERR_ARG, "tw_stitch_traces: the links do not settle in 32 doubling rounds: row_link holds a cycle");
+        hipLaunchKernelGGL(k_stitch_jump, rows, tb, 0, e->stream, S, (const unsigned long long*)a, b, round == 0 ? 1 : 0, round);
+        HIPCHK(hipGetLastError());
+        int32_t moved = 0;   // one word per round: the loop ends at the first quiet one
+        HIPCHK(hipMemcpyAsync(&moved, S.changed + round, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        std::swap(a, b);
+        if (!moved) break;
+    }
+    *rounds = round + 1;
+    if (final) HIPCHK(hipEventRecord(e->st_ev[2], e->stream));
+    hipLaunchKernelGGL(k_stitch_count, rows, tb, 0, e->stream, S, (const unsigned long long*)a, root_out, depth_out, final ? 1 : 0, true_root);
+    HIPCHK(hipGetLastError());
+    return TW_OK;
+}
+
+}  // namespace
+
+int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* out, int64_t* n_trees, int64_t* counts4) {
+    if (e == nullptr || out == nullptr || n_trees == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set)
+        return fail(e, TW_ERR_STATE, "tw_stitch_traces before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
+    if (use_truth) {
+        if (e->truth == nullptr) return fail(e, TW_ERR_STATE, "tw_stitch_traces(use_truth) before tw_set_truth");
+    } else {
+        const bool ok = (pass == 0 && e->parents_given) || (pass == 1 && (e->state == ST_PASS1 || e->state == ST_MIX)) || (pass == 2 && e->state == ST_PASS2);
+        if (!ok) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    const StitchDev& S = e->S;
+    const bool has_truth = e->truth != nullptr;
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 rows((unsigned)((S.n_rows + threads - 1) / threads)), tb(threads);
+    HIPCHK(hipMemsetAsync(S.totals, 0, sizeof(unsigned long long) * 4, e->stream));
+    HIPCHK(hipMemsetAsync(S.err, 0, sizeof(int32_t), e->stream));
+    HIPCHK(hipEventRecord(e->st_ev[0], e->stream));
+    int rounds = 0, rc;
+    if (has_truth && !use_truth) {   // the true forest first: what bit 2 of the flags compares with
+        rc = stitch_forest(e, e->truth, S.true_root, nullptr, false, nullptr, &rounds);
+        if (rc != TW_OK) return rc;
+        HIPCHK(hipEventRecord(e->st_ev[0], e->stream));   // (timed: the stitch of the assignment alone)
+    }
+    rc = stitch_forest(e, use_truth ? e->truth : (pass == 0 ? e->given_parent : e->P.parent), S.root, S.depth, true, (has_truth && !use_truth) ? S.true_root : nullptr, &rounds);
+    if (rc != TW_OK) return rc;
+    const int64_t n_chunks = (S.n_rows + (int64_t)threads * kStitchScanItems - 1) / ((int64_t)threads * kStitchScanItems);
+    hipLaunchKernelGGL(k_stitch_scan_sums, dim3((unsigned)n_chunks), tb, 0, e->stream, S);
+    hipLaunchKernelGGL(k_stitch_scan_chunks, dim3(1), tb, 0, e->stream, S, n_chunks);
+    hipLaunchKernelGGL(k_stitch_scan_write, dim3((unsigned)n_chunks), tb, 0, e->stream, S);
+    hipLaunchKernelGGL(k_stitch_scatter, rows, tb, 0, e->stream, S);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->st_ev[3], e->stream));
+    // one wavefront per kStitchTrees trees, persistent: at most 8192 workgroups of four
+    const unsigned gthreads = e->coop >= 64 ? 64u * kStitchWaves : (unsigned)e->coop;
+    const int64_t want = (S.n_rows / kStitchTrees + 1 + kStitchWaves - 1) / kStitchWaves;
+    hipLaunchKernelGGL(k_stitch_group, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, has_truth ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->st_ev[4], e->stream));
+    unsigned long long totals[4] = {0, 0, 0, 0};
+    int32_t err = 0;
+    HIPCHK(hipMemcpyAsync(totals, S.totals, sizeof(totals), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&err, S.err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (err != 0) return fail(e, TW_ERR_ARG, "tw_stitch_traces: the links hold a cycle (a row is its own ancestor): malformed row_link / row maps");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[0], e->st_ev[4])); e->st_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[0], e->st_ev[1])); e->st_ms[1] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[1], e->st_ev[2])); e->st_ms[2] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[2], e->st_ev[3])); e->st_ms[3] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[3], e->st_ev[4])); e->st_ms[4] = ms;
+    e->st_ms[5] = (double)rounds;
+    const int64_t nt = (int64_t)(totals[0] >> 32);
+    *n_trees = nt;
+    if (counts4 != nullptr) {
+        counts4[0] = (int64_t)totals[1]; counts4[1] = nt - (int64_t)totals[1]; counts4[2] = (int64_t)totals[2];
+        counts4[3] = has_truth ? (int64_t)totals[3] : -1;
+    }
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+    D2H(out->root, S.root, sizeof(int32_t) * (size_t)S.n_rows);
+    D2H(out->depth, S.depth, sizeof(int32_t) * (size_t)S.n_rows);
+    D2H(out->tree_off, S.tree_off, sizeof(int64_t) * (size_t)(nt + 1));
+    D2H(out->tree_rows, S.tree_rows, sizeof(int32_t) * (size_t)S.n_rows);
+    D2H(out->tree_root, S.tree_root, sizeof(int32_t) * (size_t)nt);
+    D2H(out->tree_latency, S.tree_latency, sizeof(int64_t) * (size_t)nt);
+    D2H(out->tree_flags, S.tree_flags, (size_t)nt);
+#undef D2H
+    HIPCHK(hipStreamSynchronize(e->stream));
     return TW_OK;
 }
 

@@ -175,6 +175,7 @@ class Engine(object):
             batch_size, batch_size_mis, _ffi.TW_TOPK, _vp(arrays["unit_time_scale"]),
             ctypes.cast(skip_arr, ctypes.c_void_p) if skip_arr is not None else ctypes.c_void_p(0), _vp(arrays["unit_part"]))
         self._check(self._lib.tw_load_batch(self._h, ctypes.byref(b), 0))
+        self._last_pass, self._n_rows = 0, 0
         self._in_off = in_off
         self._ie_off = np.concatenate([[0], np.cumsum([u.n_in * u.E for u in units])]).astype(np.int64)
         self._slot_off = np.concatenate([[0], np.cumsum([u.nslot for u in units])]).astype(np.int64)
@@ -184,9 +185,11 @@ class Engine(object):
 
     def run_pass1(self):
         self._check(self._lib.tw_run_pass1(self._h))
+        self._last_pass = 1
 
     def run_pass2(self):
         self._check(self._lib.tw_run_pass2(self._h))
+        self._last_pass = 2
 
     def gaps(self):
         """Per unit: [nslot, n_in] gap samples of the pass-1 assignment (NaN = dropped / unscored slot)."""
@@ -331,6 +334,7 @@ class Engine(object):
         op = np.zeros(n_out, dtype=np.int32)
         ts = np.zeros(len(self.units), dtype=np.float64)
         self._check(self._lib.tw_scale_load(self._h, _vp(f), _vp(tr), _vp(ip), _vp(op), _vp(ts)))
+        self._last_pass = 0
         out, o = [], 0
         for k, u in enumerate(self.units):
             a, b = int(self._in_off[k]), int(self._in_off[k + 1])
@@ -380,6 +384,61 @@ class Engine(object):
         if e2e is None:
             return out
         return (out, (int(e2e[0]), int(e2e[1])), flags) if trace_flags else (out, (int(e2e[0]), int(e2e[1])))
+
+    # ------------------------------------------------------------------------------------------
+    def set_span_rows(self, in_rows, out_rows, row_link, row_kind, row_start, row_end):
+        """The span-table rows of the loaded batch and the table's observed links (tw_set_span_rows; traces.rows_from_units
+        builds the arguments): per unit in_rows [n_in] and out_rows = one array per endpoint, then the table's columns
+        [n_rows].  load() and scale_load() drop them."""
+        ir = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.int32).ravel() for a in in_rows]), dtype=np.int32)
+        flat = [np.asarray(a, dtype=np.int32).ravel() for per in out_rows for a in per]
+        orow = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0, np.int32), dtype=np.int32)
+        if len(ir) != self._in_off[-1] or len(orow) != sum(int(u.out_off[-1]) for u in self.units) or \
+                any(len(a) != int(u.out_off[e + 1] - u.out_off[e]) for u, per in zip(self.units, out_rows) for e, a in enumerate(per)):
+            raise ValueError("row maps do not match the loaded batch")
+        link = np.ascontiguousarray(row_link, dtype=np.int32)
+        kind = np.ascontiguousarray(row_kind, dtype=np.uint8)
+        start = np.ascontiguousarray(row_start, dtype=np.int64)
+        end = np.ascontiguousarray(row_end, dtype=np.int64)
+        if not (len(link) == len(kind) == len(start) == len(end)):
+            raise ValueError("the table's columns differ in length")
+        self._check(self._lib.tw_set_span_rows(self._h, len(link), _vp(ir), _vp(orow), _vp(link), _vp(kind), _vp(start), _vp(end)))
+        self._n_rows = len(link)
+
+    def set_parents(self, parents):
+        """An assignment that this engine's last pass did not produce (per unit [E, n_in]; services solved one after the
+        other, or gathered from other ranks): stitch(pass_=0) stitches it (tw_set_parents)."""
+        p = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.int32).ravel() for a in parents]), dtype=np.int32)
+        if len(p) != self._ie_off[-1]:
+            raise ValueError("parent arrays do not match the loaded batch")
+        self._check(self._lib.tw_set_parents(self._h, _vp(p)))
+
+    def stitch(self, pass_=None, truth=False):
+        """The assignment of a pass (None = the last pass run) -- or, with truth=True, the true one of set_truth -- joined
+        with the observed links into whole traces on the device (tw_stitch_traces).  Returns traces.StitchedTraces."""
+        from .traces import StitchedTraces
+
+        n = int(getattr(self, "_n_rows", 0))
+        root, depth, tree_rows = (np.empty(n, dtype=np.int32) for _ in range(3))
+        tree_off = np.empty(n + 1, dtype=np.int64)
+        tree_root = np.empty(n, dtype=np.int32)
+        tree_latency = np.empty(n, dtype=np.int64)
+        tree_flags = np.empty(n, dtype=np.uint8)
+        out = _ffi.Stitched(*[_vp(a) for a in (root, depth, tree_off, tree_rows, tree_root, tree_latency, tree_flags)])
+        nt = ctypes.c_int64(0)
+        counts = np.zeros(4, dtype=np.int64)
+        which = int(getattr(self, "_last_pass", 0)) if pass_ is None else int(pass_)
+        self._check(self._lib.tw_stitch_traces(self._h, which, 1 if truth else 0, ctypes.byref(out), ctypes.byref(nt), _vp(counts)))
+        k = int(nt.value)
+        return StitchedTraces(root, depth, tree_off[:k + 1].copy(), tree_rows, tree_root[:k].copy(), tree_latency[:k].copy(),
+                              tree_flags[:k].copy(), counts)
+
+    def stitch_timing(self):
+        """The last stitch on the device (HIP events, ms): whole (without the copies to the host), link table, doubling
+        rounds, rows per root + scan + scatter, per-tree order and figures; `rounds` = doubling rounds."""
+        ms = np.zeros(16, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 16))
+        return dict(zip(("stitch", "links", "jump", "scatter", "group", "rounds"), ms[10:16].tolist()))
 
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):

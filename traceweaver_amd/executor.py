@@ -87,6 +87,10 @@ def parse_args(argv=None):
                     help="go on when services of the corpus cannot be solved here (skip mode, < 2 requests, cyclic call order); they are "
                          "recorded under 'left_out' in the confidence_scores pickle.  Default: stop, because the accuracy files would "
                          "otherwise count those services as right")
+    ap.add_argument("--stitch_out", type=q, default=None,
+                    help="write the traces predictor 10's assignments make together to this .npz (traceweaver_amd/traces.py: the per-service "
+                         "parent arrays joined with the observed hops on the GPU, tw_stitch_traces) and print their counts.  Default: off, "
+                         "nothing changes")
     ap.add_argument("--engine_library", type=q, default=None, help=argparse.SUPPRESS)   # tests: host-emulation build
     args = ap.parse_args(argv)
     if args.relative_path is None and args.absolute_path is None:
@@ -112,6 +116,8 @@ def unsupported(args):
         problems.append("--compressed 1")
     if args.parallel or args.instrumented:
         problems.append("--parallel / --instrumented")
+    if args.stitch_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--stitch_out without predictor 10 or with --cache_rate > 0 (a skip-mode service is solved in a batch of its own)")
     return problems
 
 
@@ -141,6 +147,31 @@ def scale_load(units, args, trace_id, corpus):
         out.append(IngestedUnit(s.arrays, s.true_parent, u.in_trace[s.in_perm], u.service, u.in_ep, u.out_eps, u.in_rows[s.in_perm],
                                 [r[p] for r, p in zip(u.out_rows, s.out_perm)], u.process_id))
     return out, factors, ranks
+
+
+def stitch_out(args, corpus, units, table, parents, n_traces, total, right):
+    """--stitch_out: all services in one batch, the assignments they were given, the span table's rows -> traces on the device."""
+    from . import traces
+    from .engine import Engine
+
+    eng = Engine(args.device, lib_path=args.engine_library)
+    eng.load([u.arrays for u in units])
+    eng.set_truth([u.true_parent for u in units], [u.in_trace for u in units], n_traces)
+    eng.set_span_rows(*traces.rows_from_units(units, table))
+    eng.set_parents(parents)
+    st = eng.stitch(0)
+    eng.close()
+    traces.write_npz(args.stitch_out, st, corpus, table)
+    c = st.counts.tolist()
+    print("Stitched traces: %d whole, %d fragments, %d with unassigned calls; exact vs ground truth: %d of %d" % (c[0], c[1], c[2], c[3], total))
+    calling = {corpus.string(x) for x in np.unique(table["service"][table["kind"] == 2])}
+    left = sorted(calling - {u.service for u in units})
+    if left:
+        print("Not in the stitch (their calls are holes, the spans below them fragments): %s" % ", ".join(left))
+    elif c[3] < right:
+        raise RuntimeError("stitched traces: %d exact, the accuracy reduction counts %d traces right" % (c[3], right))
+    elif c[3] > right:   # bit 2 compares row sets: two requests of one service in one trace that swap their calls keep the set
+        print("(%d traces hold the true spans under another assignment of calls to requests: right as a set, wrong per request)" % (c[3] - right))
 
 
 def run(args):
@@ -316,6 +347,8 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
+            if args.stitch_out:
+                stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()))
         else:
             method = BASELINES[index]
             parents, bad, all_options = [], np.zeros(n_traces, dtype=np.uint8), []

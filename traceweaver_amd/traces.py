@@ -1,0 +1,142 @@
+"""From parent arrays to traces: the arguments and the result of Engine.stitch (tw_stitch_traces, csrc/tw_stitch.h).
+
+The engine answers per service: parent[e][i] = the call of endpoint e that belongs to request i.  A trace is what these
+answers say together with the hops that are observed (an RPC is logged on both sides: the callee's server span names the
+caller's client span).  `rows_from_units` builds what Engine.set_span_rows takes from the ingest's units and span table,
+`StitchedTraces` is what Engine.stitch returns, `write_npz` stores it with the (trace id, span id) strings of every row,
+and `stitch_host` restates the device's computation in numpy -- test and cross-check code; the product path is the device.
+"""
+import numpy as np
+
+WHOLE, UNASSIGNED, EXACT = 1, 2, 4   # bits of tree_flags
+
+
+class StitchedTraces(object):
+    """root / depth [n_rows]: root row of every row's tree and the links between the row and it; tree k (trees in
+    ascending order of root row) owns tree_rows[tree_off[k]:tree_off[k + 1]], ordered by (start, row); tree_root /
+    tree_latency / tree_flags [n_trees] (WHOLE: the root is a root of the span table, every other tree is a fragment;
+    UNASSIGNED: some request of the tree has an endpoint without a call; EXACT, with ground truth set: whole and the same
+    rows as the true trace); counts = whole traces, fragments, trees with an unassigned endpoint, exact trees (-1: no truth)."""
+
+    FIELDS = ("root", "depth", "tree_off", "tree_rows", "tree_root", "tree_latency", "tree_flags", "counts")
+
+    def __init__(self, root, depth, tree_off, tree_rows, tree_root, tree_latency, tree_flags, counts):
+        self.root, self.depth, self.tree_off, self.tree_rows = root, depth, tree_off, tree_rows
+        self.tree_root, self.tree_latency, self.tree_flags = tree_root, tree_latency, tree_flags
+        self.counts = np.asarray(counts, dtype=np.int64)
+
+    @property
+    def n_trees(self):
+        return len(self.tree_root)
+
+    def __len__(self):
+        return self.n_trees
+
+    def trace(self, k):
+        """Tree k: {"root", "rows" (ordered by start), "latency", "whole", "unassigned", "exact"}."""
+        k = int(k)
+        if not 0 <= k < self.n_trees:
+            raise IndexError(k)
+        f = int(self.tree_flags[k])
+        return {"root": int(self.tree_root[k]), "rows": self.tree_rows[int(self.tree_off[k]):int(self.tree_off[k + 1])],
+                "latency": int(self.tree_latency[k]), "whole": bool(f & WHOLE), "unassigned": bool(f & UNASSIGNED), "exact": bool(f & EXACT)}
+
+    def __iter__(self):
+        return (self.trace(k) for k in range(self.n_trees))
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def rows_from_units(units, table, deleted=None):
+    """Arguments of Engine.set_span_rows for a batch of IngestedUnits (in load order) and Corpus.span_table():
+    (in_rows, out_rows, row_link, row_kind, row_start, row_end).  `deleted`: rows of calls that were taken out of the batch
+    (skipmode.cache_hits removes the calls a cache hit did not make): they are absent from the table handed over, and the
+    server spans that name one of them as their caller have no observed link (-2) -- they are not roots of the table either."""
+    link = np.array(table["parent"], dtype=np.int32)
+    kind = np.array(table["kind"], dtype=np.uint8)
+    start = np.asarray(table["start"], dtype=np.int64)
+    end = start + np.asarray(table["duration"], dtype=np.int64)
+    if deleted is not None and len(deleted):
+        gone = np.zeros(len(link), dtype=bool)
+        gone[np.asarray(deleted, dtype=np.int64)] = True
+        link[(link >= 0) & gone[np.maximum(link, 0)]] = -2
+        kind[gone] = 0
+    return ([u.in_rows for u in units], [list(u.out_rows) for u in units], link, kind, start, end)
+
+
+def stitch_host(units, parents, in_rows, out_rows, row_link, row_kind, row_start, row_end, truth=None):
+    """What tw_stitch_traces computes, in plain numpy.  units: the UnitArrays of the batch, parents: per unit [E, n_in]
+    (the assignment to stitch), truth: per unit the true [E, n_in] arrays when the EXACT bit is wanted."""
+    row_link = np.asarray(row_link, dtype=np.int64)
+    row_kind = np.asarray(row_kind)
+    n = len(row_link)
+    rows = np.arange(n, dtype=np.int64)
+
+    def forest(par):
+        link = np.where((row_kind == 1) & (row_link >= 0), row_link, -1)
+        una = np.zeros(n, dtype=bool)
+        for u, p, ir, per in zip(units, par, in_rows, out_rows):
+            ir = np.asarray(ir, dtype=np.int64)
+            for e in range(u.E):
+                x = np.asarray(p[e], dtype=np.int64)
+                ok = (x >= 0) & (x < len(per[e]))
+                link[np.asarray(per[e], dtype=np.int64)[x[ok]]] = ir[ok]
+                una[ir[x == -1]] = True
+        root = np.where(link >= 0, link, rows)
+        depth = (link >= 0).astype(np.int64)
+        for _ in range(64):
+            nxt = root[root]
+            if np.array_equal(nxt, root):
+                break
+            depth = depth + depth[root]
+            root = nxt
+        else:
+            raise ValueError("the links hold a cycle")
+        if np.any((root == rows) & (link >= 0)):
+            raise ValueError("the links hold a cycle")
+        return root, depth, una
+
+    root, depth, una = forest(parents)
+    order = np.lexsort((rows, np.asarray(row_start), root))
+    tree_root = np.unique(root)
+    counts = np.bincount(root, minlength=n)[tree_root]
+    tree_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    k_of = np.searchsorted(tree_root, root)
+    latest = np.full(len(tree_root), np.iinfo(np.int64).min, dtype=np.int64)
+    np.maximum.at(latest, k_of, np.asarray(row_end, dtype=np.int64))
+    whole = (row_kind[tree_root] == 1) & (row_link[tree_root] == -1)
+    t_una = np.zeros(len(tree_root), dtype=bool)
+    t_una[k_of[una]] = True
+    flags = whole * WHOLE + t_una * UNASSIGNED
+    n_exact = -1
+    if truth is not None:
+        t_root = forest(truth)[0]
+        bad = np.zeros(n, dtype=bool)
+        diff = t_root != root
+        bad[root[diff]] = True
+        bad[t_root[diff]] = True
+        exact = whole & ~bad[tree_root]
+        flags = flags + exact * EXACT
+        n_exact = int(exact.sum())
+    counts4 = np.array([int(whole.sum()), int(len(tree_root) - whole.sum()), int(t_una.sum()), n_exact], dtype=np.int64)
+    return StitchedTraces(root.astype(np.int32), depth.astype(np.int32), tree_off, order.astype(np.int32), tree_root.astype(np.int32),
+                          latest - np.asarray(row_start, dtype=np.int64)[tree_root], flags.astype(np.uint8), counts4)
+
+
+def write_npz(path, stitched, corpus, table=None):
+    """The stitched traces as one .npz that can be read without the corpus: the arrays of StitchedTraces plus, per row of
+    the span table, the trace id the span was logged under (`row_trace_id`), its span id, service and start / end."""
+    table = corpus.span_table() if table is None else table
+    names = corpus.trace_names()
+    trace_ids = np.array([corpus.string(x) for x in names])
+    service_ids, inverse = np.unique(np.asarray(table["service"]), return_inverse=True)
+    services = np.array([corpus.string(x) for x in service_ids])
+    start = np.asarray(table["start"], dtype=np.int64)
+    with open(path, "wb") as f:
+        np.savez_compressed(
+            f, root=stitched.root, depth=stitched.depth, tree_off=stitched.tree_off, tree_rows=stitched.tree_rows,
+            tree_root=stitched.tree_root, tree_latency=stitched.tree_latency, tree_flags=stitched.tree_flags, counts=stitched.counts,
+            row_trace_id=trace_ids[np.asarray(table["trace"])], row_span_id=np.array([corpus.string(x) for x in table["span_id"]]),
+            row_service=services[inverse], row_kind=np.asarray(table["kind"]), row_start=start,
+            row_end=start + np.asarray(table["duration"], dtype=np.int64))

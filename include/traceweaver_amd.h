@@ -246,7 +246,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * Appended: the last tw_stitch_traces (HIP events; with truth set the true forest is built first and is not in these figures):
  * ms[10] links to grouped trees on the device (without the copies to the host), ms[11] link table, ms[12] pointer-doubling
  * rounds (incl. the host's one-word read per round), ms[13] rows per root + scan + scatter, ms[14] per-tree order and figures,
- * ms[15] (a count) doubling rounds. */
+ * ms[15] (a count) doubling rounds.
+ * The last tw_attribute_traces (HIP events): ms[16] per-tree kernel, ms[17] selection (flags, sort, mark; incl. the host's
+ * read of the eligible count), ms[18] group reduction. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -362,6 +364,58 @@ typedef struct {
     uint8_t *tree_flags;
 } tw_stitched;
 int tw_stitch_traces(tw_engine *e, int pass, int use_truth, const tw_stitched *out, int64_t *n_trees, int64_t *counts4);
+
+/* ---- latency attribution on the stitched forest (csrc/tw_attr.h) ----------------------------------------------
+ *
+ * Replaces: the consumer of reconstructed traces, src/query_engine/delay_culprit.py:19-28 -- "FOR all end to end requests
+ * WHICH were in the top X %ile response latency bracket AND were initiated after time Y, FIND the worst performing service
+ * AND its mean service latency for these requests" -- and its walk over every trace on the host, delay_culprit.py:30-97.
+ * Both calls work on the forest of the last tw_stitch_traces call (a pass, pass 0 or the truth), which stays on the device.
+ *
+ * Definitions (integer microseconds; a row with end < start counts as end = start; the children of row p are the rows c
+ * with link[c] == p):
+ *   self_time[p]   (end_p - start_p) less the measure of the union of the children's intervals clipped to [start_p, end_p]
+ *   path_time[p]   p's share of the critical path of its tree.  walk(p, lo, hi), [lo, hi] inside p's interval, the root walked
+ *                  with its own: cursor = hi; among the children with cs = max(start_c, lo) < cursor and end_c > cs the one
+ *                  with the greatest ce = min(end_c, cursor) is taken (ties: the smaller cs, then the smaller row);
+ *                  path_time[p] += cursor - ce; walk(c, cs, ce); cursor = cs; again.  No such child: path_time[p] +=
+ *                  cursor - lo.  Rows never walked have 0, so the path times of a tree sum to its root's duration.
+ *   groups         row_group [n_rows] in [0, n_groups), -1 = not counted (normally the span table's interned service).
+ *                  tree_top_group = the group with the largest summed path_time among those with a row on the tree's path
+ *                  (ties: the smallest id), -1 if there is none.
+ *   selection      eligible = trees whose flags hold every bit of need_flags and none of skip_flags (the reference keeps whole
+ *                  traces without an unassigned call: need 1, skip 2).  Ordered by (tree_latency, tree), k = (int64)
+ *                  (percentile * n_eligible) in binary64 as int(0.95 * len(...)) gives it; the trees of rank >= k whose root
+ *                  starts in [start_min, start_max) are selected: the percentile first, the window second, as in the reference.
+ *   per group, over the selected trees: path_time, path_rows (rows on a path), self_time, span_time, span_rows (duration and
+ *                  count of all the group's rows: span_time / span_rows is the mean service latency), trees (selected trees
+ *                  with a row of the group on the path), top_trees (selected trees whose tree_top_group the group is)
+ *   summary6       eligible trees, selected trees, k, the latency at rank k (0 without eligible trees), the culprit = the
+ *                  group with the largest path_time among those with path_rows > 0 (ties: the smallest id; -1: none), trees
+ *
+ * tw_set_row_groups: after tw_set_span_rows; ranges are checked on the host; dropped whenever the row maps are dropped.
+ * tw_attribute_traces: outputs are caller-allocated, any may be NULL: link, self_time, path_time [n_rows]; tree_* [n_trees of
+ * the stitch]; group_* [n_groups].  TW_ERR_STATE: before a stitch, before tw_set_row_groups, after anything that drops the
+ * stitched forest (tw_load_batch, tw_scale_load, tw_set_span_rows, tw_run_pass1 / 2).  TW_ERR_ARG: percentile outside [0, 1),
+ * start_min > start_max, links that leave their tree (never after a stitch that returned TW_OK).  Covers the selected
+ * assignment only and one engine's batch.  Everything is integer arithmetic; the atomics are 64-bit integer adds of which only
+ * the sum is read: results do not depend on scheduling.  Timing: tw_get_timing slots 16..18 (per-tree kernel, selection,
+ * group reduction; HIP events, ms). */
+typedef struct {
+    double percentile;
+    int64_t start_min, start_max;
+    uint32_t need_flags, skip_flags;
+} tw_attr_query;
+typedef struct {
+    int32_t *link;
+    int64_t *self_time, *path_time;
+    int32_t *tree_top_group;
+    uint8_t *tree_selected;
+    int32_t *tree_path_rows;
+    int64_t *group_path_time, *group_path_rows, *group_self_time, *group_span_time, *group_span_rows, *group_trees, *group_top_trees;
+} tw_attribution;
+int tw_set_row_groups(tw_engine *e, int32_t n_groups, const int32_t *row_group);
+int tw_attribute_traces(tw_engine *e, const tw_attr_query *q, const tw_attribution *out, int64_t *summary6);
 
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,

@@ -68,10 +68,21 @@ class Stitched(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("root", "depth", "tree_off", "tree_rows", "tree_root", "tree_latency", "tree_flags")]
 
 
+class AttrQuery(ctypes.Structure):
+    _fields_ = [("percentile", ctypes.c_double), ("start_min", ctypes.c_int64), ("start_max", ctypes.c_int64),
+                ("need_flags", ctypes.c_uint32), ("skip_flags", ctypes.c_uint32)]
+
+
+class Attribution(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "link", "self_time", "path_time", "tree_top_group", "tree_selected", "tree_path_rows", "group_path_time", "group_path_rows",
+        "group_self_time", "group_span_time", "group_span_rows", "group_trees", "group_top_trees")]
+
+
 EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_pass1", "tw_get_gaps", "tw_set_gaps",
            "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
            "tw_assign_service", "tw_find_order", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
-           "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces",
+           "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
            "tw_corpus_string", "tw_corpus_loop_origin", "tw_corpus_trace_names", "tw_corpus_span_table", "tw_corpus_build_units"]
 
@@ -126,6 +137,8 @@ def load(path=None):
     lib.tw_set_span_rows.argtypes = [vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp]
     lib.tw_set_parents.argtypes = [vp, vp]
     lib.tw_stitch_traces.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Stitched), vp, vp]
+    lib.tw_set_row_groups.argtypes = [vp, ctypes.c_int32, vp]
+    lib.tw_attribute_traces.argtypes = [vp, ctypes.POINTER(AttrQuery), ctypes.POINTER(Attribution), vp]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]
     lib.tw_host_free.argtypes = [vp]
     lib.tw_host_free.restype = None

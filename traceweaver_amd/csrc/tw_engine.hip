@@ -23,6 +23,7 @@
 #include "tw_load.h"
 #include "tw_baselines.h"
 #include "tw_stitch.h"
+#include "tw_attr.h"
 
 using namespace tw;
 
@@ -187,6 +188,13 @@ struct tw_engine {
     int64_t rows_cap = 0;
     hipEvent_t st_ev[6] = {};
     double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
+    // tw_set_row_groups / tw_attribute_traces (tw_attr.h): the forest of the last tw_stitch_traces stays valid until a load, a load
+    // scaling, new row maps or a new pass; the groups are dropped with the row maps
+    AttrDev A{};
+    bool groups_set = false, stitched = false;
+    int64_t st_trees = 0, groups_cap = 0, attr_rows_cap = 0;
+    hipEvent_t at_ev[4] = {};
+    double at_ms[3] = {0, 0, 0};            // per-tree kernel, selection (flags, sort, mark), group reduction
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
 };
 
@@ -249,6 +257,7 @@ void free_all(tw_engine* e) {
     e->orig_is = e->orig_ie = e->orig_os = e->orig_oe = nullptr; e->orig_truth = e->orig_trace = nullptr;
     e->truth = nullptr; e->in_trace = nullptr; e->trace_bad = nullptr; e->eval_counts = nullptr; e->n_traces = 0; e->trace_cap = 0;
     e->S = StitchDev{}; e->rows_set = false; e->rows_cap = 0; e->given_parent = nullptr; e->parents_given = false;
+    e->A = AttrDev{}; e->groups_set = false; e->stitched = false; e->groups_cap = 0; e->attr_rows_cap = 0;
     e->state = ST_EMPTY;
 }
 
@@ -928,6 +937,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     e->state = ST_LOADED; e->pass1_done = false;
     e->parents_given = false;
     e->rows_set = false;   // every list was re-sorted: in_row / out_row no longer name the spans at these positions
+    e->groups_set = false; e->stitched = false;
     for (int E = 0; E <= kMaxEp; E++) { e->wide_pass1[E] = -1; e->hard_pass1[E] = -1; e->split_pass1[E] = -1; }
     return TW_OK;
 }
@@ -1026,6 +1036,8 @@ void tw_destroy(tw_engine* e) {
     }
     for (int i = 0; i < 6; i++)
         if (e->st_ev[i]) (void)hipEventDestroy(e->st_ev[i]);
+    for (int i = 0; i < 4; i++)
+        if (e->at_ev[i]) (void)hipEventDestroy(e->at_ev[i]);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1389,6 +1401,7 @@ int tw_run_pass1(tw_engine* e) {
     if (e == nullptr) return TW_ERR_ARG;
     if (e->state < ST_LOADED) return fail(e, TW_ERR_STATE, "tw_run_pass1 before tw_load_batch");
     HIPCHK(hipSetDevice(e->device));
+    e->stitched = false;   // (the parent arrays a stitched forest was made from are overwritten)
     const int rc = run_pass(e, 1);
     e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
     if (rc == TW_OK) { e->state = ST_PASS1; e->pass1_done = true; }
@@ -1706,6 +1719,7 @@ int tw_run_pass2(tw_engine* e) {
     // pass reads what the first left behind: cut-offs, window flags, tuple counts)
     if (!e->pass1_done) return fail(e, TW_ERR_STATE, "tw_run_pass2 on a batch whose first pass has not run (tw_run_pass1 first)");
     HIPCHK(hipSetDevice(e->device));
+    e->stitched = false;
     const int rc = run_pass(e, 2);
     if (rc == TW_OK) e->state = ST_PASS2;
     return rc;
@@ -1754,6 +1768,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 8) ms[8] = e->host_ms[0];
     if (n > 9) ms[9] = e->host_ms[1];
     for (int i = 0; i < 6 && 10 + i < n; i++) ms[10 + i] = e->st_ms[i];   // the last tw_stitch_traces
+    for (int i = 0; i < 3 && 16 + i < n; i++) ms[16 + i] = e->at_ms[i];   // the last tw_attribute_traces
     return TW_OK;
 }
 
@@ -1952,6 +1967,7 @@ int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const 
     for (int i = 0; i < 6; i++)
         if (e->st_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->st_ev[i]));
     e->rows_set = true;
+    e->groups_set = false; e->stitched = false;   // (new row maps: the groups name rows of the old ones)
     return TW_OK;
 }
 
@@ -2027,6 +2043,7 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
         if (!ok) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
     }
     HIPCHK(hipSetDevice(e->device));
+    e->stitched = false;
     const StitchDev& S = e->S;
     const bool has_truth = e->truth != nullptr;
     const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
@@ -2084,6 +2101,133 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
     D2H(out->tree_flags, S.tree_flags, (size_t)nt);
 #undef D2H
     HIPCHK(hipStreamSynchronize(e->stream));
+    e->stitched = true; e->st_trees = nt;
+    return TW_OK;
+}
+
+/* ---- latency attribution on the stitched forest (tw_attr.h) ------------------------------------------------------- */
+int tw_set_row_groups(tw_engine* e, int32_t n_groups, const int32_t* row_group) {
+    if (e == nullptr || row_group == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_groups before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
+    if (n_groups < 1) return fail(e, TW_ERR_ARG, "tw_set_row_groups: n_groups must be positive");
+    const int64_t n_rows = e->S.n_rows;
+    for (int64_t r = 0; r < n_rows; r++)   // k_attr_reduce indexes the totals with these values
+        if (row_group[r] < -1 || row_group[r] >= n_groups) return fail(e, TW_ERR_ARG, "tw_set_row_groups: row_group outside [-1, n_groups)");
+    HIPCHK(hipSetDevice(e->device));
+    AttrDev& A = e->A;
+    int rc;
+#define AALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
+    if (A.self_time == nullptr || n_rows > e->attr_rows_cap) {   // (freed with the batch)
+        int32_t* group_d;
+        AALLOC(group_d, n_rows); A.row_group = group_d;
+        AALLOC(A.self_time, n_rows); AALLOC(A.path_time, n_rows); AALLOC(A.row_tree, n_rows); AALLOC(A.row_flag, n_rows);
+        AALLOC(A.tree_top, n_rows); AALLOC(A.tree_path_rows, n_rows); AALLOC(A.tree_sel, n_rows);
+        AALLOC(A.key_a, n_rows); AALLOC(A.key_b, n_rows); AALLOC(A.val_a, n_rows); AALLOC(A.val_b, n_rows);
+        AALLOC(A.counters, 4); AALLOC(A.err, 1);
+        e->attr_rows_cap = n_rows;
+    }
+    if (A.totals == nullptr || n_groups > e->groups_cap) {
+        AALLOC(A.totals, (int64_t)kAttrCols * n_groups);
+        e->groups_cap = n_groups;
+    }
+#undef AALLOC
+    A.n_groups = n_groups;
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(A.row_group), row_group, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 4; i++)
+        if (e->at_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->at_ev[i]));
+    e->groups_set = true;
+    return TW_OK;
+}
+
+int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attribution* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
+        return fail(e, TW_ERR_STATE, "tw_attribute_traces needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    if (!e->groups_set) return fail(e, TW_ERR_STATE, "tw_attribute_traces before tw_set_row_groups (dropped with the row maps)");
+    if (!(q->percentile >= 0.0 && q->percentile < 1.0)) return fail(e, TW_ERR_ARG, "tw_attribute_traces: percentile outside [0, 1)");
+    if (q->start_min > q->start_max) return fail(e, TW_ERR_ARG, "tw_attribute_traces: start_min > start_max");
+    HIPCHK(hipSetDevice(e->device));
+    const StitchDev& S = e->S;
+    AttrDev& A = e->A;
+    const int64_t nt = e->st_trees, G = A.n_groups;
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), rows((unsigned)((S.n_rows + threads - 1) / threads));
+    AttrQueryDev Q{q->start_min, q->start_max, 0, q->need_flags, q->skip_flags};
+    // selection: eligible trees in order of (latency, tree), those of rank >= k inside the start window
+    HIPCHK(hipMemsetAsync(A.counters, 0, sizeof(unsigned long long) * 4, e->stream));
+    HIPCHK(hipMemsetAsync(A.err, 0, sizeof(int32_t), e->stream));
+    HIPCHK(hipMemsetAsync(A.totals, 0, sizeof(unsigned long long) * (size_t)(kAttrCols * G), e->stream));
+    HIPCHK(hipEventRecord(e->at_ev[0], e->stream));
+    hipLaunchKernelGGL(k_attr_flags, trees, tb, 0, e->stream, S, A, Q, nt);
+    HIPCHK(hipGetLastError());
+    size_t bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream));
+    int rc = ensure_sort_tmp(e, bytes);
+    if (rc != TW_OK) return rc;
+    bytes = e->sort_tmp_bytes;
+    HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream));
+    unsigned long long counters[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(counters, A.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t n_eligible = (int64_t)counters[0], big_rows = (int64_t)counters[1];
+    Q.k = (int64_t)(q->percentile * (double)n_eligible);   // int(0.95 * len(...)) of the reference, in binary64
+    hipLaunchKernelGGL(k_attr_mark, trees, tb, 0, e->stream, S, A, Q, nt, n_eligible);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->at_ev[1], e->stream));
+    if (big_rows > A.big_cap) {   // tables of the trees that outgrow a wavefront's LDS (freed with the batch)
+#define AALLOC(ptr) do { rc = dev_alloc(e, &(ptr), big_rows); if (rc != TW_OK) return rc; } while (0)
+        AALLOC(A.g_s); AALLOC(A.g_e); AALLOC(A.g_s2); AALLOC(A.g_e2);
+        AALLOC(A.g_row); AALLOC(A.g_par); AALLOC(A.g_rank); AALLOC(A.g_row2); AALLOC(A.g_par2);
+#undef AALLOC
+        A.big_cap = big_rows;
+    }
+    // one wavefront per kAttrTrees trees, persistent: at most 8192 workgroups of four
+    const unsigned gthreads = e->coop >= 64 ? 64u * kAttrWaves : (unsigned)e->coop;
+    const int64_t want = (nt / kAttrTrees + 1 + kAttrWaves - 1) / kAttrWaves;
+    hipLaunchKernelGGL(k_attr_tree, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, A, nt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->at_ev[2], e->stream));
+    hipLaunchKernelGGL(k_attr_reduce, rows, tb, 0, e->stream, S, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->at_ev[3], e->stream));
+    std::vector<unsigned long long> totals((size_t)(kAttrCols * G));
+    unsigned long long key_k = 1ull << 63;
+    int32_t err = 0;
+    HIPCHK(hipMemcpyAsync(totals.data(), A.totals, sizeof(unsigned long long) * totals.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(counters, A.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&err, A.err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (n_eligible > 0) HIPCHK(hipMemcpyAsync(&key_k, A.key_b + Q.k, sizeof(key_k), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (err == TW_ERR_DEVICE) return fail(e, TW_ERR_DEVICE, "tw_attribute_traces: the tables of the large trees are smaller than the trees");
+    if (err != 0) return fail(e, TW_ERR_ARG, "tw_attribute_traces: a row is linked to a row outside its tree: not the forest tw_stitch_traces left behind");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[1], e->at_ev[2])); e->at_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[0], e->at_ev[1])); e->at_ms[1] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[2], e->at_ev[3])); e->at_ms[2] = ms;
+    if (summary != nullptr) {
+        int64_t culprit = -1;   // the group with the largest path time among those with a row on a selected path; ties: the smallest id
+        for (int64_t g = 0; g < G; g++)
+            if (totals[(size_t)(G + g)] != 0 && (culprit < 0 || (int64_t)totals[(size_t)g] > (int64_t)totals[(size_t)culprit])) culprit = g;
+        summary[0] = n_eligible; summary[1] = (int64_t)counters[2]; summary[2] = Q.k;
+        summary[3] = (int64_t)(key_k ^ (1ull << 63)); summary[4] = culprit; summary[5] = nt;
+    }
+    if (out != nullptr) {
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+        D2H(out->link, S.link, sizeof(int32_t) * (size_t)S.n_rows);
+        D2H(out->self_time, A.self_time, sizeof(int64_t) * (size_t)S.n_rows);
+        D2H(out->path_time, A.path_time, sizeof(int64_t) * (size_t)S.n_rows);
+        D2H(out->tree_top_group, A.tree_top, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_selected, A.tree_sel, (size_t)nt);
+        D2H(out->tree_path_rows, A.tree_path_rows, sizeof(int32_t) * (size_t)nt);
+#undef D2H
+        HIPCHK(hipStreamSynchronize(e->stream));
+        int64_t* cols[kAttrCols] = {out->group_path_time, out->group_path_rows, out->group_self_time, out->group_span_time, out->group_span_rows,
+                                    out->group_trees, out->group_top_trees};
+        for (int c = 0; c < kAttrCols; c++)
+            if (cols[c] != nullptr)
+                for (int64_t g = 0; g < G; g++) cols[c][g] = (int64_t)totals[(size_t)(c * G + g)];
+    }
     return TW_OK;
 }
 

@@ -440,6 +440,43 @@ class Engine(object):
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 16))
         return dict(zip(("stitch", "links", "jump", "scatter", "group", "rounds"), ms[10:16].tolist()))
 
+    def set_row_groups(self, row_group, n_groups):
+        """The group of every span-table row, in [0, n_groups) or -1 = not counted (tw_set_row_groups; traces.groups_from_table
+        groups by service).  Call it after set_span_rows; dropped with the row maps."""
+        g = np.ascontiguousarray(row_group, dtype=np.int32)
+        if len(g) != int(getattr(self, "_n_rows", 0)):
+            raise ValueError("row_group does not match the span rows")
+        self._check(self._lib.tw_set_row_groups(self._h, int(n_groups), _vp(g)))
+        self._n_groups = int(n_groups)
+
+    def attribute(self, percentile=0.0, start_min=None, start_max=None, need_flags=1, skip_flags=2):
+        """Latency attribution on the forest of the last stitch() (tw_attribute_traces): per row self time and critical-path
+        time, per tree the top group, per group the totals over the selected trees -- the eligible trees (flags hold need_flags,
+        none of skip_flags; default: whole traces without an unassigned call) from rank int(percentile * n_eligible) by
+        latency on, whose root starts in [start_min, start_max).  Returns traces.Attribution."""
+        from .traces import Attribution
+
+        n, G = int(getattr(self, "_n_rows", 0)), int(getattr(self, "_n_groups", 0))
+        lo = np.iinfo(np.int64).min if start_min is None else int(start_min)
+        hi = np.iinfo(np.int64).max if start_max is None else int(start_max)
+        q = _ffi.AttrQuery(float(percentile), lo, hi, int(need_flags), int(skip_flags))
+        link = np.empty(n, dtype=np.int32)
+        self_time, path_time = (np.empty(n, dtype=np.int64) for _ in range(2))
+        top, path_rows = (np.empty(n, dtype=np.int32) for _ in range(2))
+        selected = np.empty(n, dtype=np.uint8)
+        groups = np.zeros((7, max(G, 1)), dtype=np.int64)
+        out = _ffi.Attribution(*[_vp(a) for a in (link, self_time, path_time, top, selected, path_rows)] + [_vp(groups[c]) for c in range(7)])
+        summary = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_attribute_traces(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        k = int(summary[5])
+        return Attribution(link, self_time, path_time, top[:k].copy(), selected[:k].copy(), path_rows[:k].copy(), groups[:, :G].copy(), summary[:5])
+
+    def attribute_timing(self):
+        """The last attribute() on the device (HIP events, ms): per-tree kernel, selection (flags, sort, mark), group reduction."""
+        ms = np.zeros(19, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 19))
+        return dict(zip(("tree", "select", "reduce"), ms[16:19].tolist()))
+
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):
         """The reference's FCFS ("FCFS", algorithms/fcfs.py) or vPath ("vPath", algorithms/vpath.py; needs set_truth) on the

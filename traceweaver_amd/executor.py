@@ -91,6 +91,13 @@ def parse_args(argv=None):
                     help="write the traces predictor 10's assignments make together to this .npz (traceweaver_amd/traces.py: the per-service "
                          "parent arrays joined with the observed hops on the GPU, tw_stitch_traces) and print their counts.  Default: off, "
                          "nothing changes")
+    ap.add_argument("--attribute_out", type=q, default=None,
+                    help="answer the reference's delay-culprit query (src/query_engine/delay_culprit.py) on the stitched traces on the GPU "
+                         "(tw_attribute_traces: critical paths, per-service totals over the slowest traces), write the result to this .npz "
+                         "and print the culprit.  Stitches whether or not --stitch_out is given.  Default: off, nothing changes")
+    ap.add_argument("--query_percentile", type=float, default=0.95, help="--attribute_out: the latency bracket, traces from this quantile on")
+    ap.add_argument("--query_after", type=int, default=None, help="--attribute_out: only traces whose root starts at or after this time (us)")
+    ap.add_argument("-v", "--verbose", action="store_true", help="--attribute_out: print the same figures taken from the true traces")
     ap.add_argument("--engine_library", type=q, default=None, help=argparse.SUPPRESS)   # tests: host-emulation build
     args = ap.parse_args(argv)
     if args.relative_path is None and args.absolute_path is None:
@@ -118,6 +125,10 @@ def unsupported(args):
         problems.append("--parallel / --instrumented")
     if args.stitch_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--stitch_out without predictor 10 or with --cache_rate > 0 (a skip-mode service is solved in a batch of its own)")
+    if args.attribute_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--attribute_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.attribute_out and not 0.0 <= args.query_percentile < 1.0:
+        problems.append("--query_percentile outside [0, 1)")
     return problems
 
 
@@ -160,7 +171,11 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right):
     eng.set_span_rows(*traces.rows_from_units(units, table))
     eng.set_parents(parents)
     st = eng.stitch(0)
+    if args.attribute_out:
+        attribute_out(args, eng, st, corpus, table)
     eng.close()
+    if not args.stitch_out:
+        return
     traces.write_npz(args.stitch_out, st, corpus, table)
     c = st.counts.tolist()
     print("Stitched traces: %d whole, %d fragments, %d with unassigned calls; exact vs ground truth: %d of %d" % (c[0], c[1], c[2], c[3], total))
@@ -172,6 +187,30 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right):
         raise RuntimeError("stitched traces: %d exact, the accuracy reduction counts %d traces right" % (c[3], right))
     elif c[3] > right:   # bit 2 compares row sets: two requests of one service in one trace that swap their calls keep the set
         print("(%d traces hold the true spans under another assignment of calls to requests: right as a set, wrong per request)" % (c[3] - right))
+
+
+def culprit_line(a, names, head="Delay culprit"):
+    g = a.culprit
+    if g < 0:
+        return "%s: none (%d of %d traces selected)" % (head, a.n_selected, a.n_eligible)
+    total = int(a.group_path_time.sum())
+    return "%s: %s, mean service latency %.1f us over %d of %d traces (critical-path share %.1f %%)" % (
+        head, names[g], a.mean_latency(g), a.n_selected, a.n_eligible, 100.0 * float(a.group_path_time[g]) / total if total else 0.0)
+
+
+def attribute_out(args, eng, st, corpus, table):
+    """--attribute_out: the delay-culprit query on the forest just stitched, groups by service."""
+    from . import traces
+
+    group, names = traces.groups_from_table(table, corpus)
+    eng.set_row_groups(group, len(names))
+    query = dict(percentile=args.query_percentile, start_min=args.query_after)
+    a = eng.attribute(**query)
+    traces.write_attribution_npz(args.attribute_out, a, names, st)
+    print(culprit_line(a, names))
+    if args.verbose:
+        eng.stitch(truth=True)
+        print(culprit_line(eng.attribute(**query), names, "Delay culprit (true traces)"))
 
 
 def run(args):
@@ -347,7 +386,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out:
+            if args.stitch_out or args.attribute_out:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()))
         else:
             method = BASELINES[index]

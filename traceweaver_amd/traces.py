@@ -5,7 +5,13 @@ answers say together with the hops that are observed (an RPC is logged on both s
 caller's client span).  `rows_from_units` builds what Engine.set_span_rows takes from the ingest's units and span table,
 `StitchedTraces` is what Engine.stitch returns, `write_npz` stores it with the (trace id, span id) strings of every row,
 and `stitch_host` restates the device's computation in numpy -- test and cross-check code; the product path is the device.
+
+Engine.attribute (tw_attribute_traces, csrc/tw_attr.h) answers the delay-culprit query on the stitched forest: `Attribution`
+is its result, `groups_from_table` the usual grouping (by service), `write_attribution_npz` stores it, and `attribute_host`
+restates the definitions in plain recursive Python -- the yardstick of the tests, nothing else.
 """
+import sys
+
 import numpy as np
 
 WHOLE, UNASSIGNED, EXACT = 1, 2, 4   # bits of tree_flags
@@ -140,3 +146,161 @@ def write_npz(path, stitched, corpus, table=None):
             row_trace_id=trace_ids[np.asarray(table["trace"])], row_span_id=np.array([corpus.string(x) for x in table["span_id"]]),
             row_service=services[inverse], row_kind=np.asarray(table["kind"]), row_start=start,
             row_end=start + np.asarray(table["duration"], dtype=np.int64))
+
+
+GROUP_COLUMNS = ("path_time", "path_rows", "self_time", "span_time", "span_rows", "trees", "top_trees")
+
+
+class Attribution(object):
+    """link / self_time / path_time [n_rows]: the stitched links, every row's own time (duration less the union of its
+    children) and its share of its tree's critical path; tree_top_group / tree_selected / tree_path_rows [n_trees]; groups
+    [7, n_groups] = GROUP_COLUMNS over the selected trees (also as attributes group_<column>); summary = eligible trees,
+    selected trees, rank k, latency at rank k, culprit (include/traceweaver_amd.h has the definitions)."""
+
+    FIELDS = ("link", "self_time", "path_time", "tree_top_group", "tree_selected", "tree_path_rows", "groups", "summary")
+
+    def __init__(self, link, self_time, path_time, tree_top_group, tree_selected, tree_path_rows, groups, summary):
+        self.link, self.self_time, self.path_time = link, self_time, path_time
+        self.tree_top_group, self.tree_selected, self.tree_path_rows = tree_top_group, tree_selected, tree_path_rows
+        self.groups = np.asarray(groups, dtype=np.int64)
+        self.summary = np.asarray(summary, dtype=np.int64)
+        for c, name in enumerate(GROUP_COLUMNS):
+            setattr(self, "group_" + name, self.groups[c])
+
+    n_eligible = property(lambda self: int(self.summary[0]))
+    n_selected = property(lambda self: int(self.summary[1]))
+    rank = property(lambda self: int(self.summary[2]))
+    rank_latency = property(lambda self: int(self.summary[3]))
+    culprit = property(lambda self: int(self.summary[4]))
+
+    def mean_latency(self, g):
+        """Mean service latency of group g over the selected trees (us), nan without a row."""
+        n = int(self.group_span_rows[g])
+        return float(self.group_span_time[g]) / n if n else float("nan")
+
+    def table(self, names=None):
+        """One dict per group: its name, GROUP_COLUMNS, mean_latency and path_share (of the selected trees' latency)."""
+        total = int(self.group_path_time.sum())
+        return [dict([("group", g if names is None else names[g])] + [(c, int(self.groups[i][g])) for i, c in enumerate(GROUP_COLUMNS)] +
+                     [("mean_latency", self.mean_latency(g)), ("path_share", float(self.group_path_time[g]) / total if total else 0.0)])
+                for g in range(self.groups.shape[1])]
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def groups_from_table(table, corpus=None):
+    """(row_group, names): the rows of a span table grouped by interned service, groups in ascending order of the service's
+    string id; names are the services' strings when the corpus is given, their string ids otherwise."""
+    ids, inverse = np.unique(np.asarray(table["service"]), return_inverse=True)
+    names = [corpus.string(x) for x in ids] if corpus is not None else [int(x) for x in ids]
+    return inverse.astype(np.int32), names
+
+
+def attribute_host(stitched, link, row_start, row_end, row_group, n_groups, percentile=0.0, start_min=None, start_max=None,
+                   need_flags=WHOLE, skip_flags=UNASSIGNED):
+    """What tw_attribute_traces computes, restated from the definitions: recursive and obvious, for the tests."""
+    link = np.asarray(link, dtype=np.int64)
+    start = [int(x) for x in row_start]
+    end = [max(int(e), s) for e, s in zip(row_end, start)]
+    group = [int(x) for x in row_group]
+    n = len(link)
+    children = [[] for _ in range(n)]
+    for c in range(n):
+        if link[c] >= 0:
+            children[int(link[c])].append(c)
+    self_time = np.zeros(n, dtype=np.int64)
+    for p in range(n):
+        clipped = sorted((max(start[c], start[p]), min(end[c], end[p])) for c in children[p])
+        covered, reach = 0, start[p]
+        for cs, ce in clipped:
+            if ce > cs:
+                covered += max(0, ce - max(cs, reach))
+                reach = max(reach, ce)
+        self_time[p] = end[p] - start[p] - covered
+    path_time = np.zeros(n, dtype=np.int64)
+    walked = np.zeros(n, dtype=bool)
+
+    def walk(p, lo, hi):
+        walked[p] = True
+        cursor = hi
+        while True:
+            best = None
+            for c in children[p]:
+                cs = max(start[c], lo)
+                ce = min(end[c], cursor)
+                if cs < cursor and ce > cs and (best is None or (-ce, cs, c) < best[0]):
+                    best = ((-ce, cs, c), c, cs, ce)
+            if best is None:
+                break
+            _, c, cs, ce = best
+            path_time[p] += cursor - ce
+            walk(c, cs, ce)
+            cursor = cs
+        path_time[p] += cursor - lo
+
+    limit = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(limit, 20000))
+    try:
+        for r in stitched.tree_root:
+            walk(int(r), start[int(r)], end[int(r)])
+    finally:
+        sys.setrecursionlimit(limit)
+    nt = stitched.n_trees
+    top = np.full(nt, -1, dtype=np.int32)
+    path_rows = np.zeros(nt, dtype=np.int32)
+    per_tree = []
+    for k in range(nt):
+        rows = [int(r) for r in stitched.tree_rows[int(stitched.tree_off[k]):int(stitched.tree_off[k + 1])]]
+        sums = {}
+        for r in rows:
+            if walked[r]:
+                path_rows[k] += 1
+                if group[r] >= 0:
+                    sums[group[r]] = sums.get(group[r], 0) + int(path_time[r])
+        if sums:
+            top[k] = min(sums, key=lambda g: (-sums[g], g))
+        per_tree.append((rows, sums))
+    flags = np.asarray(stitched.tree_flags).astype(np.int64)
+    eligible = [k for k in range(nt) if (flags[k] & need_flags) == need_flags and (flags[k] & skip_flags) == 0]
+    eligible.sort(key=lambda k: (int(stitched.tree_latency[k]), k))
+    rank = int(percentile * len(eligible))
+    lo = -2 ** 63 if start_min is None else int(start_min)
+    hi = 2 ** 63 - 1 if start_max is None else int(start_max)
+    selected = np.zeros(nt, dtype=np.uint8)
+    for k in eligible[rank:]:
+        if lo <= start[int(stitched.tree_root[k])] < hi:
+            selected[k] = 1
+    groups = np.zeros((len(GROUP_COLUMNS), n_groups), dtype=np.int64)
+    for k in np.flatnonzero(selected):
+        rows, sums = per_tree[k]
+        for r in rows:
+            g = group[r]
+            if g < 0:
+                continue
+            if walked[r]:
+                groups[0, g] += path_time[r]
+                groups[1, g] += 1
+            groups[2, g] += self_time[r]
+            groups[3, g] += end[r] - start[r]
+            groups[4, g] += 1
+        for g in sums:
+            groups[5, g] += 1
+        if top[k] >= 0:
+            groups[6, top[k]] += 1
+    on = [g for g in range(n_groups) if groups[1, g] > 0]
+    culprit = min(on, key=lambda g: (-int(groups[0, g]), g)) if on else -1
+    summary = [len(eligible), int(selected.sum()), rank, int(stitched.tree_latency[eligible[rank]]) if eligible else 0, culprit]
+    return Attribution(link.astype(np.int32), self_time, path_time, top, selected, path_rows, groups, summary)
+
+
+def write_attribution_npz(path, attribution, names, stitched):
+    """The attribution as one .npz next to the one write_npz stores: its arrays, the group names, and the trees' roots
+    and latencies so that the selection can be read without the stitched file."""
+    a = attribution
+    with open(path, "wb") as f:
+        np.savez_compressed(
+            f, link=a.link, self_time=a.self_time, path_time=a.path_time, tree_top_group=a.tree_top_group, tree_selected=a.tree_selected,
+            tree_path_rows=a.tree_path_rows, groups=a.groups, group_columns=np.array(GROUP_COLUMNS), summary=a.summary,
+            group_names=np.array([str(x) for x in names]), mean_latency=np.array([a.mean_latency(g) for g in range(a.groups.shape[1])]),
+            tree_root=stitched.tree_root, tree_latency=stitched.tree_latency, tree_flags=stitched.tree_flags)

@@ -248,7 +248,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * rounds (incl. the host's one-word read per round), ms[13] rows per root + scan + scatter, ms[14] per-tree order and figures,
  * ms[15] (a count) doubling rounds.
  * The last tw_attribute_traces (HIP events): ms[16] per-tree kernel, ms[17] selection (flags, sort, mark; incl. the host's
- * read of the eligible count), ms[18] group reduction. */
+ * read of the eligible count), ms[18] group reduction.
+ * The last tw_score_traces (HIP events): ms[19] decision kernel, ms[20] row map + per-tree reduction, ms[21] calibration
+ * (tw_get_decisions alone writes ms[19]). */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -416,6 +418,66 @@ typedef struct {
 } tw_attribution;
 int tw_set_row_groups(tw_engine *e, int32_t n_groups, const int32_t *row_group);
 int tw_attribute_traces(tw_engine *e, const tw_attr_query *q, const tw_attribution *out, int64_t *summary6);
+
+/* ---- which of the reconstructed traces can be trusted (csrc/tw_conf.h) -------------------------------------------
+ *
+ * Replaces: the reference's one figure of trust, not_best_count / num_spans per service -- the requests whose selected tuple
+ * is not their own best-scoring one (traceweaver_v3.py:1201-1207), written to confidence_scores_*.pickle (executor.py:
+ * 1203-1205,1241) and plotted as 1 - not_best / n against accuracy (utils/plot_accuracy_vs_confidence_multiple_cgs.py:76-84).
+ * tw_results.unit_stats[0] is that scalar; here the facts behind it leave the device per request and per stitched trace.
+ *
+ * Decision of request g (one per incoming span of the loaded batch, of the resident pass).  L = the candidate list the
+ * selection chose from, the one chosen[g] indexes: the list enumerated again on the remaining spans where the engine did
+ * so, else the first (tw_results.topk_* is always the first).  n = |L|, s[0..n) its scores in list order, c = chosen[g]:
+ *   rank      c (-1: none was selected)
+ *   list_n    n
+ *   margin    binary64, one subtraction: c < 0: NaN.  c == 0: s[0] - s[1], +inf when n == 1.  c > 0: s[c] - s[0].
+ *             A NaN that the subtraction itself gives (inf - inf) stays NaN; every NaN is stored as 0x7ff8000000000000.
+ *   not_best  c != 0: what unit_stats[0] counts.
+ * Per tree k of the stitched forest, over its decisions = the requests g with in_row[g] in the tree:
+ *   decisions, not_best, unassigned (c < 0)   int32 counts
+ *   min_margin   the minimum over the decisions whose margin is not NaN, in the order -inf < .. < -0 < +0 < .. < +inf;
+ *                +inf if there is none
+ *   weakest_row  in_row of a decision that attains min_margin (the same bits), the smallest row on ties; -1 if there is none
+ *   confident    decisions > 0 && not_best == 0 && min_margin >= threshold
+ * TW_TREE_CONFIDENT: after tw_score_traces the forest kept on the device for tw_attribute_traces carries this bit in the
+ * flags of its confident trees (need_flags = 1 | 8: whole and confident).  Every tw_score_traces call clears and rewrites
+ * it; before the first one it is never set, and the tree_flags tw_stitch_traces returns never show it.
+ * Calibration: ascending edges[0..n_edges), n_edges <= 15.  bucket(tree) = 0 if not_best > 0, else 1 + #{j: min_margin >=
+ * edges[j]}: n_edges + 2 buckets.  calib[n_edges + 2][3], counted over the whole trees (flag bit 0) with decisions > 0:
+ * trees, trees with flag bit 2 (exact; -1 in every row without tw_set_truth), decisions.
+ * summary5 = scored trees (decisions > 0), confident trees, decisions, not_best, unassigned (all trees).
+ *
+ * tw_get_decisions: `pass` (1 or 2) must be the resident one (TW_ERR_STATE otherwise, as for tw_get_results); needs no
+ * stitch.  Outputs [requests of the batch] in the layout of in_start, any may be NULL.
+ * tw_score_traces: works on the forest of the last tw_stitch_traces(pass = 1 | 2).  Outputs are caller-allocated, any may be
+ * NULL: rank, list_n, margin [requests]; row_request [n_rows] (the request whose incoming span the row is, -1 none); tree_*
+ * [n_trees of the stitch]; calib [(n_edges + 2) * 3].  TW_ERR_STATE: before a stitch, after anything that drops the stitched
+ * forest (see tw_attribute_traces), for a forest stitched from tw_set_parents (pass 0) or from the truth -- they hold no
+ * decisions --, when the stitched pass is no longer resident.  TW_ERR_ARG: n_edges outside [0, 15], edges that are NaN or
+ * not strictly ascending.
+ * Covers the selected assignment only and one engine's batch.  Results do not depend on scheduling: the one floating-point
+ * operation is the subtraction that defines a margin, minima are taken on integer keys, the atomic adds are integer adds
+ * of which only the sum is read.  Timing: tw_get_timing slots 19..21 (decision kernel, row map + tree reduction,
+ * calibration; HIP events, ms). */
+#define TW_TREE_CONFIDENT 8
+typedef struct {
+    double threshold;
+    int32_t n_edges;
+    const double *edges;
+} tw_conf_query;
+typedef struct {
+    int32_t *rank, *list_n;
+    double *margin;
+    int32_t *row_request;
+    int32_t *tree_decisions, *tree_not_best, *tree_unassigned;
+    double *tree_min_margin;
+    int32_t *tree_weakest_row;
+    uint8_t *tree_confident;
+    int64_t *calib;
+} tw_confidence;
+int tw_get_decisions(tw_engine *e, int pass, int32_t *rank, int32_t *list_n, double *margin);
+int tw_score_traces(tw_engine *e, const tw_conf_query *q, const tw_confidence *out, int64_t *summary5);
 
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,

@@ -24,6 +24,7 @@
 #include "tw_baselines.h"
 #include "tw_stitch.h"
 #include "tw_attr.h"
+#include "tw_conf.h"
 
 using namespace tw;
 
@@ -196,6 +197,14 @@ struct tw_engine {
     hipEvent_t at_ev[4] = {};
     double at_ms[3] = {0, 0, 0};            // per-tree kernel, selection (flags, sort, mark), group reduction
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
+    // tw_get_decisions / tw_score_traces (tw_conf.h): the decisions are those of the resident pass, so only a forest stitched
+    // from it can be scored (stitched_pass: 1 | 2; 0 = from tw_set_parents, -1 = from the truth)
+    ConfDev C{};
+    int stitched_pass = -1;
+    bool stitched_truth = false;            // ground truth was set when the forest was stitched: its flags carry bit 2
+    int64_t conf_rows_cap = 0;
+    hipEvent_t cf_ev[4] = {};
+    double cf_ms[3] = {0, 0, 0};            // decision kernel, row map + per-tree reduction, calibration
 };
 
 namespace {
@@ -258,6 +267,7 @@ void free_all(tw_engine* e) {
     e->truth = nullptr; e->in_trace = nullptr; e->trace_bad = nullptr; e->eval_counts = nullptr; e->n_traces = 0; e->trace_cap = 0;
     e->S = StitchDev{}; e->rows_set = false; e->rows_cap = 0; e->given_parent = nullptr; e->parents_given = false;
     e->A = AttrDev{}; e->groups_set = false; e->stitched = false; e->groups_cap = 0; e->attr_rows_cap = 0;
+    e->C = ConfDev{}; e->conf_rows_cap = 0;
     e->state = ST_EMPTY;
 }
 
@@ -1038,6 +1048,8 @@ void tw_destroy(tw_engine* e) {
         if (e->st_ev[i]) (void)hipEventDestroy(e->st_ev[i]);
     for (int i = 0; i < 4; i++)
         if (e->at_ev[i]) (void)hipEventDestroy(e->at_ev[i]);
+    for (int i = 0; i < 4; i++)
+        if (e->cf_ev[i]) (void)hipEventDestroy(e->cf_ev[i]);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1769,6 +1781,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 9) ms[9] = e->host_ms[1];
     for (int i = 0; i < 6 && 10 + i < n; i++) ms[10 + i] = e->st_ms[i];   // the last tw_stitch_traces
     for (int i = 0; i < 3 && 16 + i < n; i++) ms[16 + i] = e->at_ms[i];   // the last tw_attribute_traces
+    for (int i = 0; i < 3 && 19 + i < n; i++) ms[19 + i] = e->cf_ms[i];   // the last tw_score_traces
     return TW_OK;
 }
 
@@ -2102,6 +2115,7 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
 #undef D2H
     HIPCHK(hipStreamSynchronize(e->stream));
     e->stitched = true; e->st_trees = nt;
+    e->stitched_pass = use_truth ? -1 : pass; e->stitched_truth = has_truth;
     return TW_OK;
 }
 
@@ -2227,6 +2241,133 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
         for (int c = 0; c < kAttrCols; c++)
             if (cols[c] != nullptr)
                 for (int64_t g = 0; g < G; g++) cols[c][g] = (int64_t)totals[(size_t)(c * G + g)];
+    }
+    return TW_OK;
+}
+
+/* ---- which of the reconstructed traces can be trusted (tw_conf.h) -------------------------------------------------- */
+namespace {
+
+bool pass_resident(const tw_engine* e, int pass) {
+    return (pass == 1 && (e->state == ST_PASS1 || e->state == ST_MIX)) || (pass == 2 && e->state == ST_PASS2);
+}
+
+// rank, list_n and margin of the resident pass into e->C (freed with the batch); cf_ev[0] .. cf_ev[1] around the kernel
+int conf_decisions(tw_engine* e) {
+    const Dev& P = e->P;
+    ConfDev& C = e->C;
+    if (C.rank == nullptr) {
+        int rc;
+        if ((rc = dev_alloc(e, &C.rank, P.n_in_total)) != TW_OK || (rc = dev_alloc(e, &C.list_n, P.n_in_total)) != TW_OK ||
+            (rc = dev_alloc(e, &C.margin, P.n_in_total)) != TW_OK || (rc = dev_alloc(e, &C.cells, kConfCells)) != TW_OK) {
+            C.rank = nullptr;
+            return rc;
+        }
+    }
+    for (int i = 0; i < 4; i++)
+        if (e->cf_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->cf_ev[i]));
+    HIPCHK(hipEventRecord(e->cf_ev[0], e->stream));
+    hipLaunchKernelGGL(k_conf_requests, dim3((unsigned)P.n_tiles), dim3((unsigned)e->tile), 0, e->stream, P, C);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->cf_ev[1], e->stream));
+    return TW_OK;
+}
+
+}  // namespace
+
+int tw_get_decisions(tw_engine* e, int pass, int32_t* rank, int32_t* list_n, double* margin) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (!pass_resident(e, pass)) return fail(e, TW_ERR_STATE, "tw_get_decisions: the results of that pass are not resident");
+    HIPCHK(hipSetDevice(e->device));
+    const int rc = conf_decisions(e);
+    if (rc != TW_OK) return rc;
+    const ConfDev& C = e->C;
+    const size_t n = (size_t)e->P.n_in_total;
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+    D2H(rank, C.rank, sizeof(int32_t) * n);
+    D2H(list_n, C.list_n, sizeof(int32_t) * n);
+    D2H(margin, C.margin, sizeof(double) * n);
+#undef D2H
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[0], e->cf_ev[1])); e->cf_ms[0] = ms;
+    return TW_OK;
+}
+
+int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
+        return fail(e, TW_ERR_STATE, "tw_score_traces needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    if (e->stitched_pass != 1 && e->stitched_pass != 2)
+        return fail(e, TW_ERR_STATE, "tw_score_traces: the forest was stitched from tw_set_parents or from the truth: it holds no decisions of this engine");
+    if (!pass_resident(e, e->stitched_pass)) return fail(e, TW_ERR_STATE, "tw_score_traces: the pass the forest was stitched from is no longer resident");
+    if (q->n_edges < 0 || q->n_edges > kConfMaxEdges || (q->n_edges > 0 && q->edges == nullptr))
+        return fail(e, TW_ERR_ARG, "tw_score_traces: n_edges outside [0, 15]");
+    ConfQueryDev Q{};
+    Q.threshold = q->threshold;
+    Q.n_edges = q->n_edges;
+    for (int j = 0; j < q->n_edges; j++) {
+        if (!(q->edges[j] == q->edges[j]) || (j > 0 && !(q->edges[j] > q->edges[j - 1])))
+            return fail(e, TW_ERR_ARG, "tw_score_traces: the edges must be ascending and not NaN");
+        Q.edges[j] = q->edges[j];
+    }
+    HIPCHK(hipSetDevice(e->device));
+    const Dev& P = e->P;
+    const StitchDev& S = e->S;
+    ConfDev& C = e->C;
+    const int64_t nt = e->st_trees;
+    int rc;
+    if (C.row_request == nullptr || S.n_rows > e->conf_rows_cap) {   // (freed with the batch)
+#define CALLOC(ptr) do { rc = dev_alloc(e, &(ptr), S.n_rows); if (rc != TW_OK) return rc; } while (0)
+        CALLOC(C.row_request); CALLOC(C.decisions); CALLOC(C.not_best); CALLOC(C.unassigned); CALLOC(C.weakest_row);
+        CALLOC(C.min_margin); CALLOC(C.confident);
+#undef CALLOC
+        e->conf_rows_cap = S.n_rows;
+    }
+    rc = conf_decisions(e);
+    if (rc != TW_OK) return rc;
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), reqs((unsigned)((P.n_in_total + threads - 1) / threads));
+    HIPCHK(hipMemsetAsync(C.row_request, 0xff, sizeof(int32_t) * (size_t)S.n_rows, e->stream));
+    hipLaunchKernelGGL(k_conf_scatter, reqs, tb, 0, e->stream, S, C, P.n_in_total);
+    // one wavefront per kConfTrees trees, persistent: at most 8192 workgroups of four
+    const unsigned gthreads = e->coop >= 64 ? 64u * kConfWaves : (unsigned)e->coop;
+    const int64_t want = (nt / kConfTrees + 1 + kConfWaves - 1) / kConfWaves;
+    hipLaunchKernelGGL(k_conf_trees, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, C, Q, nt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->cf_ev[2], e->stream));
+    HIPCHK(hipMemsetAsync(C.cells, 0, sizeof(unsigned long long) * kConfCells, e->stream));
+    hipLaunchKernelGGL(k_conf_calib, trees, tb, 0, e->stream, S, C, Q, nt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->cf_ev[3], e->stream));
+    unsigned long long cells[kConfCells];
+    HIPCHK(hipMemcpyAsync(cells, C.cells, sizeof(cells), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[0], e->cf_ev[1])); e->cf_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[1], e->cf_ev[2])); e->cf_ms[1] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[2], e->cf_ev[3])); e->cf_ms[2] = ms;
+    if (summary != nullptr)
+        for (int k = 0; k < 5; k++) summary[k] = (int64_t)cells[(kConfMaxEdges + 2) * kConfCalibCols + k];
+    if (out != nullptr) {
+        if (out->calib != nullptr)
+            for (int b = 0; b < q->n_edges + 2; b++)
+                for (int c = 0; c < kConfCalibCols; c++)
+                    out->calib[b * kConfCalibCols + c] = (c == 1 && !e->stitched_truth) ? -1 : (int64_t)cells[b * kConfCalibCols + c];
+        const size_t n = (size_t)P.n_in_total;
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+        D2H(out->rank, C.rank, sizeof(int32_t) * n);
+        D2H(out->list_n, C.list_n, sizeof(int32_t) * n);
+        D2H(out->margin, C.margin, sizeof(double) * n);
+        D2H(out->row_request, C.row_request, sizeof(int32_t) * (size_t)S.n_rows);
+        D2H(out->tree_decisions, C.decisions, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_not_best, C.not_best, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_unassigned, C.unassigned, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_min_margin, C.min_margin, sizeof(double) * (size_t)nt);
+        D2H(out->tree_weakest_row, C.weakest_row, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_confident, C.confident, (size_t)nt);
+#undef D2H
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
     return TW_OK;
 }

@@ -430,6 +430,7 @@ class Engine(object):
         which = int(getattr(self, "_last_pass", 0)) if pass_ is None else int(pass_)
         self._check(self._lib.tw_stitch_traces(self._h, which, 1 if truth else 0, ctypes.byref(out), ctypes.byref(nt), _vp(counts)))
         k = int(nt.value)
+        self._n_trees = k
         return StitchedTraces(root, depth, tree_off[:k + 1].copy(), tree_rows, tree_root[:k].copy(), tree_latency[:k].copy(),
                               tree_flags[:k].copy(), counts)
 
@@ -476,6 +477,46 @@ class Engine(object):
         ms = np.zeros(19, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 19))
         return dict(zip(("tree", "select", "reduce"), ms[16:19].tolist()))
+
+    def decisions(self, pass_=None):
+        """The decision of every request of the resident pass (None = the last pass run; tw_get_decisions): per unit a dict
+        rank [n_in] (= chosen, -1 none), list_n [n_in] (length of the list the selection chose from: the one enumerated again
+        on the remaining spans where that happened) and margin [n_in] (float64: rank 0: best score less the runner-up's, +inf
+        for a list of one; rank > 0: the chosen score less the best, <= 0; rank -1: NaN)."""
+        n = int(self._in_off[-1])
+        rank, list_n, margin = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
+        which = int(getattr(self, "_last_pass", 0)) if pass_ is None else int(pass_)
+        self._check(self._lib.tw_get_decisions(self._h, which, _vp(rank), _vp(list_n), _vp(margin)))
+        return [{"rank": rank[a:b], "list_n": list_n[a:b], "margin": margin[a:b]} for a, b in zip(self._in_off[:-1].tolist(), self._in_off[1:].tolist())]
+
+    def score_traces(self, threshold=0.0, edges=()):
+        """Confidence of the traces of the last stitch() of a pass (tw_score_traces): the per-request decisions reduced over
+        every tree, the calibration table over the whole trees with bucket edges `edges` (ascending, at most 15), and the
+        CONFIDENT bit (not_best == 0 and min_margin >= threshold) set in the forest attribute() works on:
+        attribute(need_flags=traces.WHOLE | traces.CONFIDENT).  Returns traces.TraceConfidence."""
+        from .traces import TraceConfidence
+
+        n, rows = int(self._in_off[-1]), int(getattr(self, "_n_rows", 0))
+        ed = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        q = _ffi.ConfQuery(float(threshold), len(ed), _vp(ed) if len(ed) else ctypes.c_void_p(0))
+        rank, list_n, row_request = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(rows, dtype=np.int32)
+        margin = np.empty(n, dtype=np.float64)
+        dec, nb, una, weakest = (np.empty(rows, dtype=np.int32) for _ in range(4))
+        min_margin = np.empty(rows, dtype=np.float64)
+        confident = np.empty(rows, dtype=np.uint8)
+        calib = np.zeros((min(len(ed), _ffi.TW_CONF_MAX_EDGES) + 2, 3), dtype=np.int64)
+        out = _ffi.Confidence(*[_vp(a) for a in (rank, list_n, margin, row_request, dec, nb, una, min_margin, weakest, confident, calib)])
+        summary = np.zeros(5, dtype=np.int64)
+        self._check(self._lib.tw_score_traces(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        k = int(self._n_trees)                                        # (of the stitch the call worked on: it succeeded)
+        return TraceConfidence(rank, list_n, margin, row_request, dec[:k].copy(), nb[:k].copy(), una[:k].copy(), min_margin[:k].copy(),
+                               weakest[:k].copy(), confident[:k].copy(), calib, summary, float(threshold), ed)
+
+    def score_timing(self):
+        """The last score_traces() on the device (HIP events, ms): decision kernel, row map + per-tree reduction, calibration."""
+        ms = np.zeros(22, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 22))
+        return dict(zip(("decisions", "trees", "calibration"), ms[19:22].tolist()))
 
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):

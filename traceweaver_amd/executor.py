@@ -97,7 +97,17 @@ def parse_args(argv=None):
                          "and print the culprit.  Stitches whether or not --stitch_out is given.  Default: off, nothing changes")
     ap.add_argument("--query_percentile", type=float, default=0.95, help="--attribute_out: the latency bracket, traces from this quantile on")
     ap.add_argument("--query_after", type=int, default=None, help="--attribute_out: only traces whose root starts at or after this time (us)")
-    ap.add_argument("-v", "--verbose", action="store_true", help="--attribute_out: print the same figures taken from the true traces")
+    ap.add_argument("-v", "--verbose", action="store_true",
+                    help="--attribute_out: print the same figures taken from the true traces; --confidence_out: print the calibration table")
+    ap.add_argument("--confidence_out", type=q, default=None,
+                    help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
+                         "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
+                         "the result to this .npz and print the counts.  Needs --stitch_out's conditions and --fit device-batch: the "
+                         "decisions are those of one batch resident on the device.  Default: off, nothing changes")
+    ap.add_argument("--min_margin", type=float, default=0.0,
+                    help="--confidence_out: a trace is confident when every decision in it is the best of its list by at least this margin")
+    ap.add_argument("--query_confident", type=int, default=0, choices=[0, 1],
+                    help="1: --attribute_out asks for whole AND confident traces only (needs --confidence_out)")
     ap.add_argument("--engine_library", type=q, default=None, help=argparse.SUPPRESS)   # tests: host-emulation build
     args = ap.parse_args(argv)
     if args.relative_path is None and args.absolute_path is None:
@@ -129,6 +139,15 @@ def unsupported(args):
         problems.append("--attribute_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.attribute_out and not 0.0 <= args.query_percentile < 1.0:
         problems.append("--query_percentile outside [0, 1)")
+    if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--confidence_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.confidence_out and args.fit != "device-batch":
+        problems.append("--confidence_out without --fit device-batch (the decisions are read from the batch resident on the device; the "
+                        "other fits solve the services one after the other)")
+    if args.confidence_out and args.min_margin != args.min_margin:
+        problems.append("--min_margin nan")
+    if args.query_confident and not (args.confidence_out and args.attribute_out):
+        problems.append("--query_confident 1 without --confidence_out and --attribute_out")
     return problems
 
 
@@ -160,17 +179,41 @@ def scale_load(units, args, trace_id, corpus):
     return out, factors, ranks
 
 
-def stitch_out(args, corpus, units, table, parents, n_traces, total, right):
-    """--stitch_out: all services in one batch, the assignments they were given, the span table's rows -> traces on the device."""
+CONFIDENCE_EDGES = (0.0, 1.0, 2.0, 5.0)   # --confidence_out: bucket edges of the calibration table (differences of log scores)
+
+
+def confidence_out(args, eng, st):
+    """--confidence_out: the decisions of the resident pass over the forest just stitched from it."""
+    from . import traces
+
+    c = eng.score_traces(args.min_margin, CONFIDENCE_EDGES)
+    traces.write_confidence_npz(args.confidence_out, c, st)
+    print("Trace confidence: %d of %d scored traces confident (margin >= %g); %d of %d decisions not best, %d unassigned"
+          % (c.n_confident, c.n_scored, args.min_margin, c.summary[3], c.summary[2], c.summary[4]))
+    if args.verbose:
+        for row in c.table():
+            span = "some decision not best" if row["bucket"] == 0 else "min margin in [%g, %g)" % (row["from"], row["to"])
+            print("    %-32s %7d whole traces, %7d exact, %8d decisions" % (span, row["trees"], row["exact"], row["decisions"]))
+
+
+def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solved=None):
+    """--stitch_out: all services in one batch, the assignments they were given, the span table's rows -> traces on the device.
+    solved: the engine that still holds the batch and the pass these assignments came from (--confidence_out)."""
     from . import traces
     from .engine import Engine
 
-    eng = Engine(args.device, lib_path=args.engine_library)
-    eng.load([u.arrays for u in units])
-    eng.set_truth([u.true_parent for u in units], [u.in_trace for u in units], n_traces)
-    eng.set_span_rows(*traces.rows_from_units(units, table))
-    eng.set_parents(parents)
-    st = eng.stitch(0)
+    if solved is not None:
+        eng = solved
+        eng.set_span_rows(*traces.rows_from_units(units, table))
+        st = eng.stitch(2)
+        confidence_out(args, eng, st)
+    else:
+        eng = Engine(args.device, lib_path=args.engine_library)
+        eng.load([u.arrays for u in units])
+        eng.set_truth([u.true_parent for u in units], [u.in_trace for u in units], n_traces)
+        eng.set_span_rows(*traces.rows_from_units(units, table))
+        eng.set_parents(parents)
+        st = eng.stitch(0)
     if args.attribute_out:
         attribute_out(args, eng, st, corpus, table)
     eng.close()
@@ -205,7 +248,7 @@ def attribute_out(args, eng, st, corpus, table):
     group, names = traces.groups_from_table(table, corpus)
     eng.set_row_groups(group, len(names))
     query = dict(percentile=args.query_percentile, start_min=args.query_after)
-    a = eng.attribute(**query)
+    a = eng.attribute(need_flags=traces.WHOLE | (traces.CONFIDENT if args.query_confident else 0), **query)
     traces.write_attribution_npz(args.attribute_out, a, names, st)
     print(culprit_line(a, names))
     if args.verbose:
@@ -379,15 +422,18 @@ def run(args):
                 print("WARNING: %d window(s) hit the node budget of the exact selection search: their selection is the best one found, "
                       "not a proven optimum (DESIGN.md section 6)" % unproven)
             print("--- %s seconds --- (%d services, both passes, refit, accuracy)" % (time.time() - t1, len(units)))
-            eng.close()
+            solved = eng if args.confidence_out else None          # (device-batch, no skip mode: pass 2 of every service is resident)
+            if solved is None:
+                eng.close()
             for u, ev, r in zip(units, per, res):
                 print("Accuracy for service %s: %.3f%%\n" % (u.service, ev["accuracy"] * 100))
                 print("Top K accuracy for service %s: %.3f%%\n" % (u.service, ev["topk_accuracy"] * 100))
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out:
-                stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()))
+            if args.stitch_out or args.attribute_out or args.confidence_out:
+                stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
+                           solved=solved)
         else:
             method = BASELINES[index]
             parents, bad, all_options = [], np.zeros(n_traces, dtype=np.uint8), []

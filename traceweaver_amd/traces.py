@@ -9,12 +9,17 @@ and `stitch_host` restates the device's computation in numpy -- test and cross-c
 Engine.attribute (tw_attribute_traces, csrc/tw_attr.h) answers the delay-culprit query on the stitched forest: `Attribution`
 is its result, `groups_from_table` the usual grouping (by service), `write_attribution_npz` stores it, and `attribute_host`
 restates the definitions in plain recursive Python -- the yardstick of the tests, nothing else.
+
+Engine.decisions / Engine.score_traces (tw_get_decisions, tw_score_traces, csrc/tw_conf.h) say which traces can be trusted:
+`TraceConfidence` is the result, `decisions_host` and `confidence_host` restate the per-request and the per-tree definitions
+in numpy for the tests, `write_confidence_npz` stores the result.
 """
 import sys
 
 import numpy as np
 
 WHOLE, UNASSIGNED, EXACT = 1, 2, 4   # bits of tree_flags
+CONFIDENT = 8                        # ... of the forest on the device after Engine.score_traces (Engine.attribute(need_flags=WHOLE | CONFIDENT))
 
 
 class StitchedTraces(object):
@@ -304,3 +309,119 @@ def write_attribution_npz(path, attribution, names, stitched):
             tree_path_rows=a.tree_path_rows, groups=a.groups, group_columns=np.array(GROUP_COLUMNS), summary=a.summary,
             group_names=np.array([str(x) for x in names]), mean_latency=np.array([a.mean_latency(g) for g in range(a.groups.shape[1])]),
             tree_root=stitched.tree_root, tree_latency=stitched.tree_latency, tree_flags=stitched.tree_flags)
+
+
+CALIB_COLUMNS = ("trees", "exact", "decisions")
+
+
+class TraceConfidence(object):
+    """rank / list_n / margin [requests of the batch]: the decision of every request (Engine.decisions); row_request [n_rows]:
+    the request whose incoming span the row is, -1 none; per tree of the stitch tree_decisions / tree_not_best /
+    tree_unassigned (counts), tree_min_margin (the smallest margin that is not NaN, +inf without one), tree_weakest_row (the
+    incoming span of the request that attains it, the smallest row on ties, -1 without one) and tree_confident (decisions > 0,
+    none of them not-best, min_margin >= threshold); calib [len(edges) + 2, 3] = CALIB_COLUMNS over the whole trees with a
+    decision -- bucket 0: some decision is not the best of its list, bucket 1 + j: min_margin has passed j edges; the exact
+    column is -1 without ground truth; summary = scored trees, confident trees, decisions, not-best, unassigned."""
+
+    FIELDS = ("rank", "list_n", "margin", "row_request", "tree_decisions", "tree_not_best", "tree_unassigned", "tree_min_margin",
+              "tree_weakest_row", "tree_confident", "calib", "summary")
+
+    def __init__(self, rank, list_n, margin, row_request, tree_decisions, tree_not_best, tree_unassigned, tree_min_margin,
+                 tree_weakest_row, tree_confident, calib, summary, threshold=0.0, edges=()):
+        self.rank, self.list_n, self.margin, self.row_request = rank, list_n, margin, row_request
+        self.tree_decisions, self.tree_not_best, self.tree_unassigned = tree_decisions, tree_not_best, tree_unassigned
+        self.tree_min_margin, self.tree_weakest_row, self.tree_confident = tree_min_margin, tree_weakest_row, tree_confident
+        self.calib = np.asarray(calib, dtype=np.int64)
+        self.summary = np.asarray(summary, dtype=np.int64)
+        self.threshold = float(threshold)
+        self.edges = np.asarray(edges, dtype=np.float64)
+
+    n_scored = property(lambda self: int(self.summary[0]))
+    n_confident = property(lambda self: int(self.summary[1]))
+
+    def same_as(self, other):
+        """Bit for bit: the doubles are compared as the integers they are stored as, so that NaN and the infinities count."""
+        bits = lambda a: np.asarray(a).view(np.int64) if np.asarray(a).dtype == np.float64 else np.asarray(a)
+        return all(np.array_equal(bits(getattr(self, k)), bits(getattr(other, k))) for k in self.FIELDS)
+
+    def table(self):
+        """One dict per bucket of the calibration table: its range of min_margin, CALIB_COLUMNS and the share of exact trees."""
+        lo = ["not best"] + [float("-inf")] + self.edges.tolist()
+        hi = [None] + self.edges.tolist() + [float("inf")]
+        return [dict([("bucket", b), ("from", lo[b]), ("to", hi[b])] + [(c, int(self.calib[b][i])) for i, c in enumerate(CALIB_COLUMNS)] +
+                     [("exact_share", float(self.calib[b][1]) / int(self.calib[b][0]) if self.calib[b][0] > 0 and self.calib[b][1] >= 0 else float("nan"))])
+                for b in range(len(self.calib))]
+
+
+def margin_key(margin):
+    """uint64 keys of binary64 values, ascending in the order -inf < ... < -0 < +0 < ... < +inf (conf_key of csrc/tw_conf.h)."""
+    b = np.ascontiguousarray(margin, dtype=np.float64).view(np.uint64)
+    return np.where((b >> np.uint64(63)) != 0, ~b, b | np.uint64(1 << 63))
+
+
+def decisions_host(result):
+    """The per-request definition of include/traceweaver_amd.h on one unit's candidate lists: `result` holds chosen [n],
+    topk_n [n] and topk_score [n, K] of the list the selection chose from (the layout of the oracle's run_pass: its topk_*,
+    not topk2_*).  Returns {rank, list_n, margin}."""
+    chosen = np.asarray(result["chosen"], dtype=np.int32)
+    n = np.asarray(result["topk_n"], dtype=np.int32)
+    s = np.asarray(result["topk_score"], dtype=np.float64)
+    margin = np.full(len(chosen), np.nan, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        for g, c in enumerate(chosen.tolist()):
+            if c == 0:
+                margin[g] = s[g, 0] - s[g, 1] if n[g] > 1 else np.inf
+            elif c > 0:
+                margin[g] = s[g, c] - s[g, 0]
+    margin[np.isnan(margin)] = np.nan                             # one NaN: the sign of inf - inf differs between machines
+    return {"rank": chosen.copy(), "list_n": n.copy(), "margin": margin}
+
+
+def confidence_host(stitched, in_rows, rank, margin, threshold=0.0, edges=(), list_n=None):
+    """What tw_score_traces computes from the decisions, restated from the definitions in plain numpy, for the tests.  in_rows,
+    rank, margin: per request of the batch (flat, or one array per unit)."""
+    flat = lambda a, dt: np.concatenate([np.asarray(x, dtype=dt).ravel() for x in a]) if isinstance(a, (list, tuple)) else np.asarray(a, dtype=dt)
+    in_rows, rank, margin = flat(in_rows, np.int64), flat(rank, np.int32), flat(margin, np.float64)
+    list_n = np.zeros(len(rank), dtype=np.int32) if list_n is None else flat(list_n, np.int32)
+    edges = np.asarray(edges, dtype=np.float64).ravel()
+    nt = stitched.n_trees
+    row_request = np.full(len(stitched.root), -1, dtype=np.int32)
+    row_request[in_rows] = np.arange(len(in_rows), dtype=np.int32)
+    dec, nb, una = (np.zeros(nt, dtype=np.int32) for _ in range(3))
+    min_margin = np.full(nt, np.inf, dtype=np.float64)
+    weakest = np.full(nt, -1, dtype=np.int32)
+    for k in range(nt):
+        g = row_request[stitched.tree_rows[int(stitched.tree_off[k]):int(stitched.tree_off[k + 1])]]
+        g = g[g >= 0]
+        dec[k], nb[k], una[k] = len(g), int((rank[g] != 0).sum()), int((rank[g] < 0).sum())
+        g = g[~np.isnan(margin[g])]
+        if len(g):
+            key = margin_key(margin[g])
+            at = g[key == key.min()]
+            min_margin[k] = margin[at[0]]
+            weakest[k] = in_rows[at].min()
+    confident = (dec > 0) & (nb == 0) & (min_margin >= threshold)
+    flags = np.asarray(stitched.tree_flags).astype(np.int64)
+    has_truth = int(stitched.counts[3]) >= 0
+    calib = np.zeros((len(edges) + 2, 3), dtype=np.int64)
+    for k in range(nt):
+        if (flags[k] & WHOLE) and dec[k] > 0:
+            b = 0 if nb[k] > 0 else 1 + int(sum(1 for x in edges if min_margin[k] >= x))
+            calib[b, 0] += 1
+            calib[b, 1] += 1 if flags[k] & EXACT else 0
+            calib[b, 2] += dec[k]
+    if not has_truth:
+        calib[:, 1] = -1
+    summary = [int((dec > 0).sum()), int(confident.sum()), int(dec.sum()), int(nb.sum()), int(una.sum())]
+    return TraceConfidence(rank, list_n, margin, row_request, dec, nb, una, min_margin, weakest, confident.astype(np.uint8), calib, summary,
+                           threshold, edges)
+
+
+def write_confidence_npz(path, confidence, stitched):
+    """The confidence of the stitched traces as one .npz next to the one write_npz stores: the arrays of TraceConfidence, the
+    query (threshold, edges) and the trees' roots and flags, so that it can be read without the stitched file."""
+    c = confidence
+    with open(path, "wb") as f:
+        np.savez_compressed(
+            f, threshold=np.float64(c.threshold), edges=c.edges, calib_columns=np.array(CALIB_COLUMNS),
+            tree_root=stitched.tree_root, tree_flags=stitched.tree_flags, **{k: getattr(c, k) for k in TraceConfidence.FIELDS})

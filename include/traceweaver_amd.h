@@ -250,7 +250,10 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * The last tw_attribute_traces (HIP events): ms[16] per-tree kernel, ms[17] selection (flags, sort, mark; incl. the host's
  * read of the eligible count), ms[18] group reduction.
  * The last tw_score_traces (HIP events): ms[19] decision kernel, ms[20] row map + per-tree reduction, ms[21] calibration
- * (tw_get_decisions alone writes ms[19]). */
+ * (tw_get_decisions alone writes ms[19]).
+ * The last tw_latency_distributions (HIP events): ms[22] cohorts + the two sweeps over the rows (counts, items; incl. the host's
+ * read of the item count), ms[23] sort, offsets and values, ms[24] quantiles and histogram (22 and 23: of the call that built
+ * the items). */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -478,6 +481,63 @@ typedef struct {
 } tw_confidence;
 int tw_get_decisions(tw_engine *e, int pass, int32_t *rank, int32_t *list_n, double *margin);
 int tw_score_traces(tw_engine *e, const tw_conf_query *q, const tw_confidence *out, int64_t *summary5);
+
+/* ---- per-service latency distributions and cohorts (csrc/tw_dist.h) -----------------------------------------------
+ *
+ * Replaces: what the delay-culprit query writes, src/query_engine/delay_culprit.py:80-97 -- per service not a mean but the
+ * list of the span latencies (duration_mus) of the selected requests, once for the true and once for the predicted traces,
+ * compared afterwards as distributions.  tw_attribute_traces gives seven totals per group; here the populations behind them
+ * leave the device sorted, with quantiles and a histogram, and split by cohort (requests served by version A or B of one
+ * service, say).  Both entry points work on what the last tw_attribute_traces call left on the device: its selection
+ * (tree_selected), its per-row times and the forest it ran on, whether of a pass, of pass 0 or of the truth.
+ *
+ * Definitions (integer microseconds throughout; a row with end < start counts as end = start, as in the attribution):
+ *   cohort     row_cohort [n_rows] in [-1, n_cohorts), -1 = the row says nothing.  tree_cohort[t] = the smallest label >= 0
+ *              among the tree's rows, -1 if there is none.  Without tw_set_row_cohorts, or after n_cohorts = 1 with
+ *              row_cohort = NULL, every tree has cohort 0.  A tree of cohort -1 is counted in no segment.
+ *   items      over the selected trees of cohort c >= 0:
+ *                metric 0  span latency   every row with row_group = g >= 0              its duration
+ *                metric 1  self time      the same rows                                  self_time
+ *                metric 2  path time      those of them on the critical path             path_time
+ *                metric 3  trace latency  one item per tree, no group                    tree_latency
+ *              Metric 0 is the reference's duration_mus lists.
+ *   segments   (c, m, g) for m < 3 and (c, 3): n_seg = n_cohorts * (3 * n_groups + 1), index c * (3 G + 1) + m * G + g, the
+ *              trace-latency segment last within a cohort.
+ *   outputs    caller-allocated, any may be NULL: tree_cohort [n_trees of the stitch]; seg_count, seg_sum [n_seg]; seg_off
+ *              [n_seg + 1] and values [n_items]: segment s owns values[seg_off[s] .. seg_off[s + 1]), ascending in signed
+ *              order (ties are equal integers: the array is fully determined); n_items = summary4[0], and a call with
+ *              values == NULL returns it, so that the caller can size the array (the sorted items stay on the device until
+ *              the next tw_attribute_traces / tw_set_row_cohorts: a second call only gathers and copies).
+ *              quantile [n_seg][n_q]: for probs[j] in [0, 1] the value at index min(n - 1, (int64)(probs[j] * (double)n))
+ *              of the segment of n items -- the product in binary64, the convention of k = (int64)(percentile * n_eligible)
+ *              --, INT64_MIN for an empty segment; n_q <= 32.
+ *              hist [n_seg][n_edges + 1]: strictly ascending int64 edges, n_edges <= 63; bin of v = #{j: v >= edges[j]},
+ *              the convention of the calibration table.
+ *   summary4   items, non-empty segments, selected trees counted (cohort >= 0), selected trees left out (cohort -1)
+ *
+ * tw_set_row_cohorts: optional; after tw_set_span_rows (TW_ERR_STATE before); ranges are checked on the host (TW_ERR_ARG:
+ * n_cohorts < 1, a label outside [-1, n_cohorts), NULL with n_cohorts != 1); dropped with the row maps, like the row groups.
+ * tw_latency_distributions: TW_ERR_STATE before a tw_attribute_traces on the current forest (a new tw_stitch_traces, new row
+ * groups and everything that drops the forest drop the attribution).  TW_ERR_ARG: a prob that is NaN or outside [0, 1],
+ * edges not strictly ascending, n_q outside [0, 32], n_edges outside [0, 63].  TW_ERR_UNSUPPORTED: n_seg > 2^24.
+ * No floating point on the device but the one product probs[j] * n (a single binary64 multiplication, built with
+ * -ffp-contract=off), equal to the restatement bit for bit.  The atomics are integer adds and minima of which only the
+ * result is read; the cursor that hands out item positions decides where an item lies before the sort, never what the
+ * output holds: results do not depend on scheduling.  Covers one engine's batch.  Timing: tw_get_timing slots 22..24 (items
+ * and counts; sort, offsets and values; quantiles and histogram; HIP events, ms; 22 and 23 are those of the call that
+ * built the items). */
+typedef struct {
+    int32_t n_q;
+    const double *probs;
+    int32_t n_edges;
+    const int64_t *edges;
+} tw_dist_query;
+typedef struct {
+    int32_t *tree_cohort;
+    int64_t *seg_count, *seg_sum, *seg_off, *values, *quantile, *hist;
+} tw_distributions;
+int tw_set_row_cohorts(tw_engine *e, int32_t n_cohorts, const int32_t *row_cohort);
+int tw_latency_distributions(tw_engine *e, const tw_dist_query *q, const tw_distributions *out, int64_t *summary4);
 
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,

@@ -25,6 +25,7 @@
 #include "tw_stitch.h"
 #include "tw_attr.h"
 #include "tw_conf.h"
+#include "tw_dist.h"
 
 using namespace tw;
 
@@ -205,6 +206,15 @@ struct tw_engine {
     int64_t conf_rows_cap = 0;
     hipEvent_t cf_ev[4] = {};
     double cf_ms[3] = {0, 0, 0};            // decision kernel, row map + per-tree reduction, calibration
+    // tw_set_row_cohorts / tw_latency_distributions (tw_dist.h): they read what the last tw_attribute_traces left behind (attributed:
+    // dropped by a new stitch, new row groups and whatever drops the forest); the labels are dropped with the row maps; dist_ready:
+    // the sorted items of that attribution and these labels are resident, a further call only gathers
+    DistDev D{};
+    bool attributed = false, cohorts_set = false, dist_ready = false;
+    int64_t cohort_rows_cap = 0, dist_trees_cap = 0, dist_seg_cap = 0, dist_out_cap = 0 /* segments */, dist_items = 0;
+    DistKeyDev dist_key{};
+    hipEvent_t ds_ev[5] = {};
+    double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
 };
 
 namespace {
@@ -268,6 +278,8 @@ void free_all(tw_engine* e) {
     e->S = StitchDev{}; e->rows_set = false; e->rows_cap = 0; e->given_parent = nullptr; e->parents_given = false;
     e->A = AttrDev{}; e->groups_set = false; e->stitched = false; e->groups_cap = 0; e->attr_rows_cap = 0;
     e->C = ConfDev{}; e->conf_rows_cap = 0;
+    e->D = DistDev{}; e->attributed = false; e->cohorts_set = false; e->dist_ready = false;
+    e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;
     e->state = ST_EMPTY;
 }
 
@@ -947,7 +959,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     e->state = ST_LOADED; e->pass1_done = false;
     e->parents_given = false;
     e->rows_set = false;   // every list was re-sorted: in_row / out_row no longer name the spans at these positions
-    e->groups_set = false; e->stitched = false;
+    e->groups_set = false; e->stitched = false; e->cohorts_set = false;
     for (int E = 0; E <= kMaxEp; E++) { e->wide_pass1[E] = -1; e->hard_pass1[E] = -1; e->split_pass1[E] = -1; }
     return TW_OK;
 }
@@ -1050,6 +1062,8 @@ void tw_destroy(tw_engine* e) {
         if (e->at_ev[i]) (void)hipEventDestroy(e->at_ev[i]);
     for (int i = 0; i < 4; i++)
         if (e->cf_ev[i]) (void)hipEventDestroy(e->cf_ev[i]);
+    for (int i = 0; i < 5; i++)
+        if (e->ds_ev[i]) (void)hipEventDestroy(e->ds_ev[i]);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1782,6 +1796,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 6 && 10 + i < n; i++) ms[10 + i] = e->st_ms[i];   // the last tw_stitch_traces
     for (int i = 0; i < 3 && 16 + i < n; i++) ms[16 + i] = e->at_ms[i];   // the last tw_attribute_traces
     for (int i = 0; i < 3 && 19 + i < n; i++) ms[19 + i] = e->cf_ms[i];   // the last tw_score_traces
+    for (int i = 0; i < 3 && 22 + i < n; i++) ms[22 + i] = e->ds_ms[i];   // the last tw_latency_distributions
     return TW_OK;
 }
 
@@ -1980,7 +1995,7 @@ int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const 
     for (int i = 0; i < 6; i++)
         if (e->st_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->st_ev[i]));
     e->rows_set = true;
-    e->groups_set = false; e->stitched = false;   // (new row maps: the groups name rows of the old ones)
+    e->groups_set = false; e->stitched = false; e->cohorts_set = false;   // (new row maps: the groups and the cohort labels name rows of the old ones)
     return TW_OK;
 }
 
@@ -2056,7 +2071,7 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
         if (!ok) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
     }
     HIPCHK(hipSetDevice(e->device));
-    e->stitched = false;
+    e->stitched = false; e->attributed = false; e->dist_ready = false;
     const StitchDev& S = e->S;
     const bool has_truth = e->truth != nullptr;
     const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
@@ -2128,6 +2143,7 @@ int tw_set_row_groups(tw_engine* e, int32_t n_groups, const int32_t* row_group) 
     for (int64_t r = 0; r < n_rows; r++)   // k_attr_reduce indexes the totals with these values
         if (row_group[r] < -1 || row_group[r] >= n_groups) return fail(e, TW_ERR_ARG, "tw_set_row_groups: row_group outside [-1, n_groups)");
     HIPCHK(hipSetDevice(e->device));
+    e->attributed = false; e->dist_ready = false;   // (the per-row flags of the last attribution name the old groups)
     AttrDev& A = e->A;
     int rc;
 #define AALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
@@ -2162,6 +2178,7 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
     if (!(q->percentile >= 0.0 && q->percentile < 1.0)) return fail(e, TW_ERR_ARG, "tw_attribute_traces: percentile outside [0, 1)");
     if (q->start_min > q->start_max) return fail(e, TW_ERR_ARG, "tw_attribute_traces: start_min > start_max");
     HIPCHK(hipSetDevice(e->device));
+    e->attributed = false; e->dist_ready = false;
     const StitchDev& S = e->S;
     AttrDev& A = e->A;
     const int64_t nt = e->st_trees, G = A.n_groups;
@@ -2242,6 +2259,7 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
             if (cols[c] != nullptr)
                 for (int64_t g = 0; g < G; g++) cols[c][g] = (int64_t)totals[(size_t)(c * G + g)];
     }
+    e->attributed = true;
     return TW_OK;
 }
 
@@ -2368,6 +2386,206 @@ int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* o
         D2H(out->tree_confident, C.confident, (size_t)nt);
 #undef D2H
         HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return TW_OK;
+}
+
+/* ---- per-service latency distributions and cohorts (tw_dist.h) ----------------------------------------------------- */
+int tw_set_row_cohorts(tw_engine* e, int32_t n_cohorts, const int32_t* row_cohort) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_cohorts before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
+    if (n_cohorts < 1) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: n_cohorts must be positive");
+    if (row_cohort == nullptr && n_cohorts != 1) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: no labels with n_cohorts != 1");
+    const int64_t n_rows = e->S.n_rows;
+    if (row_cohort != nullptr)
+        for (int64_t r = 0; r < n_rows; r++)   // k_dist_items indexes the segments with the trees' cohorts
+            if (row_cohort[r] < -1 || row_cohort[r] >= n_cohorts) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: row_cohort outside [-1, n_cohorts)");
+    HIPCHK(hipSetDevice(e->device));
+    DistDev& D = e->D;
+    e->dist_ready = false;
+    if (row_cohort == nullptr) {   // back to one cohort that holds every tree
+        e->cohorts_set = false;
+        return TW_OK;
+    }
+    if (D.row_cohort == nullptr || n_rows > e->cohort_rows_cap) {   // (freed with the batch)
+        int32_t* label_d;
+        const int rc = dev_alloc(e, &label_d, n_rows);
+        if (rc != TW_OK) return rc;
+        D.row_cohort = label_d;
+        e->cohort_rows_cap = n_rows;
+    }
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(D.row_cohort), row_cohort, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    D.n_cohorts = n_cohorts;
+    e->cohorts_set = true;
+    return TW_OK;
+}
+
+namespace {
+
+int dist_bits(unsigned long long x) {   // bits needed to write x
+    int b = 0;
+    while (x != 0) { b++; x >>= 1; }
+    return b;
+}
+
+// Cohorts, counts, items, sort, offsets and values of the resident attribution into e->D; ds_ev[0] .. ds_ev[2] around the two halves.
+int dist_build(tw_engine* e) {
+    const StitchDev& S = e->S;
+    const AttrDev& A = e->A;
+    DistDev D = e->D;   // (the kernels' view: row_cohort is null without labels)
+    const int64_t nt = e->st_trees;
+    if (!e->cohorts_set) { D.row_cohort = nullptr; D.n_cohorts = 1; }
+    D.n_seg = (int64_t)D.n_cohorts * (3 * (int64_t)A.n_groups + 1);
+    int rc;
+#define DALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
+    if (D.counters == nullptr) DALLOC(D.counters, kDistCounters);   // (all of them freed with the batch)
+    if (D.tree_cohort == nullptr || nt > e->dist_trees_cap) { DALLOC(D.tree_cohort, nt); e->dist_trees_cap = nt; }
+    if (D.seg_count == nullptr || D.n_seg > e->dist_seg_cap) {
+        DALLOC(D.seg_count, D.n_seg); DALLOC(D.seg_sum, D.n_seg); DALLOC(D.seg_off, D.n_seg + 1);
+        e->dist_seg_cap = D.n_seg;
+    }
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 tb(threads);
+    // workgroups stride over the rows: at most 2048 of them clear and add up an LDS table
+    const dim3 rows((unsigned)std::min<int64_t>((S.n_rows + threads - 1) / threads, 2048));
+    unsigned long long counters[kDistCounters] = {0, ~0ull, 0, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(D.counters, counters, sizeof(counters), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(D.seg_count, 0, sizeof(unsigned long long) * (size_t)D.n_seg, e->stream));
+    HIPCHK(hipMemsetAsync(D.seg_sum, 0, sizeof(unsigned long long) * (size_t)D.n_seg, e->stream));
+    HIPCHK(hipEventRecord(e->ds_ev[0], e->stream));
+    if (D.row_cohort != nullptr) {
+        // one wavefront per kDistTrees trees, persistent: at most 8192 workgroups of four
+        const unsigned gthreads = e->coop >= 64 ? 64u * kDistWaves : (unsigned)e->coop;
+        const int64_t want = (nt / kDistTrees + 1 + kDistWaves - 1) / kDistWaves;
+        hipLaunchKernelGGL(k_dist_cohort, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, D, nt);
+    } else {
+        HIPCHK(hipMemsetAsync(D.tree_cohort, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(nt, 1), e->stream));
+    }
+    DistKeyDev K{};
+    hipLaunchKernelGGL(k_dist_items<false>, rows, tb, 0, e->stream, S, A, D, K);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t n_items = (int64_t)counters[0];
+    int seg_bits = dist_bits((unsigned long long)(D.n_seg - 1));
+    if (n_items > 0) {
+        K.vmin = counters[1] ^ (1ull << 63);
+        K.vbits = dist_bits(counters[2] - counters[1]);
+        K.wide = seg_bits + K.vbits > 64 ? 1 : 0;
+    }
+    if (D.key_a == nullptr || n_items > D.items_cap) {
+        DALLOC(D.key_a, n_items); DALLOC(D.key_b, n_items); DALLOC(D.values, n_items);
+        D.seg_a = nullptr; D.seg_b = nullptr;
+        D.items_cap = std::max<int64_t>(n_items, 1);
+    }
+    if (K.wide && D.seg_a == nullptr) { DALLOC(D.seg_a, D.items_cap); DALLOC(D.seg_b, D.items_cap); }
+#undef DALLOC
+    if (n_items > 0) hipLaunchKernelGGL(k_dist_items<true>, rows, tb, 0, e->stream, S, A, D, K);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ds_ev[1], e->stream));
+    const unsigned long long* sorted = D.key_a;
+    if (n_items > 0 && !K.wide) {
+        const unsigned end_bit = (unsigned)std::max(seg_bits + K.vbits, 1);
+        size_t bytes = 0;
+        HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, D.key_a, D.key_b, (size_t)n_items, 0u, end_bit, e->stream));
+        rc = ensure_sort_tmp(e, bytes);
+        if (rc != TW_OK) return rc;
+        bytes = e->sort_tmp_bytes;
+        HIPCHK(rocprim::radix_sort_keys(e->sort_tmp, bytes, D.key_a, D.key_b, (size_t)n_items, 0u, end_bit, e->stream));
+        sorted = D.key_b;
+    } else if (n_items > 0) {   // stable: by value, then by segment
+        size_t bytes = 0, bytes2 = 0;
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.key_a, D.key_b, D.seg_a, D.seg_b, (size_t)n_items, 0u, (unsigned)K.vbits, e->stream));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes2, D.seg_b, D.seg_a, D.key_b, D.key_a, (size_t)n_items, 0u, (unsigned)seg_bits, e->stream));
+        rc = ensure_sort_tmp(e, std::max(bytes, bytes2));
+        if (rc != TW_OK) return rc;
+        bytes = e->sort_tmp_bytes;
+        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.key_a, D.key_b, D.seg_a, D.seg_b, (size_t)n_items, 0u, (unsigned)K.vbits, e->stream));
+        bytes = e->sort_tmp_bytes;
+        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.seg_b, D.seg_a, D.key_b, D.key_a, (size_t)n_items, 0u, (unsigned)seg_bits, e->stream));
+    }
+    hipLaunchKernelGGL(k_dist_scan, dim3(1), tb, 0, e->stream, D);
+    if (n_items > 0) hipLaunchKernelGGL(k_dist_unpack, dim3((unsigned)((n_items + threads - 1) / threads)), tb, 0, e->stream, D, K, sorted, n_items);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ds_ev[2], e->stream));
+    HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (counters[7] != 0 || (int64_t)counters[6] != n_items) return fail(e, TW_ERR_DEVICE, "tw_latency_distributions: the two sweeps over the rows disagree on the number of items");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[0], e->ds_ev[1])); e->ds_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[1], e->ds_ev[2])); e->ds_ms[1] = ms;
+    const int32_t* labels = e->D.row_cohort;
+    const int32_t n_cohorts = e->D.n_cohorts;
+    e->D = D;
+    e->D.row_cohort = labels; e->D.n_cohorts = n_cohorts;   // (the labels stay set whether or not this call used them)
+    e->dist_key = K;
+    e->dist_items = n_items;
+    e->dist_ready = true;
+    return TW_OK;
+}
+
+}  // namespace
+
+int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_distributions* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set || !e->stitched || !e->groups_set || !e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_latency_distributions needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
+                                     "whatever drops the forest drop the attribution)");
+    if (q->n_q < 0 || q->n_q > kDistMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, "tw_latency_distributions: n_q outside [0, 32]");
+    if (q->n_edges < 0 || q->n_edges > kDistMaxEdges || (q->n_edges > 0 && q->edges == nullptr))
+        return fail(e, TW_ERR_ARG, "tw_latency_distributions: n_edges outside [0, 63]");
+    DistQueryDev Q{};
+    Q.n_q = q->n_q;
+    Q.n_edges = q->n_edges;
+    for (int j = 0; j < q->n_q; j++) {
+        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, "tw_latency_distributions: a prob outside [0, 1]");
+        Q.probs[j] = q->probs[j];
+    }
+    for (int j = 0; j < q->n_edges; j++) {
+        if (j > 0 && !(q->edges[j] > q->edges[j - 1])) return fail(e, TW_ERR_ARG, "tw_latency_distributions: the edges must be strictly ascending");
+        Q.edges[j] = q->edges[j];
+    }
+    const int64_t n_seg = (int64_t)(e->cohorts_set ? e->D.n_cohorts : 1) * (3 * (int64_t)e->A.n_groups + 1);
+    if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_latency_distributions: more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
+    HIPCHK(hipSetDevice(e->device));
+    for (int i = 0; i < 5; i++)
+        if (e->ds_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->ds_ev[i]));
+    int rc;
+    if (!e->dist_ready && (rc = dist_build(e)) != TW_OK) return rc;
+    DistDev& D = e->D;
+    const int64_t nt = e->st_trees, n_items = e->dist_items;
+    const int bins = Q.n_edges + 1;
+    const bool want_q = out != nullptr && out->quantile != nullptr && Q.n_q > 0, want_h = out != nullptr && out->hist != nullptr;
+    if ((want_q || want_h) && (D.quant == nullptr || n_seg > e->dist_out_cap)) {   // room for any query on these segments (freed with the batch)
+        if ((rc = dev_alloc(e, &D.quant, n_seg * kDistMaxQ)) != TW_OK || (rc = dev_alloc(e, &D.hist, n_seg * (kDistMaxEdges + 1))) != TW_OK) return rc;
+        e->dist_out_cap = n_seg;
+    }
+    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const dim3 tb(threads);
+    HIPCHK(hipEventRecord(e->ds_ev[3], e->stream));
+    if (want_q) hipLaunchKernelGGL(k_dist_quantiles, dim3((unsigned)((n_seg * Q.n_q + threads - 1) / threads)), tb, 0, e->stream, D, Q);
+    if (want_h) hipLaunchKernelGGL(k_dist_hist, dim3((unsigned)((n_seg * bins + threads - 1) / threads)), tb, 0, e->stream, D, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ds_ev[4], e->stream));
+    unsigned long long counters[kDistCounters];
+    HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    if (out != nullptr) {
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+        D2H(out->tree_cohort, D.tree_cohort, sizeof(int32_t) * (size_t)nt);
+        D2H(out->seg_count, D.seg_count, sizeof(int64_t) * (size_t)n_seg);
+        D2H(out->seg_sum, D.seg_sum, sizeof(int64_t) * (size_t)n_seg);
+        D2H(out->seg_off, D.seg_off, sizeof(int64_t) * (size_t)(n_seg + 1));
+        D2H(out->values, D.values, sizeof(int64_t) * (size_t)n_items);
+        if (want_q) D2H(out->quantile, D.quant, sizeof(int64_t) * (size_t)(n_seg * Q.n_q));
+        if (want_h) D2H(out->hist, D.hist, sizeof(int64_t) * (size_t)(n_seg * bins));
+#undef D2H
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[3], e->ds_ev[4])); e->ds_ms[2] = ms;
+    if (summary != nullptr) {
+        summary[0] = n_items; summary[1] = (int64_t)counters[5]; summary[2] = (int64_t)counters[3]; summary[3] = (int64_t)counters[4];
     }
     return TW_OK;
 }

@@ -175,6 +175,7 @@ class Engine(object):
             batch_size, batch_size_mis, _ffi.TW_TOPK, _vp(arrays["unit_time_scale"]),
             ctypes.cast(skip_arr, ctypes.c_void_p) if skip_arr is not None else ctypes.c_void_p(0), _vp(arrays["unit_part"]))
         self._check(self._lib.tw_load_batch(self._h, ctypes.byref(b), 0))
+        self._n_cohorts = 1                                           # (the cohort labels go with the row maps)
         self._last_pass, self._n_rows = 0, 0
         self._in_off = in_off
         self._ie_off = np.concatenate([[0], np.cumsum([u.n_in * u.E for u in units])]).astype(np.int64)
@@ -334,6 +335,7 @@ class Engine(object):
         op = np.zeros(n_out, dtype=np.int32)
         ts = np.zeros(len(self.units), dtype=np.float64)
         self._check(self._lib.tw_scale_load(self._h, _vp(f), _vp(tr), _vp(ip), _vp(op), _vp(ts)))
+        self._n_cohorts = 1
         self._last_pass = 0
         out, o = [], 0
         for k, u in enumerate(self.units):
@@ -404,6 +406,7 @@ class Engine(object):
             raise ValueError("the table's columns differ in length")
         self._check(self._lib.tw_set_span_rows(self._h, len(link), _vp(ir), _vp(orow), _vp(link), _vp(kind), _vp(start), _vp(end)))
         self._n_rows = len(link)
+        self._n_cohorts = 1
 
     def set_parents(self, parents):
         """An assignment that this engine's last pass did not produce (per unit [E, n_in]; services solved one after the
@@ -517,6 +520,54 @@ class Engine(object):
         ms = np.zeros(22, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 22))
         return dict(zip(("decisions", "trees", "calibration"), ms[19:22].tolist()))
+
+    def set_row_cohorts(self, labels, n_cohorts):
+        """The cohort label of every span-table row, in [0, n_cohorts) or -1 = the row says nothing (tw_set_row_cohorts): a
+        tree's cohort is the smallest label among its rows.  labels=None with n_cohorts=1: back to one cohort that holds every
+        tree.  Call it after set_span_rows; dropped with the row maps."""
+        if labels is None:
+            self._check(self._lib.tw_set_row_cohorts(self._h, int(n_cohorts), None))
+            self._n_cohorts = 1
+            return
+        c = np.ascontiguousarray(labels, dtype=np.int32)
+        if len(c) != int(getattr(self, "_n_rows", 0)):
+            raise ValueError("labels do not match the span rows")
+        self._check(self._lib.tw_set_row_cohorts(self._h, int(n_cohorts), _vp(c)))
+        self._n_cohorts = int(n_cohorts)
+
+    def distributions(self, probs=(0.5, 0.9, 0.95, 0.99), edges=None, values=True):
+        """The populations behind the last attribute() (tw_latency_distributions): per cohort, metric (span latency, self time,
+        path time, trace latency) and group the sorted values of the selected trees, their count and sum, the quantiles at
+        `probs` and, with `edges` (strictly ascending integers, at most 63), a histogram.  values=False leaves the sorted values on
+        the device (`values` is then empty).  Returns traces.LatencyDistributions."""
+        from .traces import LatencyDistributions
+
+        G, C = int(getattr(self, "_n_groups", 0)), int(getattr(self, "_n_cohorts", 1))
+        n_seg = C * (3 * G + 1)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        ed = np.ascontiguousarray(() if edges is None else edges, dtype=np.int64).ravel()
+        q = _ffi.DistQuery(len(pr), _vp(pr) if len(pr) else ctypes.c_void_p(0), len(ed), _vp(ed) if len(ed) else ctypes.c_void_p(0))
+        nq, bins = min(len(pr), _ffi.TW_DIST_MAX_Q), min(len(ed), _ffi.TW_DIST_MAX_EDGES) + 1
+        tree_cohort = np.empty(max(int(getattr(self, "_n_trees", 0)), 1), dtype=np.int32)
+        seg_count, seg_sum = np.zeros(n_seg, dtype=np.int64), np.zeros(n_seg, dtype=np.int64)
+        seg_off = np.zeros(n_seg + 1, dtype=np.int64)
+        quantile = np.zeros((n_seg, nq), dtype=np.int64)
+        hist = np.zeros((n_seg, bins), dtype=np.int64)
+        summary = np.zeros(4, dtype=np.int64)
+        out = _ffi.Distributions(_vp(tree_cohort), _vp(seg_count), _vp(seg_sum), _vp(seg_off), None, _vp(quantile) if nq else None, _vp(hist))
+        self._check(self._lib.tw_latency_distributions(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        values = np.empty(int(summary[0]) if values else 0, dtype=np.int64)   # the sorted items are resident: the second call only copies them
+        if len(values):
+            only = _ffi.Distributions(None, None, None, None, _vp(values), None, None)
+            self._check(self._lib.tw_latency_distributions(self._h, ctypes.byref(q), ctypes.byref(only), None))
+        return LatencyDistributions(tree_cohort[:int(self._n_trees)].copy(), seg_count, seg_sum, seg_off, values, quantile, hist, summary, C, G, pr, ed)
+
+    def distributions_timing(self):
+        """The last distributions() on the device (HIP events, ms): items and counts (cohorts, the two sweeps over the rows);
+        sort, offsets and values; quantiles and histogram."""
+        ms = np.zeros(25, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 25))
+        return dict(zip(("items", "sort", "quantiles"), ms[22:25].tolist()))
 
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):

@@ -98,7 +98,17 @@ def parse_args(argv=None):
     ap.add_argument("--query_percentile", type=float, default=0.95, help="--attribute_out: the latency bracket, traces from this quantile on")
     ap.add_argument("--query_after", type=int, default=None, help="--attribute_out: only traces whose root starts at or after this time (us)")
     ap.add_argument("-v", "--verbose", action="store_true",
-                    help="--attribute_out: print the same figures taken from the true traces; --confidence_out: print the calibration table")
+                    help="--attribute_out: print the same figures taken from the true traces; --confidence_out: print the calibration table; "
+                         "--latency_out: print the culprit's quantiles next to its mean")
+    ap.add_argument("--latency_out", type=q, default=None,
+                    help="write the latency distributions behind the delay-culprit query to this .npz (tw_latency_distributions: per service "
+                         "the sorted span latencies, self times and critical-path times of the selected traces, and the traces' latencies, "
+                         "with counts, sums and quantiles -- the lists delay_culprit.py writes).  Needs --attribute_out's conditions and runs "
+                         "its query.  Default: off, nothing changes")
+    ap.add_argument("--quantiles", type=q, default="0.5,0.95,0.99", help="--latency_out: the quantiles, comma-separated, each in [0, 1]")
+    ap.add_argument("--cohort_service", type=q, default=None,
+                    help="--latency_out: split the traces into cohorts by the operation of this service's span in them (the smallest "
+                         "operation index where a trace holds several); traces without a span of the service are left out")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
                          "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
@@ -123,6 +133,15 @@ def requested(args):
     return idx if idx else [10]
 
 
+def quantiles_of(args):
+    """--quantiles as a list of floats, None if it is malformed."""
+    try:
+        probs = [float(x) for x in args.quantiles.split(",") if x.strip() != ""]
+    except ValueError:
+        return None
+    return probs if 0 < len(probs) <= 32 and all(0.0 <= p <= 1.0 for p in probs) else None
+
+
 def unsupported(args):
     problems = []
     bad = [i for i in requested(args) if i != 10 and i not in BASELINES]
@@ -139,6 +158,14 @@ def unsupported(args):
         problems.append("--attribute_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.attribute_out and not 0.0 <= args.query_percentile < 1.0:
         problems.append("--query_percentile outside [0, 1)")
+    if args.latency_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--latency_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.latency_out and not args.attribute_out and not 0.0 <= args.query_percentile < 1.0:
+        problems.append("--query_percentile outside [0, 1)")
+    if args.latency_out and quantiles_of(args) is None:
+        problems.append("--quantiles %s (up to 32 comma-separated numbers in [0, 1])" % args.quantiles)
+    if args.cohort_service and not args.latency_out:
+        problems.append("--cohort_service without --latency_out")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--confidence_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.confidence_out and args.fit != "device-batch":
@@ -214,7 +241,7 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         eng.set_span_rows(*traces.rows_from_units(units, table))
         eng.set_parents(parents)
         st = eng.stitch(0)
-    if args.attribute_out:
+    if args.attribute_out or args.latency_out:
         attribute_out(args, eng, st, corpus, table)
     eng.close()
     if not args.stitch_out:
@@ -241,19 +268,61 @@ def culprit_line(a, names, head="Delay culprit"):
         head, names[g], a.mean_latency(g), a.n_selected, a.n_eligible, 100.0 * float(a.group_path_time[g]) / total if total else 0.0)
 
 
+def cohort_labels(args, corpus, table, names):
+    """--cohort_service: the rows of that service labelled by the index of their operation among the service's operations (in
+    ascending order of the string id), every other row -1.  The span table carries no instance column; without an operation column
+    either the flag is refused."""
+    if args.cohort_service not in names:
+        raise SystemExit("--cohort_service %s: no such service in the span table (services: %s)" % (args.cohort_service, ", ".join(str(x) for x in names)))
+    if "op_name" not in table:
+        raise SystemExit("--cohort_service: the span table carries neither an operation nor an instance column to tell cohorts apart")
+    service = np.asarray(table["service"])
+    of = np.array([corpus.string(x) == args.cohort_service for x in np.unique(service)])[np.unique(service, return_inverse=True)[1]]
+    ops, inverse = np.unique(np.asarray(table["op_name"])[of], return_inverse=True)
+    label = np.full(len(service), -1, dtype=np.int32)
+    label[of] = inverse
+    return label, [corpus.string(x) for x in ops]
+
+
+def quantile_line(d, g, head):
+    """The quantiles of the span latency of group g, per cohort."""
+    parts = []
+    for c in range(d.n_cohorts):
+        s = d.index(c, 0, g)
+        if d.seg_count[s] > 0:
+            parts.append("%s%s over %d spans" % ("cohort %d: " % c if d.n_cohorts > 1 else "",
+                                                 ", ".join("p%g %d us" % (100 * p, d.quantile[s][j]) for j, p in enumerate(d.probs.tolist())), d.seg_count[s]))
+    return "%s: %s" % (head, "; ".join(parts) if parts else "no spans")
+
+
 def attribute_out(args, eng, st, corpus, table):
-    """--attribute_out: the delay-culprit query on the forest just stitched, groups by service."""
+    """--attribute_out / --latency_out: the delay-culprit query on the forest just stitched, groups by service, and the
+    distributions behind its answer."""
     from . import traces
 
     group, names = traces.groups_from_table(table, corpus)
     eng.set_row_groups(group, len(names))
+    if args.latency_out and args.cohort_service:
+        label, cohort_names = cohort_labels(args, corpus, table, names)
+        eng.set_row_cohorts(label, len(cohort_names))
     query = dict(percentile=args.query_percentile, start_min=args.query_after)
     a = eng.attribute(need_flags=traces.WHOLE | (traces.CONFIDENT if args.query_confident else 0), **query)
-    traces.write_attribution_npz(args.attribute_out, a, names, st)
-    print(culprit_line(a, names))
+    if args.attribute_out:
+        traces.write_attribution_npz(args.attribute_out, a, names, st)
+        print(culprit_line(a, names))
+    if args.latency_out:
+        d = eng.distributions(quantiles_of(args))
+        traces.write_distributions_npz(args.latency_out, d, names)
+        print("Latency distributions: %d values in %d segments over %d traces (%d without a cohort)" % (d.n_items, d.summary[1], d.summary[2], d.summary[3]))
+        if args.verbose and a.culprit >= 0:
+            print(quantile_line(d, a.culprit, "Culprit span latency"))
     if args.verbose:
         eng.stitch(truth=True)
-        print(culprit_line(eng.attribute(**query), names, "Delay culprit (true traces)"))
+        b = eng.attribute(**query)
+        if args.attribute_out:
+            print(culprit_line(b, names, "Delay culprit (true traces)"))
+        if args.latency_out and b.culprit >= 0:
+            print(quantile_line(eng.distributions(quantiles_of(args)), b.culprit, "Culprit span latency (true traces)"))
 
 
 def run(args):
@@ -431,7 +500,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out or args.confidence_out:
+            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
                            solved=solved)
         else:

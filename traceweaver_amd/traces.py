@@ -13,6 +13,11 @@ restates the definitions in plain recursive Python -- the yardstick of the tests
 Engine.decisions / Engine.score_traces (tw_get_decisions, tw_score_traces, csrc/tw_conf.h) say which traces can be trusted:
 `TraceConfidence` is the result, `decisions_host` and `confidence_host` restate the per-request and the per-tree definitions
 in numpy for the tests, `write_confidence_npz` stores the result.
+
+Engine.set_row_cohorts / Engine.distributions (tw_set_row_cohorts, tw_latency_distributions, csrc/tw_dist.h) give the populations
+behind an attribution: `LatencyDistributions` is the result, `distributions_host` restates the definitions in numpy for the
+tests, `compare_distributions` sets two results side by side (predicted against true, cohort against cohort) on the host,
+`write_distributions_npz` stores a result.
 """
 import sys
 
@@ -202,27 +207,10 @@ def groups_from_table(table, corpus=None):
     return inverse.astype(np.int32), names
 
 
-def attribute_host(stitched, link, row_start, row_end, row_group, n_groups, percentile=0.0, start_min=None, start_max=None,
-                   need_flags=WHOLE, skip_flags=UNASSIGNED):
-    """What tw_attribute_traces computes, restated from the definitions: recursive and obvious, for the tests."""
-    link = np.asarray(link, dtype=np.int64)
-    start = [int(x) for x in row_start]
-    end = [max(int(e), s) for e, s in zip(row_end, start)]
-    group = [int(x) for x in row_group]
-    n = len(link)
-    children = [[] for _ in range(n)]
-    for c in range(n):
-        if link[c] >= 0:
-            children[int(link[c])].append(c)
-    self_time = np.zeros(n, dtype=np.int64)
-    for p in range(n):
-        clipped = sorted((max(start[c], start[p]), min(end[c], end[p])) for c in children[p])
-        covered, reach = 0, start[p]
-        for cs, ce in clipped:
-            if ce > cs:
-                covered += max(0, ce - max(cs, reach))
-                reach = max(reach, ce)
-        self_time[p] = end[p] - start[p] - covered
+def critical_paths_host(children, start, end, roots):
+    """(path_time, walked) of the forest with these child lists, the walk of include/traceweaver_amd.h from every root: recursive
+    and obvious, for the restatements (end already clamped to start)."""
+    n = len(start)
     path_time = np.zeros(n, dtype=np.int64)
     walked = np.zeros(n, dtype=bool)
 
@@ -247,10 +235,35 @@ def attribute_host(stitched, link, row_start, row_end, row_group, n_groups, perc
     limit = sys.getrecursionlimit()
     sys.setrecursionlimit(max(limit, 20000))
     try:
-        for r in stitched.tree_root:
+        for r in roots:
             walk(int(r), start[int(r)], end[int(r)])
     finally:
         sys.setrecursionlimit(limit)
+    return path_time, walked
+
+
+def attribute_host(stitched, link, row_start, row_end, row_group, n_groups, percentile=0.0, start_min=None, start_max=None,
+                   need_flags=WHOLE, skip_flags=UNASSIGNED):
+    """What tw_attribute_traces computes, restated from the definitions: recursive and obvious, for the tests."""
+    link = np.asarray(link, dtype=np.int64)
+    start = [int(x) for x in row_start]
+    end = [max(int(e), s) for e, s in zip(row_end, start)]
+    group = [int(x) for x in row_group]
+    n = len(link)
+    children = [[] for _ in range(n)]
+    for c in range(n):
+        if link[c] >= 0:
+            children[int(link[c])].append(c)
+    self_time = np.zeros(n, dtype=np.int64)
+    for p in range(n):
+        clipped = sorted((max(start[c], start[p]), min(end[c], end[p])) for c in children[p])
+        covered, reach = 0, start[p]
+        for cs, ce in clipped:
+            if ce > cs:
+                covered += max(0, ce - max(cs, reach))
+                reach = max(reach, ce)
+        self_time[p] = end[p] - start[p] - covered
+    path_time, walked = critical_paths_host(children, start, end, stitched.tree_root)
     nt = stitched.n_trees
     top = np.full(nt, -1, dtype=np.int32)
     path_rows = np.zeros(nt, dtype=np.int32)
@@ -425,3 +438,151 @@ def write_confidence_npz(path, confidence, stitched):
         np.savez_compressed(
             f, threshold=np.float64(c.threshold), edges=c.edges, calib_columns=np.array(CALIB_COLUMNS),
             tree_root=stitched.tree_root, tree_flags=stitched.tree_flags, **{k: getattr(c, k) for k in TraceConfidence.FIELDS})
+
+
+METRICS = ("span_latency", "self_time", "path_time", "trace_latency")
+EMPTY = np.iinfo(np.int64).min       # quantile of an empty segment
+
+
+class LatencyDistributions(object):
+    """The populations behind an attribution, per segment = (cohort c, metric m of METRICS, group g), index c * (3 G + 1) + m * G
+    + g, the trace-latency segment (no group) last within a cohort: tree_cohort [n_trees] (the smallest label >= 0 among the
+    tree's rows, -1 none: such a tree is counted nowhere); seg_count / seg_sum [n_seg]; values [n_items], of which segment s
+    owns values[seg_off[s]:seg_off[s + 1]], ascending; quantile [n_seg, len(probs)] (the value at index min(n - 1, int(p * n)),
+    EMPTY for an empty segment); hist [n_seg, len(edges) + 1] (bin of v = the number of edges <= v); summary = items, non-empty
+    segments, selected trees counted, selected trees left out (include/traceweaver_amd.h has the definitions)."""
+
+    FIELDS = ("tree_cohort", "seg_count", "seg_sum", "seg_off", "values", "quantile", "hist", "summary")
+
+    def __init__(self, tree_cohort, seg_count, seg_sum, seg_off, values, quantile, hist, summary, n_cohorts, n_groups, probs=(), edges=()):
+        self.tree_cohort, self.seg_count, self.seg_sum, self.seg_off, self.values = tree_cohort, seg_count, seg_sum, seg_off, values
+        self.quantile, self.hist = quantile, hist
+        self.summary = np.asarray(summary, dtype=np.int64)
+        self.n_cohorts, self.n_groups = int(n_cohorts), int(n_groups)
+        self.probs = np.asarray(probs, dtype=np.float64)
+        self.edges = np.asarray(edges, dtype=np.int64)
+
+    n_items = property(lambda self: int(self.summary[0]))
+    n_seg = property(lambda self: self.n_cohorts * (3 * self.n_groups + 1))
+
+    def index(self, cohort, metric, group=None):
+        m = METRICS.index(metric) if isinstance(metric, str) else int(metric)
+        if not (0 <= cohort < self.n_cohorts and 0 <= m < 4 and (m == 3 or 0 <= group < self.n_groups)):
+            raise IndexError((cohort, metric, group))
+        return cohort * (3 * self.n_groups + 1) + m * self.n_groups + (0 if m == 3 else int(group))
+
+    def segment(self, cohort, metric, group=None):
+        """The sorted values of one segment, a view of `values`."""
+        s = self.index(cohort, metric, group)
+        return self.values[int(self.seg_off[s]):int(self.seg_off[s + 1])]
+
+    def cohort(self, c):
+        """Cohort c alone, in the layout of a result with one cohort (compare_distributions(d.cohort(0), d.cohort(1)))."""
+        per = 3 * self.n_groups + 1
+        a, b = c * per, (c + 1) * per
+        lo, hi = int(self.seg_off[a]), int(self.seg_off[b])
+        count = self.seg_count[a:b]
+        summary = [hi - lo, int((count > 0).sum()), int(count[-1]), int(self.summary[2] + self.summary[3] - count[-1])]
+        return LatencyDistributions(np.where(self.tree_cohort == c, 0, -1).astype(np.int32), count, self.seg_sum[a:b], self.seg_off[a:b + 1] - lo,
+                                    self.values[lo:hi], self.quantile[a:b], self.hist[a:b], summary, 1, self.n_groups, self.probs, self.edges)
+
+    def table(self, names=None):
+        """One dict per non-empty segment: cohort, metric, group (None for the trace latency), count, mean and the quantiles as
+        p<percent>."""
+        rows, per = [], 3 * self.n_groups + 1
+        for s in np.flatnonzero(self.seg_count > 0).tolist():
+            c, rest = divmod(s, per)
+            m, g = (3, None) if rest == 3 * self.n_groups else divmod(rest, self.n_groups)
+            rows.append(dict([("cohort", c), ("metric", METRICS[m]), ("group", g if names is None or g is None else names[g]),
+                              ("count", int(self.seg_count[s])), ("mean", float(self.seg_sum[s]) / int(self.seg_count[s]))] +
+                             [("p%g" % (100 * p), int(self.quantile[s][j])) for j, p in enumerate(self.probs.tolist())]))
+        return rows
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def distributions_host(stitched, attribution, row_start, row_end, row_group, n_groups, row_cohort=None, n_cohorts=1,
+                       probs=(0.5, 0.9, 0.95, 0.99), edges=None):
+    """What tw_latency_distributions computes, restated from the definitions in plain Python and numpy, for the tests.  The
+    attribution is the one the device call follows (its link, self_time, path_time and tree_selected are read)."""
+    start = np.asarray(row_start, dtype=np.int64)
+    end = np.maximum(np.asarray(row_end, dtype=np.int64), start)
+    group = np.asarray(row_group, dtype=np.int64)
+    n, nt, G = len(start), stitched.n_trees, int(n_groups)
+    children = [[] for _ in range(n)]
+    for c, p in enumerate(np.asarray(attribution.link).tolist()):
+        if p >= 0:
+            children[p].append(c)
+    _, walked = critical_paths_host(children, start.tolist(), end.tolist(), stitched.tree_root)
+    tree_cohort = np.zeros(nt, dtype=np.int32)
+    if row_cohort is not None:
+        label = np.asarray(row_cohort, dtype=np.int64)
+        for k in range(nt):
+            x = label[stitched.tree_rows[int(stitched.tree_off[k]):int(stitched.tree_off[k + 1])]]
+            tree_cohort[k] = x[x >= 0].min() if (x >= 0).any() else -1
+    else:
+        n_cohorts = 1
+    per = 3 * G + 1
+    items = [[] for _ in range(n_cohorts * per)]
+    counted = left = 0
+    for k in np.flatnonzero(np.asarray(attribution.tree_selected)).tolist():
+        c = int(tree_cohort[k])
+        if c < 0:
+            left += 1
+            continue
+        counted += 1
+        for r in stitched.tree_rows[int(stitched.tree_off[k]):int(stitched.tree_off[k + 1])].tolist():
+            g = int(group[r])
+            if g < 0:
+                continue
+            items[c * per + g].append(int(end[r] - start[r]))
+            items[c * per + G + g].append(int(attribution.self_time[r]))
+            if walked[r]:
+                items[c * per + 2 * G + g].append(int(attribution.path_time[r]))
+        items[c * per + 3 * G].append(int(stitched.tree_latency[k]))
+    probs = np.asarray(probs, dtype=np.float64).ravel()
+    edges = np.asarray(() if edges is None else edges, dtype=np.int64).ravel()
+    n_seg = len(items)
+    seg_count = np.array([len(x) for x in items], dtype=np.int64)
+    seg_sum = np.array([sum(x) for x in items], dtype=np.int64)
+    seg_off = np.concatenate([[0], np.cumsum(seg_count)]).astype(np.int64)
+    values = np.array([v for x in items for v in sorted(x)], dtype=np.int64)
+    quantile = np.full((n_seg, len(probs)), EMPTY, dtype=np.int64)
+    hist = np.zeros((n_seg, len(edges) + 1), dtype=np.int64)
+    for s, x in enumerate(items):
+        x = sorted(x)
+        for j, p in enumerate(probs.tolist()):
+            if x:
+                quantile[s, j] = x[min(len(x) - 1, int(p * float(len(x))))]
+        for v in x:
+            hist[s, sum(1 for edge in edges.tolist() if v >= edge)] += 1
+    summary = [len(values), int((seg_count > 0).sum()), counted, left]
+    return LatencyDistributions(tree_cohort, seg_count, seg_sum, seg_off, values, quantile, hist, summary, n_cohorts, G, probs, edges)
+
+
+def compare_distributions(a, b):
+    """Two results with the same segment layout side by side, per segment: quantile_diff [n_seg, n_q] = b's quantile less a's (0
+    where either segment is empty), both [n_seg] = neither is empty, and cdf_gap [n_seg] = the largest |F_a(x) - F_b(x)| over the
+    union of both value sets, F(x) = the share of values <= x (nan where either is empty).  On the host, in numpy."""
+    if (a.n_cohorts, a.n_groups) != (b.n_cohorts, b.n_groups) or not np.array_equal(a.probs, b.probs):
+        raise ValueError("the two results differ in their segments or probs")
+    both = (np.asarray(a.seg_count) > 0) & (np.asarray(b.seg_count) > 0)
+    diff = np.where(both[:, None], np.asarray(b.quantile) - np.where(both[:, None], a.quantile, 0), 0).astype(np.int64)
+    gap = np.full(a.n_seg, np.nan, dtype=np.float64)
+    for s in np.flatnonzero(both).tolist():
+        x = a.values[int(a.seg_off[s]):int(a.seg_off[s + 1])]
+        y = b.values[int(b.seg_off[s]):int(b.seg_off[s + 1])]
+        at = np.union1d(x, y)
+        gap[s] = np.abs(np.searchsorted(x, at, side="right") / float(len(x)) - np.searchsorted(y, at, side="right") / float(len(y))).max()
+    return {"quantile_diff": diff, "both": both, "cdf_gap": gap}
+
+
+def write_distributions_npz(path, distributions, names):
+    """The distributions as one .npz next to the one write_attribution_npz stores: the arrays of LatencyDistributions, the
+    layout (n_cohorts, n_groups, metrics, group names) and the query (probs, edges)."""
+    d = distributions
+    with open(path, "wb") as f:
+        np.savez_compressed(
+            f, n_cohorts=np.int64(d.n_cohorts), n_groups=np.int64(d.n_groups), metrics=np.array(METRICS), group_names=np.array([str(x) for x in names]),
+            probs=d.probs, edges=d.edges, **{k: getattr(d, k) for k in LatencyDistributions.FIELDS})

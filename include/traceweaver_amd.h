@@ -539,6 +539,76 @@ typedef struct {
 int tw_set_row_cohorts(tw_engine *e, int32_t n_cohorts, const int32_t *row_cohort);
 int tw_latency_distributions(tw_engine *e, const tw_dist_query *q, const tw_distributions *out, int64_t *summary4);
 
+/* ---- traces grouped by call-graph signature (csrc/tw_sig.h) -------------------------------------------------------
+ *
+ * Replaces: AssignCGSignature and FindUniqueCGs (alibaba-analysis/analysis.py:99-126, 214-221) -- per trace and depth the
+ * sorted list of the services seen there, and the traces grouped by it; PreparePerCGData (:233-292) then works on one group
+ * at a time.  The four sections above treat a trace as a bag of rows with times; this one says what it looks like: which
+ * call graphs occur, how often, how slow each is, and whether a reconstructed trace has the call graph its request had.
+ * It works on the forest of the last tw_stitch_traces (of a pass, of pass 0 or of the truth) and on row_group / n_groups of
+ * tw_set_row_groups.  Everything is integer.
+ *
+ * Definitions:
+ *   level[r]    for a server row (row_kind 1) the number of server rows strictly above it on the way to its tree's root; -1
+ *               for every other row.  Server rows link to client rows and client rows to the request's server row, so this
+ *               equals depth[r] >> 1.  A fragment rooted at a client row has its server child at level 0.
+ *   items       of a tree: its server rows with row_group[r] = g >= 0.  Rows of group -1 are no items, but they count as
+ *               ancestors (they are levels, and the cg of their children is -1).
+ *   item key    mode 0 ("levels", the reference's signature): (level, 0, g).  Mode 1 ("edges"): (level, cg, g), cg = the
+ *               row_group of the nearest server ancestor, -1 if there is none or its group is -1: per level the multiset of
+ *               caller -> callee edges, which separates traces that mode 0 merges.
+ *   signature   of a tree: its items sorted by key and run-length encoded, a sequence of entries (level, cg, g, count);
+ *               fully determined; empty for a tree without items.  Two signatures are equal iff the sequences are equal
+ *               entry by entry.  The device decides this exactly: a 64-bit hash of the sequence orders and buckets the
+ *               trees, equality is then decided by comparing the entries, never by the hash.
+ *   eligible    flags hold every bit of need_flags and none of skip_flags (TW_TREE_CONFIDENT as in the attribution).
+ *   classes     rep[t] = the smallest eligible tree index with a signature equal to t's; classes are numbered in ascending
+ *               order of their rep: the numbering depends on nothing but the forest and the groups.  tree_class[t] = the
+ *               class, -1 for a tree that is not eligible.  tree_items[t] = the number of items, of every tree.
+ *   per class   class_rep, class_trees, class_latency_sum / _min / _max over tree_latency, and the signature itself:
+ *               class c owns the entries class_off[c] .. class_off[c + 1) of class_entries, four int32 each (level, cg, g,
+ *               count).
+ *   reference   keep_reference != 0 stores the signatures of this call's eligible trees on the device, keyed by the root
+ *               row of their tree.  The set survives a new tw_stitch_traces; it is dropped with the row maps (tw_load_batch,
+ *               tw_scale_load, tw_set_span_rows) and with new row groups.
+ *   comparison  compare != 0 writes tree_same[t]: 1 if the reference set holds a tree with the same root row and an equal
+ *               signature, 0 if it holds one with a different signature, 255 if it holds none or t is not eligible (255
+ *               everywhere without compare).  A call with both compares with the set it then replaces.
+ *   summary6    eligible trees, classes, items of the eligible trees, entries of all class signatures, compared trees
+ *               (tree_same < 255), same trees; the last two are -1 without compare.
+ * Against the reference: it also puts the root's `caller` into level 0 (the caller of a root is not in the span table),
+ * joins the names into one string before hashing (which can merge distinct multisets) and uses Python's hash, salted per
+ * process (analysis.py:111-125).  The classes here are those of the multisets: the reference's apart from these three points.
+ *
+ * Outputs are caller-allocated, any may be NULL: row_level [n_rows]; tree_class, tree_items, tree_same [n_trees of the
+ * stitch]; class_rep, class_trees, class_latency_* with room for n_trees, class_off for n_trees + 1; class_entries [4 *
+ * summary6[3]]: a call with class_entries == NULL returns the sizes, the result stays on the device until the forest, the
+ * groups, the flags (tw_score_traces) or the query change, and a second call with the same query only copies.
+ * TW_ERR_STATE: before a stitch, before tw_set_row_groups, after anything that drops the forest (see tw_attribute_traces);
+ * compare without a reference set.  TW_ERR_ARG: mode outside {0, 1}; compare in another mode than the reference set's.
+ * TW_ERR_UNSUPPORTED: n_groups > 2^20 or a server row at level >= 2^16: the packed sort key holds 16 bits of level, 21 of
+ * cg + 1 and 20 of g.  TW_SIG_HASH_BITS (default 64, read by tw_create) keeps only that many low bits of the hash: with 2,
+ * unrelated signatures share a bucket and the exact comparison alone separates them -- the results are the same.
+ * Results do not depend on scheduling: no floating point; the atomics are integer adds, minima and maxima of which only the
+ * result is read.  Covers one engine's batch.  Timing: tw_get_timing slots 25..27 (items and levels; sort, run lengths and
+ * hash; classes, comparison and per-class reduction; HIP events, ms; those of the last call that did not just copy). */
+typedef struct {
+    int32_t mode;
+    uint32_t need_flags, skip_flags;
+    int32_t keep_reference, compare;
+} tw_sig_query;
+typedef struct {
+    int32_t *row_level;
+    int32_t *tree_class;
+    int64_t *tree_items;
+    uint8_t *tree_same;
+    int32_t *class_rep;
+    int64_t *class_trees, *class_latency_sum, *class_latency_min, *class_latency_max;
+    int64_t *class_off;
+    int32_t *class_entries;
+} tw_signatures;
+int tw_trace_signatures(tw_engine *e, const tw_sig_query *q, const tw_signatures *out, int64_t *summary6);
+
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,
  * 1 + e = span of outgoing endpoint e), large_delay = the longest incoming span.  Per span: key_out = a * (E + 1) + b

@@ -26,6 +26,7 @@
 #include "tw_attr.h"
 #include "tw_conf.h"
 #include "tw_dist.h"
+#include "tw_sig.h"
 
 using namespace tw;
 
@@ -215,6 +216,16 @@ struct tw_engine {
     DistKeyDev dist_key{};
     hipEvent_t ds_ev[5] = {};
     double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
+    // tw_trace_signatures (tw_sig.h): works on the forest of the last tw_stitch_traces and the row groups; sig_ready: the result of
+    // sig_q on that forest is resident, a further call with the same query only copies; the reference set (ref_set) is keyed by
+    // root row: it survives a new stitch and is dropped with the row maps and with new row groups
+    SigDev G{};
+    bool sig_ready = false, ref_set = false;
+    tw_sig_query sig_q{};
+    int32_t ref_mode = 0, sig_hash_bits = 64;
+    int64_t sig_rows_cap = 0, sig_trees_cap = 0, sig_ent_cap = 0, sig_ref_cap = 0, sig_summary[6] = {0, 0, 0, 0, 0, 0};
+    hipEvent_t sg_ev[4] = {};
+    double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
 };
 
 namespace {
@@ -280,6 +291,8 @@ void free_all(tw_engine* e) {
     e->C = ConfDev{}; e->conf_rows_cap = 0;
     e->D = DistDev{}; e->attributed = false; e->cohorts_set = false; e->dist_ready = false;
     e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;
+    e->G = SigDev{}; e->sig_ready = false; e->ref_set = false;
+    e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;
     e->state = ST_EMPTY;
 }
 
@@ -959,7 +972,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     e->state = ST_LOADED; e->pass1_done = false;
     e->parents_given = false;
     e->rows_set = false;   // every list was re-sorted: in_row / out_row no longer name the spans at these positions
-    e->groups_set = false; e->stitched = false; e->cohorts_set = false;
+    e->groups_set = false; e->stitched = false; e->cohorts_set = false; e->ref_set = false;
     for (int E = 0; E <= kMaxEp; E++) { e->wide_pass1[E] = -1; e->hard_pass1[E] = -1; e->split_pass1[E] = -1; }
     return TW_OK;
 }
@@ -1010,6 +1023,7 @@ int tw_create(int device_id, tw_engine** out) {
         for (int j = 0; j < 3 && s == hipSuccess; j++) s = hipEventCreateWithFlags(&e->post_join[i][j], hipEventDisableTiming);
     }
     e->pipeline = env_int("TW_CLASS_PIPELINE", 1);
+    e->sig_hash_bits = std::min(std::max(env_int("TW_SIG_HASH_BITS", 64), 1), 64);
     e->tile_gate = env_int("TW_TILE_GATE", 0);
     e->enum_stretches = std::min(std::max(env_int("TW_ENUM_STRETCHES", 1), 1), kEnumStretches);
     e->heavy_grid = std::max(env_int("TW_HEAVY_GRID", 4096), 64);
@@ -1797,6 +1811,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 3 && 16 + i < n; i++) ms[16 + i] = e->at_ms[i];   // the last tw_attribute_traces
     for (int i = 0; i < 3 && 19 + i < n; i++) ms[19 + i] = e->cf_ms[i];   // the last tw_score_traces
     for (int i = 0; i < 3 && 22 + i < n; i++) ms[22 + i] = e->ds_ms[i];   // the last tw_latency_distributions
+    for (int i = 0; i < 3 && 25 + i < n; i++) ms[25 + i] = e->sg_ms[i];   // the last tw_trace_signatures that ran kernels
     return TW_OK;
 }
 
@@ -1995,6 +2010,7 @@ int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const 
     for (int i = 0; i < 6; i++)
         if (e->st_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->st_ev[i]));
     e->rows_set = true;
+    e->ref_set = false;
     e->groups_set = false; e->stitched = false; e->cohorts_set = false;   // (new row maps: the groups and the cohort labels name rows of the old ones)
     return TW_OK;
 }
@@ -2071,7 +2087,7 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
         if (!ok) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
     }
     HIPCHK(hipSetDevice(e->device));
-    e->stitched = false; e->attributed = false; e->dist_ready = false;
+    e->stitched = false; e->attributed = false; e->dist_ready = false; e->sig_ready = false;
     const StitchDev& S = e->S;
     const bool has_truth = e->truth != nullptr;
     const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
@@ -2144,6 +2160,7 @@ int tw_set_row_groups(tw_engine* e, int32_t n_groups, const int32_t* row_group) 
         if (row_group[r] < -1 || row_group[r] >= n_groups) return fail(e, TW_ERR_ARG, "tw_set_row_groups: row_group outside [-1, n_groups)");
     HIPCHK(hipSetDevice(e->device));
     e->attributed = false; e->dist_ready = false;   // (the per-row flags of the last attribution name the old groups)
+    e->sig_ready = false; e->ref_set = false;       // (... and the signatures, the reference set's among them)
     AttrDev& A = e->A;
     int rc;
 #define AALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
@@ -2344,6 +2361,7 @@ int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* o
     }
     rc = conf_decisions(e);
     if (rc != TW_OK) return rc;
+    e->sig_ready = false;   // (the CONFIDENT bit of the flags is rewritten: the eligible trees of a resident signature result may change)
     const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
     const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), reqs((unsigned)((P.n_in_total + threads - 1) / threads));
     HIPCHK(hipMemsetAsync(C.row_request, 0xff, sizeof(int32_t) * (size_t)S.n_rows, e->stream));
@@ -2586,6 +2604,145 @@ int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_dist
     HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[3], e->ds_ev[4])); e->ds_ms[2] = ms;
     if (summary != nullptr) {
         summary[0] = n_items; summary[1] = (int64_t)counters[5]; summary[2] = (int64_t)counters[3]; summary[3] = (int64_t)counters[4];
+    }
+    return TW_OK;
+}
+
+/* ---- traces grouped by call-graph signature (tw_sig.h) --------------------------------------------------------------- */
+int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
+        return fail(e, TW_ERR_STATE, "tw_trace_signatures needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    if (!e->groups_set) return fail(e, TW_ERR_STATE, "tw_trace_signatures before tw_set_row_groups (dropped with the row maps)");
+    if (q->mode != 0 && q->mode != 1) return fail(e, TW_ERR_ARG, "tw_trace_signatures: mode outside {0 levels, 1 edges}");
+    if ((int64_t)e->A.n_groups > ((int64_t)1 << kSigGroupBits)) return fail(e, TW_ERR_UNSUPPORTED, "tw_trace_signatures: more than 2^20 groups (the packed key holds 20 bits of group)");
+    if (q->compare != 0 && !e->ref_set)
+        return fail(e, TW_ERR_STATE, "tw_trace_signatures: compare without a reference set (keep_reference first; new row maps and new row groups drop the set)");
+    if (q->compare != 0 && e->ref_mode != q->mode) return fail(e, TW_ERR_ARG, "tw_trace_signatures: the reference set was kept in the other mode");
+    HIPCHK(hipSetDevice(e->device));
+    const StitchDev& S = e->S;
+    SigDev& D = e->G;
+    const int64_t nt = e->st_trees, n_rows = S.n_rows;
+    const bool same_query = e->sig_ready && e->sig_q.mode == q->mode && e->sig_q.need_flags == q->need_flags && e->sig_q.skip_flags == q->skip_flags &&
+                            (e->sig_q.keep_reference != 0) == (q->keep_reference != 0) && (e->sig_q.compare != 0) == (q->compare != 0);
+    int rc;
+    if (!same_query) {
+        e->sig_ready = false;
+        for (int i = 0; i < 4; i++)
+            if (e->sg_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->sg_ev[i]));
+#define GALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
+        if (D.counters == nullptr) GALLOC(D.counters, kSigCounters);   // (all of them freed with the batch)
+        if (D.key_a == nullptr || n_rows > e->sig_rows_cap) {
+            GALLOC(D.row_level, n_rows); GALLOC(D.key_a, n_rows); GALLOC(D.key_b, n_rows); GALLOC(D.ent_cnt, n_rows);
+            GALLOC(D.big_begin, n_rows / kSigCap + 1); GALLOC(D.big_end, n_rows / kSigCap + 1);
+            e->sig_rows_cap = n_rows;
+        }
+        if (D.hkey_a == nullptr || nt > e->sig_trees_cap) {
+            GALLOC(D.hkey_a, nt); GALLOC(D.hkey_b, nt); GALLOC(D.val_a, nt); GALLOC(D.val_b, nt); GALLOC(D.tree_ent, nt); GALLOC(D.rep, nt);
+            GALLOC(D.tree_class, nt); GALLOC(D.tree_items, nt); GALLOC(D.elig, nt); GALLOC(D.tree_same, nt); GALLOC(D.chunk_sum, nt / kSigScanItems + 2);
+            GALLOC(D.class_rep, nt); GALLOC(D.class_trees, nt); GALLOC(D.class_sum, nt); GALLOC(D.class_min, nt); GALLOC(D.class_max, nt);
+            GALLOC(D.class_off, nt + 1);
+            e->sig_trees_cap = nt;
+        }
+        if (q->keep_reference != 0 && (D.ref_key == nullptr || n_rows > e->sig_ref_cap)) {
+            GALLOC(D.ref_key, n_rows); GALLOC(D.ref_cnt, n_rows); GALLOC(D.ref_n, n_rows); GALLOC(D.ref_pos, n_rows);
+            e->sig_ref_cap = n_rows;
+            e->ref_set = false;
+        }
+        D.mode = q->mode; D.hash_bits = e->sig_hash_bits; D.need_flags = q->need_flags; D.skip_flags = q->skip_flags;
+        D.row_group = e->A.row_group;
+        const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+        const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), rows((unsigned)((n_rows + threads - 1) / threads));
+        unsigned long long counters[kSigCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
+        HIPCHK(hipMemsetAsync(D.counters, 0, sizeof(counters), e->stream));
+        HIPCHK(hipEventRecord(e->sg_ev[0], e->stream));
+        hipLaunchKernelGGL(k_sig_items, rows, tb, 0, e->stream, S, D);
+        hipLaunchKernelGGL(k_sig_trees, trees, tb, 0, e->stream, S, D, nt);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->sg_ev[1], e->stream));
+        HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (counters[3] != 0) return fail(e, TW_ERR_UNSUPPORTED, "tw_trace_signatures: a server row lies 2^16 or more levels deep (the packed key holds 16 bits of level)");
+        const int64_t n_big = (int64_t)counters[2];
+        if (n_big > 0) {   // the trees beyond a wavefront's LDS table: sorted before k_sig_sign reads them
+            size_t bytes = 0;
+            HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, bytes, (const unsigned long long*)D.key_a, D.key_b, (unsigned)n_rows, (unsigned)n_big, D.big_begin,
+                                                      D.big_end, 0u, 64u, e->stream));
+            rc = ensure_sort_tmp(e, bytes);
+            if (rc != TW_OK) return rc;
+            bytes = e->sort_tmp_bytes;
+            HIPCHK(rocprim::segmented_radix_sort_keys(e->sort_tmp, bytes, (const unsigned long long*)D.key_a, D.key_b, (unsigned)n_rows, (unsigned)n_big, D.big_begin,
+                                                      D.big_end, 0u, 64u, e->stream));
+        }
+        {   // one wavefront per kSigTrees trees, persistent: at most 8192 workgroups of four
+            const unsigned gthreads = e->coop >= 64 ? 64u * kSigWaves : (unsigned)e->coop;
+            const int64_t want = (nt / kSigTrees + 1 + kSigWaves - 1) / kSigWaves;
+            hipLaunchKernelGGL(k_sig_sign, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, D, nt);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->sg_ev[2], e->stream));
+        size_t bytes = 0;
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream));
+        rc = ensure_sort_tmp(e, bytes);
+        if (rc != TW_OK) return rc;
+        bytes = e->sort_tmp_bytes;
+        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream));
+        hipLaunchKernelGGL(k_sig_rep, trees, tb, 0, e->stream, S, D, nt);
+        const int64_t n_chunks = (nt + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
+        hipLaunchKernelGGL(k_sig_scan_sums, dim3((unsigned)n_chunks), tb, 0, e->stream, D, nt);
+        hipLaunchKernelGGL(k_sig_scan_chunks, dim3(1), tb, 0, e->stream, D, n_chunks);
+        hipLaunchKernelGGL(k_sig_scan_write, dim3((unsigned)n_chunks), tb, 0, e->stream, D, nt);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        const int64_t n_classes = (int64_t)(counters[6] >> 32), n_entries = (int64_t)(counters[6] & 0xffffffffull);
+        if (D.class_entries == nullptr || n_entries > e->sig_ent_cap) {
+            GALLOC(D.class_entries, 4 * n_entries);
+            e->sig_ent_cap = std::max<int64_t>(n_entries, 1);
+        }
+#undef GALLOC
+        hipLaunchKernelGGL(k_sig_classes, trees, tb, 0, e->stream, S, D, nt);
+        if (q->compare != 0) hipLaunchKernelGGL(k_sig_compare, trees, tb, 0, e->stream, S, D, nt);
+        else HIPCHK(hipMemsetAsync(D.tree_same, 0xff, (size_t)nt, e->stream));
+        if (q->keep_reference != 0) {   // (after the comparison: a call with both compares with the set it replaces)
+            e->ref_set = false;
+            HIPCHK(hipMemsetAsync(D.ref_n, 0xff, sizeof(int32_t) * (size_t)n_rows, e->stream));
+            HIPCHK(hipMemcpyAsync(D.ref_key, D.key_a, sizeof(unsigned long long) * (size_t)n_rows, hipMemcpyDeviceToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(D.ref_cnt, D.ent_cnt, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, e->stream));
+            hipLaunchKernelGGL(k_sig_keep, trees, tb, 0, e->stream, S, D, nt);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->sg_ev[3], e->stream));
+        HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[0], e->sg_ev[1])); e->sg_ms[0] = ms;
+        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[1], e->sg_ev[2])); e->sg_ms[1] = ms;
+        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[2], e->sg_ev[3])); e->sg_ms[2] = ms;
+        e->sig_summary[0] = (int64_t)counters[0]; e->sig_summary[1] = n_classes; e->sig_summary[2] = (int64_t)counters[1]; e->sig_summary[3] = n_entries;
+        e->sig_summary[4] = q->compare != 0 ? (int64_t)counters[4] : -1; e->sig_summary[5] = q->compare != 0 ? (int64_t)counters[5] : -1;
+        if (q->keep_reference != 0) { e->ref_set = true; e->ref_mode = q->mode; }
+        e->sig_q = *q;
+        e->sig_ready = true;
+    }
+    if (summary != nullptr)
+        for (int k = 0; k < 6; k++) summary[k] = e->sig_summary[k];
+    if (out != nullptr) {
+        const size_t nc = (size_t)e->sig_summary[1], ne = (size_t)e->sig_summary[3];
+#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
+        D2H(out->row_level, D.row_level, sizeof(int32_t) * (size_t)n_rows);
+        D2H(out->tree_class, D.tree_class, sizeof(int32_t) * (size_t)nt);
+        D2H(out->tree_items, D.tree_items, sizeof(int64_t) * (size_t)nt);
+        D2H(out->tree_same, D.tree_same, (size_t)nt);
+        D2H(out->class_rep, D.class_rep, sizeof(int32_t) * nc);
+        D2H(out->class_trees, D.class_trees, sizeof(int64_t) * nc);
+        D2H(out->class_latency_sum, D.class_sum, sizeof(int64_t) * nc);
+        D2H(out->class_latency_min, D.class_min, sizeof(int64_t) * nc);
+        D2H(out->class_latency_max, D.class_max, sizeof(int64_t) * nc);
+        D2H(out->class_off, D.class_off, sizeof(int64_t) * (nc + 1));
+        if (ne > 0) D2H(out->class_entries, D.class_entries, sizeof(int32_t) * 4 * ne);
+#undef D2H
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
     return TW_OK;
 }

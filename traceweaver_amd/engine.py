@@ -434,6 +434,7 @@ class Engine(object):
         self._check(self._lib.tw_stitch_traces(self._h, which, 1 if truth else 0, ctypes.byref(out), ctypes.byref(nt), _vp(counts)))
         k = int(nt.value)
         self._n_trees = k
+        self._tree_root = tree_root[:k].copy()
         return StitchedTraces(root, depth, tree_off[:k + 1].copy(), tree_rows, tree_root[:k].copy(), tree_latency[:k].copy(),
                               tree_flags[:k].copy(), counts)
 
@@ -568,6 +569,40 @@ class Engine(object):
         ms = np.zeros(25, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 25))
         return dict(zip(("items", "sort", "quantiles"), ms[22:25].tolist()))
+
+    def signatures(self, mode="levels", need_flags=1, skip_flags=0, keep_reference=False, compare=False):
+        """The trees of the last stitch() grouped by call-graph signature (tw_trace_signatures): per eligible tree (flags hold
+        need_flags, none of skip_flags; default: whole traces, those with an unassigned call included) the run-length encoded,
+        sorted list of its (level, caller group, group) items -- mode "levels": the caller group left out, the reference's
+        signature; "edges": with it --, the classes of equal signatures numbered by their first tree, and per class its trees,
+        latency sum / min / max and entries.  keep_reference stores the signatures on the device, keyed by root row;
+        compare=True sets tree_same against that set.  Needs set_row_groups.  Returns traces.TraceSignatures."""
+        from .traces import SIGNATURE_MODES, TraceSignatures
+
+        m = SIGNATURE_MODES.index(mode) if isinstance(mode, str) else int(mode)
+        n, nt = int(getattr(self, "_n_rows", 0)), max(int(getattr(self, "_n_trees", 0)), 1)
+        q = _ffi.SigQuery(m, int(need_flags), int(skip_flags), 1 if keep_reference else 0, 1 if compare else 0)
+        level, tree_class, rep = (np.empty(k, dtype=np.int32) for k in (max(n, 1), nt, nt))
+        items, trees, lsum, lmin, lmax = (np.empty(nt, dtype=np.int64) for _ in range(5))
+        same = np.empty(nt, dtype=np.uint8)
+        off = np.empty(nt + 1, dtype=np.int64)
+        summary = np.zeros(6, dtype=np.int64)
+        out = _ffi.Signatures(*[_vp(a) for a in (level, tree_class, items, same, rep, trees, lsum, lmin, lmax, off)] + [None])
+        self._check(self._lib.tw_trace_signatures(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        entries = np.empty((int(summary[3]), 4), dtype=np.int32)   # the result is resident: the second call only copies the entries
+        if len(entries):
+            only = _ffi.Signatures(*([None] * 10 + [_vp(entries)]))
+            self._check(self._lib.tw_trace_signatures(self._h, ctypes.byref(q), ctypes.byref(only), None))
+        k, c = int(self._n_trees), int(summary[1])
+        return TraceSignatures(level[:n].copy(), tree_class[:k].copy(), items[:k].copy(), same[:k].copy(), rep[:c].copy(), trees[:c].copy(),
+                               lsum[:c].copy(), lmin[:c].copy(), lmax[:c].copy(), off[:c + 1].copy(), entries, summary, m, self._tree_root)
+
+    def signatures_timing(self):
+        """The last signatures() that ran kernels on the device (HIP events, ms): items and levels; sort, run lengths and hash;
+        classes, comparison and per-class reduction."""
+        ms = np.zeros(28, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 28))
+        return dict(zip(("items", "sort", "classes"), ms[25:28].tolist()))
 
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):

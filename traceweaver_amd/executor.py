@@ -109,6 +109,13 @@ def parse_args(argv=None):
     ap.add_argument("--cohort_service", type=q, default=None,
                     help="--latency_out: split the traces into cohorts by the operation of this service's span in them (the smallest "
                          "operation index where a trace holds several); traces without a span of the service are left out")
+    ap.add_argument("--signatures_out", type=q, default=None,
+                    help="group the traces by call-graph signature on the device (per level the services seen there, the reference's "
+                         "AssignCGSignature / FindUniqueCGs): the signatures of the true traces are kept as the reference set, those of "
+                         "the predicted traces compared with them; write both and the shape accuracy (the share of whole traces with "
+                         "the true call graph) to this .npz and print the most frequent call graphs.  Needs --stitch_out's conditions")
+    ap.add_argument("--signature_mode", type=q, default="levels", choices=("levels", "edges"),
+                    help="--signatures_out: levels = the services per level; edges = the caller -> callee edges per level")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
                          "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
@@ -166,6 +173,8 @@ def unsupported(args):
         problems.append("--quantiles %s (up to 32 comma-separated numbers in [0, 1])" % args.quantiles)
     if args.cohort_service and not args.latency_out:
         problems.append("--cohort_service without --latency_out")
+    if args.signatures_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--signatures_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--confidence_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.confidence_out and args.fit != "device-batch":
@@ -243,6 +252,8 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         st = eng.stitch(0)
     if args.attribute_out or args.latency_out:
         attribute_out(args, eng, st, corpus, table)
+    if args.signatures_out:
+        signatures_out(args, eng, corpus, table, 2 if solved is not None else 0)
     eng.close()
     if not args.stitch_out:
         return
@@ -257,6 +268,30 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         raise RuntimeError("stitched traces: %d exact, the accuracy reduction counts %d traces right" % (c[3], right))
     elif c[3] > right:   # bit 2 compares row sets: two requests of one service in one trace that swap their calls keep the set
         print("(%d traces hold the true spans under another assignment of calls to requests: right as a set, wrong per request)" % (c[3] - right))
+
+
+def signatures_out(args, eng, corpus, table, pass_, has_truth=True):
+    """--signatures_out: the true forest's signatures kept as the reference set, the predicted forest's compared with them; groups
+    by service.  Without ground truth the predicted side alone."""
+    from . import traces
+
+    group, names = traces.groups_from_table(table, corpus)
+    eng.set_row_groups(group, len(names))
+    true = None
+    if has_truth:
+        eng.stitch(truth=True)
+        true = eng.signatures(args.signature_mode, keep_reference=True)
+    eng.stitch(pass_)
+    pred = eng.signatures(args.signature_mode, compare=has_truth)
+    traces.write_signatures_npz(args.signatures_out, names, pred, true)
+    print("Call graphs (%s): %d among %d whole traces%s" % (args.signature_mode, pred.n_classes, pred.n_eligible,
+                                                           "; true traces: %d among %d" % (true.n_classes, true.n_eligible) if true is not None else ""))
+    if true is not None:
+        print("Shape accuracy: %d of %d whole traces have the call graph of the true trace" % (pred.summary[5], pred.summary[4]))
+    for row in pred.table(names)[:3 if not args.verbose else None]:
+        print("  %6d traces, mean %.1f us (min %d, max %d): %s" % (
+            row["trees"], row["mean_latency"], row["min_latency"], row["max_latency"],
+            " | ".join("L%d %s%s x%d" % (lv, "%s>" % cg if cg is not None else "", g, k) for lv, cg, g, k in row["signature"]) or "(no service)"))
 
 
 def culprit_line(a, names, head="Delay culprit"):
@@ -500,7 +535,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out:
+            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
                            solved=solved)
         else:

@@ -18,6 +18,10 @@ Engine.set_row_cohorts / Engine.distributions (tw_set_row_cohorts, tw_latency_di
 behind an attribution: `LatencyDistributions` is the result, `distributions_host` restates the definitions in numpy for the
 tests, `compare_distributions` sets two results side by side (predicted against true, cohort against cohort) on the host,
 `write_distributions_npz` stores a result.
+
+Engine.signatures (tw_trace_signatures, csrc/tw_sig.h) groups the stitched traces by call-graph signature: `TraceSignatures` is the
+result, `signatures_host` restates the definitions with dictionaries of tuples for the tests, `compare_signatures` cross-checks
+tree_same on the host and gives the share of traces with the true signature, `write_signatures_npz` stores results.
 """
 import sys
 
@@ -586,3 +590,155 @@ def write_distributions_npz(path, distributions, names):
         np.savez_compressed(
             f, n_cohorts=np.int64(d.n_cohorts), n_groups=np.int64(d.n_groups), metrics=np.array(METRICS), group_names=np.array([str(x) for x in names]),
             probs=d.probs, edges=d.edges, **{k: getattr(d, k) for k in LatencyDistributions.FIELDS})
+
+
+SIGNATURE_MODES = ("levels", "edges")
+NOT_COMPARED = 255                   # tree_same of a tree that is not eligible or whose root row the reference set does not hold
+
+
+class TraceSignatures(object):
+    """The trees of a stitch grouped by call-graph signature (include/traceweaver_amd.h has the definitions): row_level [n_rows]
+    (server rows: the server rows above them, -1 otherwise); tree_class (-1 not eligible), tree_items, tree_same (1 / 0 against
+    the reference set, NOT_COMPARED otherwise) [n_trees]; per class, numbered by their first tree, class_rep, class_trees,
+    class_latency_sum / _min / _max; class c owns class_entries[class_off[c]:class_off[c + 1]], rows (level, caller group, group,
+    count) -- the caller group is 0 in mode "levels"; summary = eligible trees, classes, items, entries, compared trees, same
+    trees (the last two -1 without a comparison).  tree_root (not compared by same_as) names the trees' root rows."""
+
+    FIELDS = ("row_level", "tree_class", "tree_items", "tree_same", "class_rep", "class_trees", "class_latency_sum", "class_latency_min",
+              "class_latency_max", "class_off", "class_entries", "summary")
+
+    def __init__(self, row_level, tree_class, tree_items, tree_same, class_rep, class_trees, class_latency_sum, class_latency_min,
+                 class_latency_max, class_off, class_entries, summary, mode=0, tree_root=None):
+        self.row_level, self.tree_class, self.tree_items, self.tree_same = row_level, tree_class, tree_items, tree_same
+        self.class_rep, self.class_trees, self.class_latency_sum = class_rep, class_trees, class_latency_sum
+        self.class_latency_min, self.class_latency_max, self.class_off = class_latency_min, class_latency_max, class_off
+        self.class_entries = np.asarray(class_entries, dtype=np.int32).reshape(-1, 4)
+        self.summary = np.asarray(summary, dtype=np.int64)
+        self.mode = int(mode)
+        self.tree_root = None if tree_root is None else np.asarray(tree_root, dtype=np.int32)
+
+    n_classes = property(lambda self: len(self.class_rep))
+    n_eligible = property(lambda self: int(self.summary[0]))
+
+    def entries(self, c):
+        """The signature of class c: an [n, 4] view of class_entries."""
+        c = int(c)
+        if not 0 <= c < self.n_classes:
+            raise IndexError(c)
+        return self.class_entries[int(self.class_off[c]):int(self.class_off[c + 1])]
+
+    def signature(self, c):
+        """... as a tuple of (level, caller group, group, count) tuples."""
+        return tuple(tuple(int(x) for x in row) for row in self.entries(c))
+
+    def by_root(self):
+        """{root row: signature} of the eligible trees: what keep_reference stores, the `reference` of signatures_host."""
+        sigs = [self.signature(c) for c in range(self.n_classes)]
+        return {int(r): sigs[int(c)] for r, c in zip(self.tree_root.tolist(), self.tree_class.tolist()) if c >= 0}
+
+    def table(self, names=None):
+        """One dict per class, sorted by class_trees descending (ties: the class number): class, rep, trees, share of the eligible
+        trees, mean / min / max latency, and the signature as a list of (level, caller, group, count) with the groups' names."""
+        name = lambda g: g if names is None or g < 0 else names[g]
+        rows = []
+        for c in sorted(range(self.n_classes), key=lambda c: (-int(self.class_trees[c]), c)):
+            n = int(self.class_trees[c])
+            sig = [(lv, name(cg) if self.mode == 1 else None, name(g), k) for lv, cg, g, k in self.signature(c)]
+            rows.append({"class": c, "rep": int(self.class_rep[c]), "trees": n, "share": float(n) / max(self.n_eligible, 1),
+                         "mean_latency": float(self.class_latency_sum[c]) / n, "min_latency": int(self.class_latency_min[c]),
+                         "max_latency": int(self.class_latency_max[c]), "signature": sig})
+        return rows
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def signatures_host(stitched, link, row_kind, row_group, n_groups, mode=0, need_flags=WHOLE, skip_flags=0, reference=None):
+    """What tw_trace_signatures computes, restated from the definitions in plain Python: ancestors walked one by one, signatures
+    as tuples in a dictionary, no hash of our own.  link: the stitched links (Attribution.link, or test code's own); reference:
+    {root row: signature} (TraceSignatures.by_root of the call that kept the reference set) for tree_same."""
+    mode = SIGNATURE_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    link = [int(x) for x in link]
+    kind = [int(x) for x in row_kind]
+    group = [int(x) for x in row_group]
+    n, nt = len(link), stitched.n_trees
+    assert all(-1 <= g < n_groups for g in group)
+    level = np.full(n, -1, dtype=np.int32)
+    caller = [-1] * n
+    for r in range(n):
+        if kind[r] != 1:
+            continue
+        above, p = [], link[r]
+        while p >= 0:
+            if kind[p] == 1:
+                above.append(p)
+            p = link[p]
+        level[r] = len(above)
+        caller[r] = group[above[0]] if above else -1
+    flags = np.asarray(stitched.tree_flags).astype(np.int64)
+    tree_class = np.full(nt, -1, dtype=np.int32)
+    tree_items = np.zeros(nt, dtype=np.int64)
+    tree_same = np.full(nt, NOT_COMPARED, dtype=np.uint8)
+    classes, sigs, members = {}, [], []
+    for t in range(nt):
+        rows = stitched.tree_rows[int(stitched.tree_off[t]):int(stitched.tree_off[t + 1])].tolist()
+        items = sorted((int(level[r]), caller[r] if mode == 1 else 0, group[r]) for r in rows if kind[r] == 1 and group[r] >= 0)
+        tree_items[t] = len(items)
+        if not ((flags[t] & need_flags) == need_flags and (flags[t] & skip_flags) == 0):
+            continue
+        sig = []
+        for it in items:
+            if sig and sig[-1][0] == it:
+                sig[-1][1] += 1
+            else:
+                sig.append([it, 1])
+        sig = tuple(it + (k,) for it, k in sig)
+        if sig not in classes:                                    # trees ascend: the first tree of a class is its rep
+            classes[sig] = len(sigs)
+            sigs.append(sig)
+            members.append([])
+        tree_class[t] = classes[sig]
+        members[classes[sig]].append(t)
+        if reference is not None and int(stitched.tree_root[t]) in reference:
+            tree_same[t] = 1 if reference[int(stitched.tree_root[t])] == sig else 0
+    lat = np.asarray(stitched.tree_latency, dtype=np.int64)
+    class_off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    entries = np.array([e for s in sigs for e in s], dtype=np.int32).reshape(-1, 4)
+    eligible = tree_class >= 0
+    compared = [int((tree_same != NOT_COMPARED).sum()), int((tree_same == 1).sum())] if reference is not None else [-1, -1]
+    summary = [int(eligible.sum()), len(sigs), int(tree_items[eligible].sum()), len(entries)] + compared
+    return TraceSignatures(level, tree_class, tree_items, tree_same, np.array([m[0] for m in members], dtype=np.int32),
+                           np.array([len(m) for m in members], dtype=np.int64), np.array([lat[m].sum() for m in members], dtype=np.int64),
+                           np.array([lat[m].min() for m in members], dtype=np.int64), np.array([lat[m].max() for m in members], dtype=np.int64),
+                           class_off, entries, summary, mode, stitched.tree_root)
+
+
+def compare_signatures(pred, true):
+    """The host-side cross-check of tree_same: the eligible trees of `pred` matched with those of `true` by root row, their entry
+    lists compared.  Returns {"tree_same" [trees of pred] as the device writes it, "compared", "same", "share" = same / compared
+    (nan without a compared tree): the share of the matched traces that have the true signature}."""
+    if pred.mode != true.mode:
+        raise ValueError("the two results were computed in different modes")
+    ref = true.by_root()
+    sigs = [pred.signature(c) for c in range(pred.n_classes)]
+    same = np.full(len(pred.tree_class), NOT_COMPARED, dtype=np.uint8)
+    for t, (r, c) in enumerate(zip(pred.tree_root.tolist(), pred.tree_class.tolist())):
+        if c >= 0 and r in ref:
+            same[t] = 1 if ref[r] == sigs[c] else 0
+    compared, ok = int((same != NOT_COMPARED).sum()), int((same == 1).sum())
+    return {"tree_same": same, "compared": compared, "same": ok, "share": float(ok) / compared if compared else float("nan")}
+
+
+def write_signatures_npz(path, names, pred, true=None):
+    """The signatures as one .npz: the arrays of TraceSignatures of the predicted forest (and, prefixed true_, of the true one),
+    the trees' root rows, the mode, the group names, and with both sides shape_accuracy = the share of the compared traces whose
+    signature is the true one."""
+    out = {"mode": np.array(SIGNATURE_MODES[pred.mode]), "group_names": np.array([str(x) for x in names]), "tree_root": pred.tree_root}
+    out.update({k: getattr(pred, k) for k in TraceSignatures.FIELDS})
+    if true is not None:
+        out.update({"true_" + k: getattr(true, k) for k in TraceSignatures.FIELDS})
+        out["true_tree_root"] = true.tree_root
+        compared, same = int(pred.summary[4]), int(pred.summary[5])
+        out["shape_accuracy"] = np.float64(float(same) / compared if compared > 0 else float("nan"))
+    with open(path, "wb") as f:
+        np.savez_compressed(f, **out)

@@ -325,6 +325,97 @@ def test_state_errors(emu_lib, tmp_path):
     eng.close()
 
 
+# ---- 6b. residency: what every event drops of the stages that follow the stitch ----------------------------------------------
+# Consumers in the order they are probed after an event: a refused call changes nothing, and no call restores what a later one
+# needs (the distributions need the attribution, so they go first; the attribution goes last).
+CONSUMERS = ("distributions", "compare", "signatures", "score", "attribute")
+EVERY = frozenset(CONSUMERS)
+# event -> the consumers that refuse with TW_ERR_STATE afterwards; every other one answers what it answered before the event.
+# Taken from the engine as it was before the flags had one owner (tw_engine.hip, "residency of the trace stages").
+RESIDENCY = {
+    "stitch": {"distributions"},                                  # a new forest: the attribution goes, the reference set stays
+    "set_row_groups": {"distributions", "compare"},               # ... the attribution and the reference set go
+    "set_row_cohorts": set(),                                     # only the sorted items, which the next call builds again
+    "score_traces": set(),                                        # only a resident signature result, see below
+    "set_span_rows": EVERY, "run_pass1": EVERY, "load": EVERY, "scale_load": EVERY,
+}
+
+
+def run_residency(lib, tmp_path):
+    corpus, units, skipped, n_traces, table = make_corpus(tmp_path, lib, "hotel", 5, 200, 1.2)
+    rows = traces.rows_from_units(units, table)
+    group, names = traces.groups_from_table(table)
+    cohort = (np.asarray(table["trace"]) % 2).astype(np.int32)
+    W, C = traces.WHOLE, traces.CONFIDENT
+    eng = solve(lib, units, n_traces)
+    calls = {"distributions": lambda: eng.distributions((0.5, 0.9), (1000, 5000)), "compare": lambda: eng.signatures(compare=True),
+             "signatures": lambda: eng.signatures(), "score": lambda: eng.score_traces(0.0), "attribute": lambda: eng.attribute()}
+
+    def resident():
+        """Everything set and every stage run: what the consumers answer now."""
+        eng.set_span_rows(*rows)
+        eng.set_row_groups(group, len(names))
+        eng.set_row_cohorts(cohort, 2)
+        st = eng.stitch()
+        eng.signatures(keep_reference=True)
+        before = {k: calls[k]() for k in reversed(CONSUMERS)}
+        assert before["compare"].summary[4] > 0 and before["distributions"].summary[0] > 0 and before["attribute"].n_selected > 0
+        return st, before
+
+    def probe(before):
+        refused = set()
+        for k in CONSUMERS:
+            try:
+                got = calls[k]()
+            except EngineError as ex:
+                assert ex.code == -4 and "TW_ERR_STATE" in str(ex), (k, str(ex))
+                refused.add(k)
+            else:
+                assert got.same_as(before[k]), k
+        return refused
+
+    seen = {}
+    for event in ("stitch", "set_row_groups", "set_row_cohorts", "score_traces", "set_span_rows", "run_pass1", "load", "scale_load"):
+        st, before = resident()
+        if event == "stitch":
+            eng.stitch()
+        elif event == "set_row_groups":
+            eng.set_row_groups(group, len(names))
+        elif event == "set_row_cohorts":
+            eng.set_row_cohorts(cohort, 2)
+        elif event == "score_traces":
+            # the same query before and after: the call after must compute again, on the CONFIDENT bits of the new threshold
+            sure = eng.signatures(need_flags=W | C)
+            conf = eng.score_traces(2.0)
+            want = int(((st.tree_flags & W) != 0).astype(np.int64) @ conf.tree_confident.astype(np.int64))
+            again = eng.signatures(need_flags=W | C)
+            print("signatures(WHOLE | CONFIDENT): %d eligible at threshold 0, %d at 2" % (sure.n_eligible, again.n_eligible))
+            assert 0 < again.n_eligible == want < sure.n_eligible
+        elif event == "set_span_rows":
+            eng.set_span_rows(*rows)
+        elif event == "run_pass1":
+            eng.run_pass1()
+        elif event == "load":
+            eng.load([u.arrays for u in units])
+        else:
+            eng.scale_load([2] * len(units))
+        seen[event] = probe(before)
+        if event == "load":                                       # back to a solved batch for the last event
+            eng.set_truth([u.true_parent for u in units], [u.in_trace for u in units], n_traces)
+            eng.run_pass1()
+    eng.close()
+    assert seen == {k: set(v) for k, v in RESIDENCY.items()}, seen
+
+
+def test_residency_of_the_trace_stages(emu_lib, tmp_path):
+    run_residency(emu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_residency_of_the_trace_stages_gpu(tmp_path):
+    run_residency(None, tmp_path)
+
+
 def test_malformed_links_end_in_a_status(emu_lib, tmp_path):
     """Host build only: malformed input is never sent to a GPU on purpose."""
     import time

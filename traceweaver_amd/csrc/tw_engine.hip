@@ -35,6 +35,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_COUNT = 22 };   // stage events: 5 + 4 + 4 + 5 + 4
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -182,50 +183,36 @@ struct tw_engine {
     bool scaled_upload = false;             // the batch was uploaded with unit_time_scale (already load-scaled by the caller)
     hipEvent_t ev[EV_COUNT] = {};
     double ms[6] = {0, 0, 0, 0, 0, 0};
-    // tw_set_span_rows / tw_stitch_traces (tw_stitch.h): the row maps of the loaded batch and the scratch of a stitch; dropped by
-    // tw_load_batch (freed with the batch) and tw_scale_load (the lists are re-sorted: the caller permutes the maps and sets them again)
-    StitchDev S{};
+    // The trace stages (tw_set_span_rows .. tw_trace_signatures).  What is resident, what it needs and what drops it: the residency
+    // model below the helpers (drop_*); the flags and capacities here are assigned there and at the one place that makes each resident.
+    StitchDev S{};                          // tw_set_span_rows / tw_stitch_traces (tw_stitch.h): row maps, scratch and forest of a stitch
     int32_t* given_parent = nullptr;        // tw_set_parents: an assignment handed over by the caller (stitched as pass 0)
-    bool parents_given = false;
-    bool rows_set = false;
-    int64_t rows_cap = 0;
-    hipEvent_t st_ev[6] = {};
-    double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
-    // tw_set_row_groups / tw_attribute_traces (tw_attr.h): the forest of the last tw_stitch_traces stays valid until a load, a load
-    // scaling, new row maps or a new pass; the groups are dropped with the row maps
-    AttrDev A{};
-    bool groups_set = false, stitched = false;
-    int64_t st_trees = 0, groups_cap = 0, attr_rows_cap = 0;
-    hipEvent_t at_ev[4] = {};
-    double at_ms[3] = {0, 0, 0};            // per-tree kernel, selection (flags, sort, mark), group reduction
-    double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
-    // tw_get_decisions / tw_score_traces (tw_conf.h): the decisions are those of the resident pass, so only a forest stitched
-    // from it can be scored (stitched_pass: 1 | 2; 0 = from tw_set_parents, -1 = from the truth)
-    ConfDev C{};
-    int stitched_pass = -1;
+    bool rows_set = false, parents_given = false, stitched = false;
+    int64_t rows_cap = 0, st_trees = 0;
+    int stitched_pass = -1;                 // the forest is that of pass 1 | 2 (only such a forest can be scored), 0 = of tw_set_parents, -1 = of the truth
     bool stitched_truth = false;            // ground truth was set when the forest was stitched: its flags carry bit 2
+    AttrDev A{};                            // tw_set_row_groups / tw_attribute_traces (tw_attr.h)
+    bool groups_set = false, attributed = false;
+    int64_t groups_cap = 0, attr_rows_cap = 0;
+    ConfDev C{};                            // tw_get_decisions / tw_score_traces (tw_conf.h): the decisions are those of the resident pass
     int64_t conf_rows_cap = 0;
-    hipEvent_t cf_ev[4] = {};
-    double cf_ms[3] = {0, 0, 0};            // decision kernel, row map + per-tree reduction, calibration
-    // tw_set_row_cohorts / tw_latency_distributions (tw_dist.h): they read what the last tw_attribute_traces left behind (attributed:
-    // dropped by a new stitch, new row groups and whatever drops the forest); the labels are dropped with the row maps; dist_ready:
-    // the sorted items of that attribution and these labels are resident, a further call only gathers
-    DistDev D{};
-    bool attributed = false, cohorts_set = false, dist_ready = false;
+    DistDev D{};                            // tw_set_row_cohorts / tw_latency_distributions (tw_dist.h); dist_ready: the sorted items of the
+    bool cohorts_set = false, dist_ready = false;   // last attribution and the current labels are resident, a further call only gathers
     int64_t cohort_rows_cap = 0, dist_trees_cap = 0, dist_seg_cap = 0, dist_out_cap = 0 /* segments */, dist_items = 0;
     DistKeyDev dist_key{};
-    hipEvent_t ds_ev[5] = {};
-    double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
-    // tw_trace_signatures (tw_sig.h): works on the forest of the last tw_stitch_traces and the row groups; sig_ready: the result of
-    // sig_q on that forest is resident, a further call with the same query only copies; the reference set (ref_set) is keyed by
-    // root row: it survives a new stitch and is dropped with the row maps and with new row groups
-    SigDev G{};
-    bool sig_ready = false, ref_set = false;
+    SigDev G{};                             // tw_trace_signatures (tw_sig.h); sig_ready: the result of sig_q on the forest is resident, a further
+    bool sig_ready = false, ref_set = false;        // call with the same query only copies; ref_set: the reference set, keyed by root row
     tw_sig_query sig_q{};
     int32_t ref_mode = 0, sig_hash_bits = 64;
     int64_t sig_rows_cap = 0, sig_trees_cap = 0, sig_ent_cap = 0, sig_ref_cap = 0, sig_summary[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t sg_ev[4] = {};
+    // HIP events around the parts of a stage (SE_*: a stage's first event; created by tw_create) and what tw_get_timing reports of them
+    hipEvent_t stage_ev[SE_COUNT] = {};
+    double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
+    double at_ms[3] = {0, 0, 0};            // per-tree kernel, selection (flags, sort, mark), group reduction
+    double cf_ms[3] = {0, 0, 0};            // decision kernel, row map + per-tree reduction, calibration
+    double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
+    double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
 };
 
 namespace {
@@ -242,6 +229,12 @@ int fail(tw_engine* e, int code, const std::string& msg) {
             return fail(e, TW_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_s));      \
     } while (0)
 
+#define TWCHK(call)                                                                                \
+    do {                                                                                           \
+        const int _rc = (call);                                                                    \
+        if (_rc != TW_OK) return _rc;                                                              \
+    } while (0)
+
 template <class T>
 int dev_alloc(tw_engine* e, T** p, int64_t count) {
     const size_t bytes = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
@@ -255,6 +248,106 @@ int dev_alloc(tw_engine* e, T** p, int64_t count) {
     e->allocs.push_back(q);
     *p = (T*)q;
     return TW_OK;
+}
+
+#define DEV_ALLOC(ptr, count) TWCHK(dev_alloc(e, &(ptr), (count)))
+
+int ensure_sort_tmp(tw_engine* e, size_t bytes) {
+    if (bytes > e->sort_tmp_bytes) {
+        void* q = nullptr;
+        HIPCHK(hipMalloc(&q, bytes));
+        e->allocs.push_back(q);
+        e->sort_tmp = q;
+        e->sort_tmp_bytes = bytes;
+    }
+    return TW_OK;
+}
+
+// rocprim's two-step call: call(nullptr, bytes) asks for the size of the temporary, call(e->sort_tmp, bytes) runs.  `at_least`: room
+// that a call right after this one needs (the temporary grows before this one is queued, not between the two).
+template <class F>
+int rocprim_call(tw_engine* e, F call, size_t at_least = 0) {
+    size_t bytes = 0;
+    HIPCHK(call(nullptr, bytes));
+    TWCHK(ensure_sort_tmp(e, std::max(bytes, at_least)));
+    bytes = e->sort_tmp_bytes;
+    HIPCHK(call(e->sort_tmp, bytes));
+    return TW_OK;
+}
+
+// an output array the caller may leave out: `count` elements of the device array `src` (queued on the engine's stream)
+template <class T, class U>
+int copy_out(tw_engine* e, T* dst, const U* src, size_t count) {
+    static_assert(sizeof(T) == sizeof(U), "copy_out: the host and the device array differ in element size");
+    if (dst != nullptr) HIPCHK(hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, e->stream));
+    return TW_OK;
+}
+
+// launch shapes.  Flat kernels: a thread per item, workgroups of 256.  Persistent wavefronts that take `per_wave` items at a time:
+// workgroups of `waves` wavefronts, at most 8192 of them.  (TW_COOP_THREADS < 64, the emulation of the tests: that many threads.)
+unsigned flat_threads(const tw_engine* e) { return (unsigned)(e->coop >= 64 ? 256 : e->coop); }
+unsigned flat_grid(int64_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
+struct WaveShape { dim3 grid, block; };
+WaveShape wave_shape(const tw_engine* e, int64_t n, int per_wave, int waves) {
+    const int64_t want = (n / per_wave + 1 + waves - 1) / waves;
+    return WaveShape{dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(e->coop >= 64 ? 64u * (unsigned)waves : (unsigned)e->coop)};
+}
+
+// stage events: milliseconds between events a and b of the stage whose first event is `stage` (SE_*)
+int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
+    float f = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, e->stage_ev[stage + a], e->stage_ev[stage + b]));
+    *ms = f;
+    return TW_OK;
+}
+
+/* ---- residency of the trace stages -----------------------------------------------------------------------------------
+   What the engine holds beyond the batch and the results of a pass, what each item needs (<-) and what drops it besides the
+   items it needs.  Dropping an item drops everything that needs it: the functions below are the only code that clears a flag,
+   so a flag is set only while everything it needs is set, and a consumer tests the items it reads directly.
+
+     row maps         rows_set       tw_set_span_rows     <- the loaded batch.  Dropped by a load and by tw_scale_load (the lists
+                                                             are re-sorted: the caller permutes the maps and sets them again)
+     given parents    parents_given  tw_set_parents       <- the loaded batch.  Dropped like the row maps
+     row groups       groups_set     tw_set_row_groups    <- row maps
+     cohort labels    cohorts_set    tw_set_row_cohorts   <- row maps.  Not set = one cohort that holds every tree
+     reference set    ref_set        tw_trace_signatures  <- row maps, row groups (keyed by root row: it survives a new stitch)
+     forest           stitched       tw_stitch_traces     <- row maps and the parent arrays it was made from.  Dropped by a new pass
+                                                             (it overwrites them) and by a new stitch
+     attribution      attributed     tw_attribute_traces  <- forest, row groups
+     distribution     dist_ready     tw_latency_distributions <- attribution, the cohort labels as they are (set or not)
+       items
+     signature        sig_ready      tw_trace_signatures  <- forest, row groups.  Dropped by tw_score_traces (it rewrites the CONFIDENT
+       result                                                bit that a query may select by) and by a call with another query
+   An API function drops what it is about to replace with one call, before it overwrites anything, and sets its own flag last, when
+   everything has succeeded (tw_trace_signatures owns two items: its result and, with keep_reference, the reference set). */
+void drop_dist(tw_engine* e) { e->dist_ready = false; }
+void drop_sig(tw_engine* e) { e->sig_ready = false; }
+void drop_ref(tw_engine* e) { e->ref_set = false; }
+void drop_attribution(tw_engine* e) { e->attributed = false; drop_dist(e); }
+void drop_forest(tw_engine* e) { e->stitched = false; drop_attribution(e); drop_sig(e); }
+void drop_groups(tw_engine* e) { e->groups_set = false; drop_attribution(e); drop_sig(e); drop_ref(e); }
+void drop_cohorts(tw_engine* e) { e->cohorts_set = false; drop_dist(e); }
+void drop_rows(tw_engine* e) { e->rows_set = false; drop_forest(e); drop_groups(e); drop_cohorts(e); }
+void drop_batch_order(tw_engine* e) { drop_rows(e); e->parents_given = false; }   // a load, tw_scale_load: whatever names spans by position
+// ... and a load frees every buffer with the batch (free_all): the arrays and what was known of their sizes go with the flags
+void drop_buffers(tw_engine* e) {
+    drop_batch_order(e);
+    e->S = StitchDev{}; e->rows_cap = 0; e->given_parent = nullptr;                                    // row maps, forest, given parents
+    e->A = AttrDev{}; e->groups_cap = 0; e->attr_rows_cap = 0;                                         // row groups, attribution
+    e->C = ConfDev{}; e->conf_rows_cap = 0;                                                            // decisions, confidence
+    e->D = DistDev{}; e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;   // cohort labels, items
+    e->G = SigDev{}; e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;   // signatures, reference set
+}
+
+bool pass_resident(const tw_engine* e, int pass) {
+    return (pass == 1 && (e->state == ST_PASS1 || e->state == ST_MIX)) || (pass == 2 && e->state == ST_PASS2);
+}
+
+// what the consumers of the forest say when there is none
+int need_forest(tw_engine* e, const char* fn) {
+    if (e->stitched) return TW_OK;
+    return fail(e, TW_ERR_STATE, std::string(fn) + " needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
 }
 
 int ensure_class_stream(tw_engine* e, int E) {
@@ -286,13 +379,7 @@ void free_all(tw_engine* e) {
     e->allocs.clear();
     e->orig_is = e->orig_ie = e->orig_os = e->orig_oe = nullptr; e->orig_truth = e->orig_trace = nullptr;
     e->truth = nullptr; e->in_trace = nullptr; e->trace_bad = nullptr; e->eval_counts = nullptr; e->n_traces = 0; e->trace_cap = 0;
-    e->S = StitchDev{}; e->rows_set = false; e->rows_cap = 0; e->given_parent = nullptr; e->parents_given = false;
-    e->A = AttrDev{}; e->groups_set = false; e->stitched = false; e->groups_cap = 0; e->attr_rows_cap = 0;
-    e->C = ConfDev{}; e->conf_rows_cap = 0;
-    e->D = DistDev{}; e->attributed = false; e->cohorts_set = false; e->dist_ready = false;
-    e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;
-    e->G = SigDev{}; e->sig_ready = false; e->ref_set = false;
-    e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;
+    drop_buffers(e);
     e->state = ST_EMPTY;
 }
 
@@ -632,7 +719,7 @@ int key_bits(tw_engine* e, const void* keys, const uint32_t* seg_begin, const ui
     if (nseg <= 0 || total <= 0) return TW_OK;
     HIPCHK(hipMemsetAsync(e->key_acc, 0, 2 * sizeof(unsigned long long), e->stream));
     const int bx = (int)std::min<int64_t>(std::max<int64_t>(2048 / nseg, 1), total / nseg / 2048 + 1);  // ~2k workgroups at most
-    hipLaunchKernelGGL(k_key_bits, dim3((unsigned)bx, (unsigned)std::min(nseg, 1024)), dim3(e->coop >= 64 ? 256 : e->coop), 0, e->stream,
+    hipLaunchKernelGGL(k_key_bits, dim3((unsigned)bx, (unsigned)std::min(nseg, 1024)), dim3(flat_threads(e)), 0, e->stream,
                        (const unsigned long long*)keys, seg_begin, seg_end, nseg, e->key_acc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, e->key_acc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -644,17 +731,6 @@ unsigned bit_length(unsigned long long x) {
     unsigned n = 0;
     while (x) { n++; x >>= 1; }
     return n;
-}
-
-int ensure_sort_tmp(tw_engine* e, size_t bytes) {
-    if (bytes > e->sort_tmp_bytes) {
-        void* q = nullptr;
-        HIPCHK(hipMalloc(&q, bytes));
-        e->allocs.push_back(q);
-        e->sort_tmp = q;
-        e->sort_tmp_bytes = bytes;
-    }
-    return TW_OK;
 }
 
 // Sorts every row [seg_begin[s], seg_end[s]) of 64-bit keys ascending into `out` (same positions).  Only the bits
@@ -669,25 +745,17 @@ int sort_rows(tw_engine* e, const Key* keys, Key* out, unsigned size, const uint
     unsigned segbits = 0;
     while ((1u << segbits) < (unsigned)nseg) segbits++;
     const unsigned kb = end_bit - begin_bit;
-    size_t bytes = 0;
     const bool mixed_signs = std::is_signed<Key>::value && end_bit >= 64;  // composite keys compare unsigned
     if (kb + segbits > 64 || kb == 0 || packed > e->comp_cap || mixed_signs) {
-        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, bytes, keys, out, size, (unsigned)nseg, seg_begin, seg_end, begin_bit, end_bit, e->stream));
-        int rc = ensure_sort_tmp(e, bytes);
-        if (rc != TW_OK) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::segmented_radix_sort_keys(e->sort_tmp, bytes, keys, out, size, (unsigned)nseg, seg_begin, seg_end, begin_bit, end_bit, e->stream));
-        return TW_OK;
+        return rocprim_call(e, [&](void* tmp, size_t& bytes) {
+            return rocprim::segmented_radix_sort_keys(tmp, bytes, keys, out, size, (unsigned)nseg, seg_begin, seg_end, begin_bit, end_bit, e->stream);
+        });
     }
     const int bx = (int)std::min<int64_t>(std::max<int64_t>(4096 / nseg, 1), packed / nseg / 1024 + 1);
-    const dim3 grid((unsigned)bx, (unsigned)std::min(nseg, 1024)), block(e->coop >= 64 ? 256 : e->coop);
+    const dim3 grid((unsigned)bx, (unsigned)std::min(nseg, 1024)), block(flat_threads(e));
     hipLaunchKernelGGL(k_rows_pack, grid, block, 0, e->stream, (const unsigned long long*)keys, seg_begin, seg_end, dst_off, nseg,
                        (int)begin_bit, (int)kb, e->comp_a);
-    HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, e->comp_a, e->comp_b, (size_t)packed, 0u, kb + segbits, e->stream));
-    int rc = ensure_sort_tmp(e, bytes);
-    if (rc != TW_OK) return rc;
-    bytes = e->sort_tmp_bytes;
-    HIPCHK(rocprim::radix_sort_keys(e->sort_tmp, bytes, e->comp_a, e->comp_b, (size_t)packed, 0u, kb + segbits, e->stream));
+    TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys(tmp, bytes, e->comp_a, e->comp_b, (size_t)packed, 0u, kb + segbits, e->stream); }));
     hipLaunchKernelGGL(k_rows_unpack, grid, block, 0, e->stream, (const unsigned long long*)e->comp_b, seg_begin, seg_end, dst_off, nseg,
                        (int)begin_bit, (int)kb, fixed, (unsigned long long*)out);
     HIPCHK(hipGetLastError());
@@ -834,15 +902,10 @@ namespace {
 template <class Src>
 int load_sort_pass(tw_engine* e, const Src* src, int64_t n, unsigned bits, unsigned long long* ka, unsigned long long* kb, uint32_t** perm, uint32_t** perm_alt) {
     if (n <= 0 || bits == 0) return TW_OK;
-    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192), block = e->coop >= 64 ? 256 : e->coop;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192), block = flat_threads(e);
     if (sizeof(Src) == 8) hipLaunchKernelGGL(k_load_keys64, dim3(grid), dim3(block), 0, e->stream, (const int64_t*)src, (const uint32_t*)*perm, n, ka);
     else hipLaunchKernelGGL(k_load_keys32, dim3(grid), dim3(block), 0, e->stream, (const int32_t*)src, (const uint32_t*)*perm, n, ka);
-    size_t bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, ka, kb, *perm, *perm_alt, (size_t)n, 0u, bits, e->stream));
-    int rc = ensure_sort_tmp(e, bytes);
-    if (rc != TW_OK) return rc;
-    bytes = e->sort_tmp_bytes;
-    HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, ka, kb, *perm, *perm_alt, (size_t)n, 0u, bits, e->stream));
+    TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, *perm, *perm_alt, (size_t)n, 0u, bits, e->stream); }));
     std::swap(*perm, *perm_alt);
     return TW_OK;
 }
@@ -934,7 +997,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
                                    "or the scaled timestamps span too many binades for int64");
     // stable least-significant-key-first passes: trace order, end, start, list
     const unsigned grid_in = (unsigned)std::min<int64_t>((n_in + 255) / 256, 8192), grid_out = (unsigned)std::min<int64_t>((n_out + 255) / 256, 8192);
-    const unsigned block = e->coop >= 64 ? 256 : e->coop;
+    const unsigned block = flat_threads(e);
     int64_t* d_is = const_cast<int64_t*>(P.in_start); int64_t* d_ie = const_cast<int64_t*>(P.in_end);
     int64_t* d_os = const_cast<int64_t*>(P.out_start); int64_t* d_oe = const_cast<int64_t*>(P.out_end);
     for (int side = 0; side < 2; side++) {
@@ -970,9 +1033,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     HIPCHK(hipMemcpyAsync(const_cast<UnitDev*>(P.units), e->units.data(), sizeof(UnitDev) * e->units.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->state = ST_LOADED; e->pass1_done = false;
-    e->parents_given = false;
-    e->rows_set = false;   // every list was re-sorted: in_row / out_row no longer name the spans at these positions
-    e->groups_set = false; e->stitched = false; e->cohorts_set = false; e->ref_set = false;
+    drop_batch_order(e);   // every list was re-sorted: in_row / out_row and the given parents no longer name the spans at these positions
     for (int E = 0; E <= kMaxEp; E++) { e->wide_pass1[E] = -1; e->hard_pass1[E] = -1; e->split_pass1[E] = -1; }
     return TW_OK;
 }
@@ -998,6 +1059,7 @@ int tw_create(int device_id, tw_engine** out) {
     hipError_t s = hipSetDevice(device_id);
     if (s == hipSuccess) s = hipStreamCreate(&e->stream);
     for (int i = 0; i < EV_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->ev[i]);
+    for (int i = 0; i < SE_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->stage_ev[i]);
     // (Priorities for the class streams were measured: every class stream created with one -- the classes of four and more
     // endpoints highest -- takes the media shape's enumeration from 4.6 to 4.4 ms per launch set and the nodejs shape's from 0.9
     // to 1.2 ms: streams created with a priority, any, are mapped to the hardware queues differently and that shape's two classes
@@ -1070,14 +1132,8 @@ void tw_destroy(tw_engine* e) {
         for (int j = 0; j < 3; j++)
             if (e->post_join[i][j]) (void)hipEventDestroy(e->post_join[i][j]);
     }
-    for (int i = 0; i < 6; i++)
-        if (e->st_ev[i]) (void)hipEventDestroy(e->st_ev[i]);
-    for (int i = 0; i < 4; i++)
-        if (e->at_ev[i]) (void)hipEventDestroy(e->at_ev[i]);
-    for (int i = 0; i < 4; i++)
-        if (e->cf_ev[i]) (void)hipEventDestroy(e->cf_ev[i]);
-    for (int i = 0; i < 5; i++)
-        if (e->ds_ev[i]) (void)hipEventDestroy(e->ds_ev[i]);
+    for (int i = 0; i < SE_COUNT; i++)
+        if (e->stage_ev[i]) (void)hipEventDestroy(e->stage_ev[i]);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1255,34 +1311,33 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     P.lean_grid = std::max(env_int("TW_LEAN_GRID", TW_LEAN_GRID), 1);
     P.tile_max_deep = std::min(std::max(env_int("TW_TILE_MAX_DEEP", kTileMax), 0), kTileMax);
     int rc;
-#define ALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
     e->arena_req.clear();
     e->arena_open = true;
     UnitDev* d_units; TileDev* d_tiles; int64_t *d_is, *d_ie, *d_os, *d_oe, *d_gs;
-    ALLOC(d_units, P.n_units); ALLOC(d_tiles, P.n_tiles);
-    ALLOC(d_is, n_in_total); ALLOC(d_ie, n_in_total); ALLOC(d_os, n_out_total); ALLOC(d_oe, n_out_total);
-    ALLOC(d_gs, P.n_units);
-    ALLOC(P.in_end_sorted, n_in_total); ALLOC(P.out_end_sorted, n_out_total);
-    ALLOC(P.gparam, gp * 4);
-    ALLOC(e->mix_n_dev, slots); ALLOC(e->mix_p_dev, slots * kMaxComp * 3); ALLOC(e->mix_c_dev, slots * kMaxComp * 4);
-    ALLOC(P.pm_val, n_in_total); ALLOC(P.pm_idx, n_in_total); ALLOC(P.pc, n_in_total + 1); ALLOC(P.seg, n_in_total);
-    ALLOC(P.win_end, n_in_total); ALLOC(P.wid, n_in_total); ALLOC(P.w_last, n_in_total);
-    ALLOC(P.unit_nwin, P.n_units); ALLOC(P.w_dirty, n_in_total); ALLOC(P.w_conf, n_in_total);
-    ALLOC(P.tk_n, n_in_total); ALLOC(P.leaves, n_in_total); ALLOC(P.leaves0, n_in_total); ALLOC(P.chosen, n_in_total); ALLOC(P.rep, n_in_total);
-    ALLOC(P.tkr_n, n_in_total);
-    ALLOC(P.tk_idx, ie * kTopK); ALLOC(P.tkr_idx, ie * kTopK);
-    ALLOC(P.tk_score, n_in_total * kTopK); ALLOC(P.tkr_score, n_in_total * kTopK);
-    ALLOC(P.c_lo, ie); ALLOC(P.c_hi, ie); ALLOC(P.c_bits, ie * kCandWords); ALLOC(P.parent, ie);
-    ALLOC(P.gone, ie * kCandWords); ALLOC(P.gone_valid, n_in_total); ALLOC(P.leaves_r, n_in_total);
-    ALLOC(P.frontier, (int64_t)kFrontierSlots * 2 * kFrontierCap); 
+    DEV_ALLOC(d_units, P.n_units); DEV_ALLOC(d_tiles, P.n_tiles);
+    DEV_ALLOC(d_is, n_in_total); DEV_ALLOC(d_ie, n_in_total); DEV_ALLOC(d_os, n_out_total); DEV_ALLOC(d_oe, n_out_total);
+    DEV_ALLOC(d_gs, P.n_units);
+    DEV_ALLOC(P.in_end_sorted, n_in_total); DEV_ALLOC(P.out_end_sorted, n_out_total);
+    DEV_ALLOC(P.gparam, gp * 4);
+    DEV_ALLOC(e->mix_n_dev, slots); DEV_ALLOC(e->mix_p_dev, slots * kMaxComp * 3); DEV_ALLOC(e->mix_c_dev, slots * kMaxComp * 4);
+    DEV_ALLOC(P.pm_val, n_in_total); DEV_ALLOC(P.pm_idx, n_in_total); DEV_ALLOC(P.pc, n_in_total + 1); DEV_ALLOC(P.seg, n_in_total);
+    DEV_ALLOC(P.win_end, n_in_total); DEV_ALLOC(P.wid, n_in_total); DEV_ALLOC(P.w_last, n_in_total);
+    DEV_ALLOC(P.unit_nwin, P.n_units); DEV_ALLOC(P.w_dirty, n_in_total); DEV_ALLOC(P.w_conf, n_in_total);
+    DEV_ALLOC(P.tk_n, n_in_total); DEV_ALLOC(P.leaves, n_in_total); DEV_ALLOC(P.leaves0, n_in_total); DEV_ALLOC(P.chosen, n_in_total); DEV_ALLOC(P.rep, n_in_total);
+    DEV_ALLOC(P.tkr_n, n_in_total);
+    DEV_ALLOC(P.tk_idx, ie * kTopK); DEV_ALLOC(P.tkr_idx, ie * kTopK);
+    DEV_ALLOC(P.tk_score, n_in_total * kTopK); DEV_ALLOC(P.tkr_score, n_in_total * kTopK);
+    DEV_ALLOC(P.c_lo, ie); DEV_ALLOC(P.c_hi, ie); DEV_ALLOC(P.c_bits, ie * kCandWords); DEV_ALLOC(P.parent, ie);
+    DEV_ALLOC(P.gone, ie * kCandWords); DEV_ALLOC(P.gone_valid, n_in_total); DEV_ALLOC(P.leaves_r, n_in_total);
+    DEV_ALLOC(P.frontier, (int64_t)kFrontierSlots * 2 * kFrontierCap); 
     // long tuple lists: a pool that grows with the batch (one list per 16 k incoming spans, 48 ... 512 of 32 MB each; recycled)
     P.frontier_big_slots = (int32_t)std::min<int64_t>(std::max<int64_t>(n_in_total / 16384, kFrontierBigSlots), std::max(kFrontierBigSlots, 512));
-    ALLOC(P.frontier_big, (int64_t)P.frontier_big_slots * 2 * kFrontierBigCap);
-    ALLOC(P.pair_pool, (int64_t)kPairSlots * kPairSpill);
-    ALLOC(P.owner, n_out_total);
-    ALLOC(P.gaps, gaps);
-    ALLOC(e->tile_ids, (int64_t)tile_ids_h.size());
-    ALLOC(P.heavy_in_unit, n_in_total); ALLOC(P.heavy_in_idx, n_in_total);
+    DEV_ALLOC(P.frontier_big, (int64_t)P.frontier_big_slots * 2 * kFrontierBigCap);
+    DEV_ALLOC(P.pair_pool, (int64_t)kPairSlots * kPairSpill);
+    DEV_ALLOC(P.owner, n_out_total);
+    DEV_ALLOC(P.gaps, gaps);
+    DEV_ALLOC(e->tile_ids, (int64_t)tile_ids_h.size());
+    DEV_ALLOC(P.heavy_in_unit, n_in_total); DEV_ALLOC(P.heavy_in_idx, n_in_total);
     {   // long enumerations: a list entry per span plus the extra entries of the split ones (an eighth of the class + 64), two
         // scratch slots per extra entry
         int64_t big_total = 0, slots = 0, want = 0;
@@ -1297,22 +1352,22 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
             big_total += n_cls + extra; slots += 2 * extra;
         }
         P.heavy_big_off[kMaxEp + 1] = (int32_t)big_total; P.part_off[kMaxEp + 1] = (int32_t)slots;
-        ALLOC(P.heavy_big_unit, big_total); ALLOC(P.heavy_big_idx, big_total);
-        ALLOC(P.heavy_big_part, big_total); ALLOC(P.heavy_big_slot, big_total);
-        ALLOC(P.fb_unit, big_total); ALLOC(P.fb_idx, big_total); ALLOC(P.fb_part, big_total); ALLOC(P.fb_slot, big_total);
-        ALLOC(P.split_unit, slots); ALLOC(P.split_idx, slots); ALLOC(P.split_slot, slots); ALLOC(P.split_parts, slots);
-        ALLOC(P.part_n, slots); ALLOC(P.part_leaves, slots); ALLOC(P.part_score, slots * kTopK); ALLOC(P.part_idx, slots * kTopK * kMaxEp);
-        ALLOC(P.part_bits, slots * kMaxEp * kCandWords);
-        ALLOC(P.part_logn, slots); ALLOC(P.part_log_sc, slots * kPartLogCap); ALLOC(P.part_log_ix, slots * kPartLogCap);
-        ALLOC(P.part_lo, slots); ALLOC(P.part_hi, slots); ALLOC(P.part_lvl, slots);
+        DEV_ALLOC(P.heavy_big_unit, big_total); DEV_ALLOC(P.heavy_big_idx, big_total);
+        DEV_ALLOC(P.heavy_big_part, big_total); DEV_ALLOC(P.heavy_big_slot, big_total);
+        DEV_ALLOC(P.fb_unit, big_total); DEV_ALLOC(P.fb_idx, big_total); DEV_ALLOC(P.fb_part, big_total); DEV_ALLOC(P.fb_slot, big_total);
+        DEV_ALLOC(P.split_unit, slots); DEV_ALLOC(P.split_idx, slots); DEV_ALLOC(P.split_slot, slots); DEV_ALLOC(P.split_parts, slots);
+        DEV_ALLOC(P.part_n, slots); DEV_ALLOC(P.part_leaves, slots); DEV_ALLOC(P.part_score, slots * kTopK); DEV_ALLOC(P.part_idx, slots * kTopK * kMaxEp);
+        DEV_ALLOC(P.part_bits, slots * kMaxEp * kCandWords);
+        DEV_ALLOC(P.part_logn, slots); DEV_ALLOC(P.part_log_sc, slots * kPartLogCap); DEV_ALLOC(P.part_log_ix, slots * kPartLogCap);
+        DEV_ALLOC(P.part_lo, slots); DEV_ALLOC(P.part_hi, slots); DEV_ALLOC(P.part_lvl, slots);
         // the arena of the deferred spans' prefix lists: a few thousand entries per span that defers, recycled every pass
         int64_t deep = 0;
         for (int cls = std::max(P.defer_min_e, 3); cls <= kMaxEp; cls++) deep += heavy_off_h[cls + 1] - heavy_off_h[cls];
         P.defer_cap = (int32_t)(deep > 0 ? std::min<int64_t>(std::max<int64_t>(deep * kDeferListPerSpan, kDeferListMin), 1ll << 28) : 1);
-        ALLOC(P.defer_list, P.defer_cap);
+        DEV_ALLOC(P.defer_list, P.defer_cap);
     }
     for (int cls = 0; cls <= kMaxEp + 1; cls++) P.heavy_in_off[cls] = heavy_off_h[cls];
-    ALLOC(P.prof, 32); ALLOC(e->key_acc, 2);
+    DEV_ALLOC(P.prof, 32); DEV_ALLOC(e->key_acc, 2);
     const int64_t sel_cap = (int64_t)P.n_tiles * e->tile + 1;   // every segment of the selection lists has room for all windows of its tiles
     {   // the counter block (every array on a 128-byte line of its own: their atomics come from different kernels)
         int64_t at = 0;
@@ -1337,24 +1392,24 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
             D.unit_stats = (int64_t*)(c + o_us);
         };
         if (e->arena_open) e->arena_req.emplace_back(place, ((size_t)at * sizeof(int32_t) + 255) / 256 * 256);   // (placed by arena_commit, like the rest)
-        else { ALLOC(e->ctr, at); place(e->ctr); }
+        else { DEV_ALLOC(e->ctr, at); place(e->ctr); }
     }
-    ALLOC(P.heavy_unit, sel_cap); ALLOC(P.heavy_win, sel_cap);
-    ALLOC(P.tiny_unit, sel_cap); ALLOC(P.tiny_win, sel_cap);
-    ALLOC(P.rheavy_unit, sel_cap); ALLOC(P.rheavy_win, sel_cap); ALLOC(P.rtiny_unit, sel_cap); ALLOC(P.rtiny_win, sel_cap);
-    ALLOC(P.hard_unit, sel_cap / (kBruteMax + 1) + 1 + kSelSlots); ALLOC(P.hard_win, sel_cap / (kBruteMax + 1) + 1 + kSelSlots);   // (a searched window holds more than kBruteMax spans)
-    ALLOC(e->rank_in, n_in_total); ALLOC(e->rank_out, n_out_total);
-    ALLOC(e->agg_pair, P.n_tiles); ALLOC(e->agg_i32, P.n_tiles); ALLOC(e->agg_i32b, P.n_tiles);
-    ALLOC(e->seg_in, (int64_t)seg_in.size()); ALLOC(e->seg_out, (int64_t)seg_out.size());
-    ALLOC(e->gaps_sorted, gaps); ALLOC(e->fit_models, slots * kMaxComp * kModelStride);
-    ALLOC(e->fit_uval, gaps); ALLOC(e->fit_ustart, gaps); ALLOC(e->fit_row_n, slots); ALLOC(e->fit_row_uniq, slots);
-    ALLOC(e->fit_tape, slots * kFitRowTape); ALLOC(e->fit_tape_off, slots); ALLOC(e->fit_tape100, kMaxComp * 13);
+    DEV_ALLOC(P.heavy_unit, sel_cap); DEV_ALLOC(P.heavy_win, sel_cap);
+    DEV_ALLOC(P.tiny_unit, sel_cap); DEV_ALLOC(P.tiny_win, sel_cap);
+    DEV_ALLOC(P.rheavy_unit, sel_cap); DEV_ALLOC(P.rheavy_win, sel_cap); DEV_ALLOC(P.rtiny_unit, sel_cap); DEV_ALLOC(P.rtiny_win, sel_cap);
+    DEV_ALLOC(P.hard_unit, sel_cap / (kBruteMax + 1) + 1 + kSelSlots); DEV_ALLOC(P.hard_win, sel_cap / (kBruteMax + 1) + 1 + kSelSlots);   // (a searched window holds more than kBruteMax spans)
+    DEV_ALLOC(e->rank_in, n_in_total); DEV_ALLOC(e->rank_out, n_out_total);
+    DEV_ALLOC(e->agg_pair, P.n_tiles); DEV_ALLOC(e->agg_i32, P.n_tiles); DEV_ALLOC(e->agg_i32b, P.n_tiles);
+    DEV_ALLOC(e->seg_in, (int64_t)seg_in.size()); DEV_ALLOC(e->seg_out, (int64_t)seg_out.size());
+    DEV_ALLOC(e->gaps_sorted, gaps); DEV_ALLOC(e->fit_models, slots * kMaxComp * kModelStride);
+    DEV_ALLOC(e->fit_uval, gaps); DEV_ALLOC(e->fit_ustart, gaps); DEV_ALLOC(e->fit_row_n, slots); DEV_ALLOC(e->fit_row_uniq, slots);
+    DEV_ALLOC(e->fit_tape, slots * kFitRowTape); DEV_ALLOC(e->fit_tape_off, slots); DEV_ALLOC(e->fit_tape100, kMaxComp * 13);
     e->fit_tape_cap = slots * kFitRowTape;
-    ALLOC(e->fit_centres, slots * kMaxComp * (kMaxComp + 1));
-    ALLOC(e->slot_unit, slots); ALLOC(e->slot_scored, slots);
-    ALLOC(e->seg_gap, (int64_t)seg_gap_h.size()); ALLOC(e->seg_gap_end, (int64_t)seg_gap_end_h.size()); ALLOC(e->seg_gap_dst, (int64_t)seg_gap_dst_h.size());
+    DEV_ALLOC(e->fit_centres, slots * kMaxComp * (kMaxComp + 1));
+    DEV_ALLOC(e->slot_unit, slots); DEV_ALLOC(e->slot_scored, slots);
+    DEV_ALLOC(e->seg_gap, (int64_t)seg_gap_h.size()); DEV_ALLOC(e->seg_gap_end, (int64_t)seg_gap_end_h.size()); DEV_ALLOC(e->seg_gap_dst, (int64_t)seg_gap_dst_h.size());
     e->comp_cap = std::max(std::max(n_in_total, n_out_total), e->n_gap_scored);
-    ALLOC(e->comp_a, e->comp_cap); ALLOC(e->comp_b, e->comp_cap);
+    DEV_ALLOC(e->comp_a, e->comp_cap); DEV_ALLOC(e->comp_b, e->comp_cap);
     // skip mode: per unit the start-ordered view of every endpoint list (TallySkipSpans sorts the lists in place,
     // traceweaver_v3.py:968-971; the top_k_2 enumeration walks that order), time windows, pools, (mean, std) table, draw counters
     e->skip_mode = b->skip != nullptr;
@@ -1381,10 +1436,9 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
             dist_h.insert(dist_h.end(), K.dist, K.dist + (int64_t)(U.E + 1) * (U.E + 1) * 2);
         }
         e->skip_fetch_n = (int64_t)pool_h.size();
-        ALLOC(e->skip_units, b->n_units); ALLOC(e->skip_perm, n_out_total); ALLOC(e->skip_tw, (int64_t)tw_h.size());
-        ALLOC(e->skip_pool, (int64_t)pool_h.size()); ALLOC(e->skip_dist, (int64_t)dist_h.size()); ALLOC(e->skip_fetch, e->skip_fetch_n);
+        DEV_ALLOC(e->skip_units, b->n_units); DEV_ALLOC(e->skip_perm, n_out_total); DEV_ALLOC(e->skip_tw, (int64_t)tw_h.size());
+        DEV_ALLOC(e->skip_pool, (int64_t)pool_h.size()); DEV_ALLOC(e->skip_dist, (int64_t)dist_h.size()); DEV_ALLOC(e->skip_fetch, e->skip_fetch_n);
     }
-#undef ALLOC
     rc = arena_commit(e);
     if (rc != TW_OK) return rc;
     if (e->skip_mode) {
@@ -1441,7 +1495,7 @@ int tw_run_pass1(tw_engine* e) {
     if (e == nullptr) return TW_ERR_ARG;
     if (e->state < ST_LOADED) return fail(e, TW_ERR_STATE, "tw_run_pass1 before tw_load_batch");
     HIPCHK(hipSetDevice(e->device));
-    e->stitched = false;   // (the parent arrays a stitched forest was made from are overwritten)
+    drop_forest(e);   // (the parent arrays a stitched forest was made from are overwritten)
     const int rc = run_pass(e, 1);
     e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
     if (rc == TW_OK) { e->state = ST_PASS1; e->pass1_done = true; }
@@ -1556,7 +1610,6 @@ int fit_prepare(tw_engine* e) {
             return TW_OK;
         }
     }
-    size_t bytes = 0;
     const unsigned size = (unsigned)e->n_gaps, nseg = (unsigned)e->n_gap_rows;
     // gap samples are non-negative integers (and NaN = 0x7ff8...0) stored as doubles: their low mantissa bits
     // are all zero, the sort starts at the lowest bit set anywhere.  A negative key (none can occur: children
@@ -1566,13 +1619,10 @@ int fit_prepare(tw_engine* e) {
     if (rck != TW_OK) return rck;
     unsigned begin_bit = 0;
     if (kb[1] != 0 && !(kb[1] >> 63)) while (!((kb[1] >> begin_bit) & 1)) begin_bit++;
-    (void)bytes;
     if (kb[1] >> 63) {  // a negative sample: leave the key transform to rocprim (never seen; see above)
-        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, bytes, (const double*)e->P.gaps, e->gaps_sorted, size, nseg, e->seg_gap, e->seg_gap_end, 0, 64, e->stream));
-        int rcs = ensure_sort_tmp(e, bytes);
-        if (rcs != TW_OK) return rcs;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::segmented_radix_sort_keys(e->sort_tmp, bytes, (const double*)e->P.gaps, e->gaps_sorted, size, nseg, e->seg_gap, e->seg_gap_end, 0, 64, e->stream));
+        TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) {
+            return rocprim::segmented_radix_sort_keys(tmp, bytes, (const double*)e->P.gaps, e->gaps_sorted, size, nseg, e->seg_gap, e->seg_gap_end, 0, 64, e->stream);
+        }));
     } else {  // non-negative doubles order like their bit patterns
         int rcs = sort_rows(e, (const unsigned long long*)e->P.gaps, (unsigned long long*)e->gaps_sorted, size, e->seg_gap, e->seg_gap_end,
                             e->seg_gap_dst, (int)nseg, e->n_gap_scored, begin_bit, 64, 0ull);
@@ -1759,7 +1809,7 @@ int tw_run_pass2(tw_engine* e) {
     // pass reads what the first left behind: cut-offs, window flags, tuple counts)
     if (!e->pass1_done) return fail(e, TW_ERR_STATE, "tw_run_pass2 on a batch whose first pass has not run (tw_run_pass1 first)");
     HIPCHK(hipSetDevice(e->device));
-    e->stitched = false;
+    drop_forest(e);
     const int rc = run_pass(e, 2);
     if (rc == TW_OK) e->state = ST_PASS2;
     return rc;
@@ -1772,16 +1822,14 @@ int tw_get_results(tw_engine* e, int pass, const tw_results* r) {
     HIPCHK(hipSetDevice(e->device));
     const Dev& P = e->P;
     const int64_t n = P.n_in_total;
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-    D2H(r->parent, P.parent, sizeof(int32_t) * e->n_ie);
-    D2H(r->topk_idx, P.tk_idx, sizeof(int32_t) * e->n_ie * kTopK);
-    D2H(r->topk_score, P.tk_score, sizeof(double) * n * kTopK);
-    D2H(r->topk_n, P.tk_n, sizeof(int32_t) * n);
-    D2H(r->chosen, P.chosen, sizeof(int32_t) * n);
-    D2H(r->leaves, P.leaves, sizeof(int64_t) * n);
-    D2H(r->window_end, P.win_end, sizeof(uint8_t) * n);
-    D2H(r->unit_stats, P.unit_stats, sizeof(int64_t) * 8 * P.n_units);
-#undef D2H
+    TWCHK(copy_out(e, r->parent, P.parent, e->n_ie));
+    TWCHK(copy_out(e, r->topk_idx, P.tk_idx, e->n_ie * kTopK));
+    TWCHK(copy_out(e, r->topk_score, P.tk_score, n * kTopK));
+    TWCHK(copy_out(e, r->topk_n, P.tk_n, n));
+    TWCHK(copy_out(e, r->chosen, P.chosen, n));
+    TWCHK(copy_out(e, r->leaves, P.leaves, n));
+    TWCHK(copy_out(e, r->window_end, P.win_end, n));
+    TWCHK(copy_out(e, r->unit_stats, P.unit_stats, 8 * P.n_units));
     HIPCHK(hipStreamSynchronize(e->stream));
     return TW_OK;
 }
@@ -1869,7 +1917,7 @@ int tw_find_order(tw_engine* e, int32_t n_units, const int64_t* unit_in_off, con
         O.unit_in_off = (const int64_t*)d_io; O.unit_E = (const int32_t*)d_E; O.ep_base = (const int64_t*)d_eb; O.ep_off = (const int64_t*)d_eo;
         O.ie_off = (const int64_t*)d_ie; O.out_start = (const int64_t*)d_os; O.out_end = (const int64_t*)d_oe; O.truth = (const int32_t*)d_tr;
         O.viol = (unsigned long long*)d_v;
-        const int threads = e->coop >= 64 ? 256 : e->coop;
+        const int threads = (int)flat_threads(e);
         const unsigned bx = (unsigned)std::min<int64_t>((max_n + threads - 1) / threads + 1, 1024);
         for (int u0 = 0; u0 < n_units && s == hipSuccess; u0 += 32768) {  // grid.y is limited to 65535
             OrderDev Q = O;
@@ -1941,7 +1989,7 @@ int tw_evaluate(tw_engine* e, int64_t* per_unit, uint8_t* trace_flags, int64_t* 
                        (const int32_t*)(e->n_traces > 0 ? e->in_trace : nullptr), e->eval_counts, e->trace_bad,
                        e->n_traces > 0 ? e->trace_bad + e->n_traces : nullptr);
     if (e->n_traces > 0 && e2e != nullptr)
-        hipLaunchKernelGGL(k_count_flags, dim3((unsigned)std::min<int64_t>(e->n_traces / 1024 + 1, 1024)), dim3(e->coop >= 64 ? 256 : e->coop), 0, e->stream,
+        hipLaunchKernelGGL(k_count_flags, dim3((unsigned)std::min<int64_t>(e->n_traces / 1024 + 1, 1024)), dim3(flat_threads(e)), 0, e->stream,
                            (const uint8_t*)e->trace_bad, (const uint8_t*)(e->trace_bad + e->n_traces), e->n_traces, e->eval_counts + (nc - 2));
     HIPCHK(hipGetLastError());
     std::vector<unsigned long long> h((size_t)nc);
@@ -1983,22 +2031,20 @@ int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const 
             return fail(e, TW_ERR_ARG, in ? "tw_set_span_rows: in_row must name distinct server rows of the table" : "tw_set_span_rows: out_row must name distinct client rows of the table");
         seen[(size_t)r] = 1;
     }
+    drop_rows(e);   // (the groups, the cohort labels and the reference set name rows of the old maps)
     StitchDev& S = e->S;
-    int rc;
-#define SALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
     if (S.link == nullptr || n_rows > e->rows_cap) {   // (freed with the batch)
         int32_t *in_d, *out_d, *link_d; uint8_t* kind_d; int64_t *start_d, *end_d;
-        SALLOC(in_d, P.n_in_total); SALLOC(out_d, P.n_out_total); SALLOC(link_d, n_rows); SALLOC(kind_d, n_rows); SALLOC(start_d, n_rows); SALLOC(end_d, n_rows);
+        DEV_ALLOC(in_d, P.n_in_total); DEV_ALLOC(out_d, P.n_out_total); DEV_ALLOC(link_d, n_rows); DEV_ALLOC(kind_d, n_rows); DEV_ALLOC(start_d, n_rows); DEV_ALLOC(end_d, n_rows);
         S.in_row = in_d; S.out_row = out_d; S.row_link = link_d; S.row_kind = kind_d; S.row_start = start_d; S.row_end = end_d;
-        SALLOC(S.link, n_rows); SALLOC(S.state_a, n_rows); SALLOC(S.state_b, n_rows);
-        SALLOC(S.root, n_rows); SALLOC(S.depth, n_rows); SALLOC(S.true_root, n_rows); SALLOC(S.una, n_rows); SALLOC(S.bad, n_rows);
-        SALLOC(S.cursor, n_rows); SALLOC(S.chunk_sum, n_rows / kStitchScanItems + 2);
-        SALLOC(S.rows_tmp, n_rows); SALLOC(S.tree_rows, n_rows); SALLOC(S.tree_root, n_rows);
-        SALLOC(S.tree_off, n_rows + 1); SALLOC(S.tree_latency, n_rows); SALLOC(S.tree_flags, n_rows);
-        SALLOC(S.totals, 4); SALLOC(S.changed, kStitchMaxRounds); SALLOC(S.err, 1);
+        DEV_ALLOC(S.link, n_rows); DEV_ALLOC(S.state_a, n_rows); DEV_ALLOC(S.state_b, n_rows);
+        DEV_ALLOC(S.root, n_rows); DEV_ALLOC(S.depth, n_rows); DEV_ALLOC(S.true_root, n_rows); DEV_ALLOC(S.una, n_rows); DEV_ALLOC(S.bad, n_rows);
+        DEV_ALLOC(S.cursor, n_rows); DEV_ALLOC(S.chunk_sum, n_rows / kStitchScanItems + 2);
+        DEV_ALLOC(S.rows_tmp, n_rows); DEV_ALLOC(S.tree_rows, n_rows); DEV_ALLOC(S.tree_root, n_rows);
+        DEV_ALLOC(S.tree_off, n_rows + 1); DEV_ALLOC(S.tree_latency, n_rows); DEV_ALLOC(S.tree_flags, n_rows);
+        DEV_ALLOC(S.totals, 4); DEV_ALLOC(S.changed, kStitchMaxRounds); DEV_ALLOC(S.err, 1);
         e->rows_cap = n_rows;
     }
-#undef SALLOC
     S.n_rows = n_rows;
     HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(S.in_row), in_row, sizeof(int32_t) * (size_t)P.n_in_total, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(S.out_row), out_row, sizeof(int32_t) * (size_t)P.n_out_total, hipMemcpyHostToDevice, e->stream));
@@ -2007,11 +2053,7 @@ int tw_set_span_rows(tw_engine* e, int64_t n_rows, const int32_t* in_row, const 
     HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(S.row_start), row_start, sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(S.row_end), row_end, sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 6; i++)
-        if (e->st_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->st_ev[i]));
     e->rows_set = true;
-    e->ref_set = false;
-    e->groups_set = false; e->stitched = false; e->cohorts_set = false;   // (new row maps: the groups and the cohort labels name rows of the old ones)
     return TW_OK;
 }
 
@@ -2031,7 +2073,7 @@ int tw_set_parents(tw_engine* e, const int32_t* parent) {
                 if (p[i] >= 0 && taken[(size_t)p[i]]++) return fail(e, TW_ERR_ARG, "tw_set_parents: a call is given to two requests");
             }
         }
-    if (e->given_parent == nullptr) { const int rc = dev_alloc(e, &e->given_parent, e->n_ie); if (rc != TW_OK) return rc; }
+    if (e->given_parent == nullptr) DEV_ALLOC(e->given_parent, e->n_ie);
     HIPCHK(hipMemcpyAsync(e->given_parent, parent, sizeof(int32_t) * (size_t)e->n_ie, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->parents_given = true;
@@ -2045,15 +2087,15 @@ namespace {
 int stitch_forest(tw_engine* e, const int32_t* src, int32_t* root_out, int32_t* depth_out, bool final, const int32_t* true_root, int* rounds) {
     const Dev& P = e->P;
     const StitchDev& S = e->S;
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
-    const dim3 rows((unsigned)((S.n_rows + threads - 1) / threads)), tb(threads);
+    const unsigned threads = flat_threads(e);
+    const dim3 rows(flat_grid(S.n_rows, threads)), tb(threads);
     HIPCHK(hipMemsetAsync(S.changed, 0, sizeof(int32_t) * kStitchMaxRounds, e->stream));
     hipLaunchKernelGGL(k_stitch_init, rows, tb, 0, e->stream, S);
     int max_e = 1;
     for (const UnitDev& U : e->units) max_e = std::max(max_e, (int)U.E);
     hipLaunchKernelGGL(k_stitch_links, dim3((unsigned)P.n_tiles, (unsigned)max_e), dim3((unsigned)e->tile), 0, e->stream, P, S, src);
     HIPCHK(hipGetLastError());
-    if (final) HIPCHK(hipEventRecord(e->st_ev[1], e->stream));
+    if (final) HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH + 1], e->stream));
     unsigned long long *a = S.state_a, *b = S.state_b;
     int round = 0;
     for (;; round++) {
@@ -2068,7 +2110,7 @@ int stitch_forest(tw_engine* e, const int32_t* src, int32_t* root_out, int32_t* 
         if (!moved) break;
     }
     *rounds = round + 1;
-    if (final) HIPCHK(hipEventRecord(e->st_ev[2], e->stream));
+    if (final) HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH + 2], e->stream));
     hipLaunchKernelGGL(k_stitch_count, rows, tb, 0, e->stream, S, (const unsigned long long*)a, root_out, depth_out, final ? 1 : 0, true_root);
     HIPCHK(hipGetLastError());
     return TW_OK;
@@ -2078,56 +2120,47 @@ int stitch_forest(tw_engine* e, const int32_t* src, int32_t* root_out, int32_t* 
 
 int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* out, int64_t* n_trees, int64_t* counts4) {
     if (e == nullptr || out == nullptr || n_trees == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set)
+    if (!e->rows_set)
         return fail(e, TW_ERR_STATE, "tw_stitch_traces before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
     if (use_truth) {
         if (e->truth == nullptr) return fail(e, TW_ERR_STATE, "tw_stitch_traces(use_truth) before tw_set_truth");
     } else {
-        const bool ok = (pass == 0 && e->parents_given) || (pass == 1 && (e->state == ST_PASS1 || e->state == ST_MIX)) || (pass == 2 && e->state == ST_PASS2);
-        if (!ok) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
+        if (!(pass == 0 && e->parents_given) && !pass_resident(e, pass)) return fail(e, TW_ERR_STATE, "tw_stitch_traces: the results of that pass are not resident (pass 0: tw_set_parents first)");
     }
     HIPCHK(hipSetDevice(e->device));
-    e->stitched = false; e->attributed = false; e->dist_ready = false; e->sig_ready = false;
+    drop_forest(e);
     const StitchDev& S = e->S;
     const bool has_truth = e->truth != nullptr;
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
-    const dim3 rows((unsigned)((S.n_rows + threads - 1) / threads)), tb(threads);
+    const unsigned threads = flat_threads(e);
+    const dim3 rows(flat_grid(S.n_rows, threads)), tb(threads);
     HIPCHK(hipMemsetAsync(S.totals, 0, sizeof(unsigned long long) * 4, e->stream));
     HIPCHK(hipMemsetAsync(S.err, 0, sizeof(int32_t), e->stream));
-    HIPCHK(hipEventRecord(e->st_ev[0], e->stream));
-    int rounds = 0, rc;
+    HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH], e->stream));
+    int rounds = 0;
     if (has_truth && !use_truth) {   // the true forest first: what bit 2 of the flags compares with
-        rc = stitch_forest(e, e->truth, S.true_root, nullptr, false, nullptr, &rounds);
-        if (rc != TW_OK) return rc;
-        HIPCHK(hipEventRecord(e->st_ev[0], e->stream));   // (timed: the stitch of the assignment alone)
+        TWCHK(stitch_forest(e, e->truth, S.true_root, nullptr, false, nullptr, &rounds));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH], e->stream));   // (timed: the stitch of the assignment alone)
     }
-    rc = stitch_forest(e, use_truth ? e->truth : (pass == 0 ? e->given_parent : e->P.parent), S.root, S.depth, true, (has_truth && !use_truth) ? S.true_root : nullptr, &rounds);
-    if (rc != TW_OK) return rc;
+    TWCHK(stitch_forest(e, use_truth ? e->truth : (pass == 0 ? e->given_parent : e->P.parent), S.root, S.depth, true, (has_truth && !use_truth) ? S.true_root : nullptr, &rounds));
     const int64_t n_chunks = (S.n_rows + (int64_t)threads * kStitchScanItems - 1) / ((int64_t)threads * kStitchScanItems);
     hipLaunchKernelGGL(k_stitch_scan_sums, dim3((unsigned)n_chunks), tb, 0, e->stream, S);
     hipLaunchKernelGGL(k_stitch_scan_chunks, dim3(1), tb, 0, e->stream, S, n_chunks);
     hipLaunchKernelGGL(k_stitch_scan_write, dim3((unsigned)n_chunks), tb, 0, e->stream, S);
     hipLaunchKernelGGL(k_stitch_scatter, rows, tb, 0, e->stream, S);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->st_ev[3], e->stream));
-    // one wavefront per kStitchTrees trees, persistent: at most 8192 workgroups of four
-    const unsigned gthreads = e->coop >= 64 ? 64u * kStitchWaves : (unsigned)e->coop;
-    const int64_t want = (S.n_rows / kStitchTrees + 1 + kStitchWaves - 1) / kStitchWaves;
-    hipLaunchKernelGGL(k_stitch_group, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, has_truth ? 1 : 0);
+    HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH + 3], e->stream));
+    const WaveShape group = wave_shape(e, S.n_rows, kStitchTrees, kStitchWaves);   // (the trees are not counted yet: as if every row were one)
+    hipLaunchKernelGGL(k_stitch_group, group.grid, group.block, 0, e->stream, S, has_truth ? 1 : 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->st_ev[4], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH + 4], e->stream));
     unsigned long long totals[4] = {0, 0, 0, 0};
     int32_t err = 0;
     HIPCHK(hipMemcpyAsync(totals, S.totals, sizeof(totals), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(&err, S.err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (err != 0) return fail(e, TW_ERR_ARG, "tw_stitch_traces: the links hold a cycle (a row is its own ancestor): malformed row_link / row maps");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[0], e->st_ev[4])); e->st_ms[0] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[0], e->st_ev[1])); e->st_ms[1] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[1], e->st_ev[2])); e->st_ms[2] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[2], e->st_ev[3])); e->st_ms[3] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->st_ev[3], e->st_ev[4])); e->st_ms[4] = ms;
+    TWCHK(stage_elapsed(e, SE_STITCH, 0, 4, &e->st_ms[0]));
+    for (int i = 1; i <= 4; i++) TWCHK(stage_elapsed(e, SE_STITCH, i - 1, i, &e->st_ms[i]));
     e->st_ms[5] = (double)rounds;
     const int64_t nt = (int64_t)(totals[0] >> 32);
     *n_trees = nt;
@@ -2135,15 +2168,13 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
         counts4[0] = (int64_t)totals[1]; counts4[1] = nt - (int64_t)totals[1]; counts4[2] = (int64_t)totals[2];
         counts4[3] = has_truth ? (int64_t)totals[3] : -1;
     }
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-    D2H(out->root, S.root, sizeof(int32_t) * (size_t)S.n_rows);
-    D2H(out->depth, S.depth, sizeof(int32_t) * (size_t)S.n_rows);
-    D2H(out->tree_off, S.tree_off, sizeof(int64_t) * (size_t)(nt + 1));
-    D2H(out->tree_rows, S.tree_rows, sizeof(int32_t) * (size_t)S.n_rows);
-    D2H(out->tree_root, S.tree_root, sizeof(int32_t) * (size_t)nt);
-    D2H(out->tree_latency, S.tree_latency, sizeof(int64_t) * (size_t)nt);
-    D2H(out->tree_flags, S.tree_flags, (size_t)nt);
-#undef D2H
+    TWCHK(copy_out(e, out->root, S.root, S.n_rows));
+    TWCHK(copy_out(e, out->depth, S.depth, S.n_rows));
+    TWCHK(copy_out(e, out->tree_off, S.tree_off, nt + 1));
+    TWCHK(copy_out(e, out->tree_rows, S.tree_rows, S.n_rows));
+    TWCHK(copy_out(e, out->tree_root, S.tree_root, nt));
+    TWCHK(copy_out(e, out->tree_latency, S.tree_latency, nt));
+    TWCHK(copy_out(e, out->tree_flags, S.tree_flags, nt));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->stitched = true; e->st_trees = nt;
     e->stitched_pass = use_truth ? -1 : pass; e->stitched_truth = has_truth;
@@ -2153,68 +2184,56 @@ int tw_stitch_traces(tw_engine* e, int pass, int use_truth, const tw_stitched* o
 /* ---- latency attribution on the stitched forest (tw_attr.h) ------------------------------------------------------- */
 int tw_set_row_groups(tw_engine* e, int32_t n_groups, const int32_t* row_group) {
     if (e == nullptr || row_group == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_groups before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
+    if (!e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_groups before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
     if (n_groups < 1) return fail(e, TW_ERR_ARG, "tw_set_row_groups: n_groups must be positive");
     const int64_t n_rows = e->S.n_rows;
     for (int64_t r = 0; r < n_rows; r++)   // k_attr_reduce indexes the totals with these values
         if (row_group[r] < -1 || row_group[r] >= n_groups) return fail(e, TW_ERR_ARG, "tw_set_row_groups: row_group outside [-1, n_groups)");
     HIPCHK(hipSetDevice(e->device));
-    e->attributed = false; e->dist_ready = false;   // (the per-row flags of the last attribution name the old groups)
-    e->sig_ready = false; e->ref_set = false;       // (... and the signatures, the reference set's among them)
+    drop_groups(e);   // (the per-row flags of the last attribution name the old groups, and so do the signatures, the reference set's among them)
     AttrDev& A = e->A;
-    int rc;
-#define AALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
     if (A.self_time == nullptr || n_rows > e->attr_rows_cap) {   // (freed with the batch)
         int32_t* group_d;
-        AALLOC(group_d, n_rows); A.row_group = group_d;
-        AALLOC(A.self_time, n_rows); AALLOC(A.path_time, n_rows); AALLOC(A.row_tree, n_rows); AALLOC(A.row_flag, n_rows);
-        AALLOC(A.tree_top, n_rows); AALLOC(A.tree_path_rows, n_rows); AALLOC(A.tree_sel, n_rows);
-        AALLOC(A.key_a, n_rows); AALLOC(A.key_b, n_rows); AALLOC(A.val_a, n_rows); AALLOC(A.val_b, n_rows);
-        AALLOC(A.counters, 4); AALLOC(A.err, 1);
+        DEV_ALLOC(group_d, n_rows); A.row_group = group_d;
+        DEV_ALLOC(A.self_time, n_rows); DEV_ALLOC(A.path_time, n_rows); DEV_ALLOC(A.row_tree, n_rows); DEV_ALLOC(A.row_flag, n_rows);
+        DEV_ALLOC(A.tree_top, n_rows); DEV_ALLOC(A.tree_path_rows, n_rows); DEV_ALLOC(A.tree_sel, n_rows);
+        DEV_ALLOC(A.key_a, n_rows); DEV_ALLOC(A.key_b, n_rows); DEV_ALLOC(A.val_a, n_rows); DEV_ALLOC(A.val_b, n_rows);
+        DEV_ALLOC(A.counters, 4); DEV_ALLOC(A.err, 1);
         e->attr_rows_cap = n_rows;
     }
     if (A.totals == nullptr || n_groups > e->groups_cap) {
-        AALLOC(A.totals, (int64_t)kAttrCols * n_groups);
+        DEV_ALLOC(A.totals, (int64_t)kAttrCols * n_groups);
         e->groups_cap = n_groups;
     }
-#undef AALLOC
     A.n_groups = n_groups;
     HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(A.row_group), row_group, sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 4; i++)
-        if (e->at_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->at_ev[i]));
     e->groups_set = true;
     return TW_OK;
 }
 
 int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attribution* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
-        return fail(e, TW_ERR_STATE, "tw_attribute_traces needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    TWCHK(need_forest(e, "tw_attribute_traces"));
     if (!e->groups_set) return fail(e, TW_ERR_STATE, "tw_attribute_traces before tw_set_row_groups (dropped with the row maps)");
     if (!(q->percentile >= 0.0 && q->percentile < 1.0)) return fail(e, TW_ERR_ARG, "tw_attribute_traces: percentile outside [0, 1)");
     if (q->start_min > q->start_max) return fail(e, TW_ERR_ARG, "tw_attribute_traces: start_min > start_max");
     HIPCHK(hipSetDevice(e->device));
-    e->attributed = false; e->dist_ready = false;
+    drop_attribution(e);
     const StitchDev& S = e->S;
     AttrDev& A = e->A;
     const int64_t nt = e->st_trees, G = A.n_groups;
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
-    const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), rows((unsigned)((S.n_rows + threads - 1) / threads));
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads), trees(flat_grid(nt, threads)), rows(flat_grid(S.n_rows, threads));
     AttrQueryDev Q{q->start_min, q->start_max, 0, q->need_flags, q->skip_flags};
     // selection: eligible trees in order of (latency, tree), those of rank >= k inside the start window
     HIPCHK(hipMemsetAsync(A.counters, 0, sizeof(unsigned long long) * 4, e->stream));
     HIPCHK(hipMemsetAsync(A.err, 0, sizeof(int32_t), e->stream));
     HIPCHK(hipMemsetAsync(A.totals, 0, sizeof(unsigned long long) * (size_t)(kAttrCols * G), e->stream));
-    HIPCHK(hipEventRecord(e->at_ev[0], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_ATTR + 0], e->stream));
     hipLaunchKernelGGL(k_attr_flags, trees, tb, 0, e->stream, S, A, Q, nt);
     HIPCHK(hipGetLastError());
-    size_t bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream));
-    int rc = ensure_sort_tmp(e, bytes);
-    if (rc != TW_OK) return rc;
-    bytes = e->sort_tmp_bytes;
-    HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream));
+    TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream); }));
     unsigned long long counters[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(counters, A.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -2222,23 +2241,19 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
     Q.k = (int64_t)(q->percentile * (double)n_eligible);   // int(0.95 * len(...)) of the reference, in binary64
     hipLaunchKernelGGL(k_attr_mark, trees, tb, 0, e->stream, S, A, Q, nt, n_eligible);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->at_ev[1], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_ATTR + 1], e->stream));
     if (big_rows > A.big_cap) {   // tables of the trees that outgrow a wavefront's LDS (freed with the batch)
-#define AALLOC(ptr) do { rc = dev_alloc(e, &(ptr), big_rows); if (rc != TW_OK) return rc; } while (0)
-        AALLOC(A.g_s); AALLOC(A.g_e); AALLOC(A.g_s2); AALLOC(A.g_e2);
-        AALLOC(A.g_row); AALLOC(A.g_par); AALLOC(A.g_rank); AALLOC(A.g_row2); AALLOC(A.g_par2);
-#undef AALLOC
+        DEV_ALLOC(A.g_s, big_rows); DEV_ALLOC(A.g_e, big_rows); DEV_ALLOC(A.g_s2, big_rows); DEV_ALLOC(A.g_e2, big_rows); DEV_ALLOC(A.g_row, big_rows);
+        DEV_ALLOC(A.g_par, big_rows); DEV_ALLOC(A.g_rank, big_rows); DEV_ALLOC(A.g_row2, big_rows); DEV_ALLOC(A.g_par2, big_rows);
         A.big_cap = big_rows;
     }
-    // one wavefront per kAttrTrees trees, persistent: at most 8192 workgroups of four
-    const unsigned gthreads = e->coop >= 64 ? 64u * kAttrWaves : (unsigned)e->coop;
-    const int64_t want = (nt / kAttrTrees + 1 + kAttrWaves - 1) / kAttrWaves;
-    hipLaunchKernelGGL(k_attr_tree, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, A, nt);
+    const WaveShape per_tree = wave_shape(e, nt, kAttrTrees, kAttrWaves);
+    hipLaunchKernelGGL(k_attr_tree, per_tree.grid, per_tree.block, 0, e->stream, S, A, nt);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->at_ev[2], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_ATTR + 2], e->stream));
     hipLaunchKernelGGL(k_attr_reduce, rows, tb, 0, e->stream, S, A);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->at_ev[3], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_ATTR + 3], e->stream));
     std::vector<unsigned long long> totals((size_t)(kAttrCols * G));
     unsigned long long key_k = 1ull << 63;
     int32_t err = 0;
@@ -2249,10 +2264,9 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
     HIPCHK(hipStreamSynchronize(e->stream));
     if (err == TW_ERR_DEVICE) return fail(e, TW_ERR_DEVICE, "tw_attribute_traces: the tables of the large trees are smaller than the trees");
     if (err != 0) return fail(e, TW_ERR_ARG, "tw_attribute_traces: a row is linked to a row outside its tree: not the forest tw_stitch_traces left behind");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[1], e->at_ev[2])); e->at_ms[0] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[0], e->at_ev[1])); e->at_ms[1] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->at_ev[2], e->at_ev[3])); e->at_ms[2] = ms;
+    TWCHK(stage_elapsed(e, SE_ATTR, 1, 2, &e->at_ms[0]));
+    TWCHK(stage_elapsed(e, SE_ATTR, 0, 1, &e->at_ms[1]));
+    TWCHK(stage_elapsed(e, SE_ATTR, 2, 3, &e->at_ms[2]));
     if (summary != nullptr) {
         int64_t culprit = -1;   // the group with the largest path time among those with a row on a selected path; ties: the smallest id
         for (int64_t g = 0; g < G; g++)
@@ -2261,14 +2275,12 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
         summary[3] = (int64_t)(key_k ^ (1ull << 63)); summary[4] = culprit; summary[5] = nt;
     }
     if (out != nullptr) {
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-        D2H(out->link, S.link, sizeof(int32_t) * (size_t)S.n_rows);
-        D2H(out->self_time, A.self_time, sizeof(int64_t) * (size_t)S.n_rows);
-        D2H(out->path_time, A.path_time, sizeof(int64_t) * (size_t)S.n_rows);
-        D2H(out->tree_top_group, A.tree_top, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_selected, A.tree_sel, (size_t)nt);
-        D2H(out->tree_path_rows, A.tree_path_rows, sizeof(int32_t) * (size_t)nt);
-#undef D2H
+        TWCHK(copy_out(e, out->link, S.link, S.n_rows));
+        TWCHK(copy_out(e, out->self_time, A.self_time, S.n_rows));
+        TWCHK(copy_out(e, out->path_time, A.path_time, S.n_rows));
+        TWCHK(copy_out(e, out->tree_top_group, A.tree_top, nt));
+        TWCHK(copy_out(e, out->tree_selected, A.tree_sel, nt));
+        TWCHK(copy_out(e, out->tree_path_rows, A.tree_path_rows, nt));
         HIPCHK(hipStreamSynchronize(e->stream));
         int64_t* cols[kAttrCols] = {out->group_path_time, out->group_path_rows, out->group_self_time, out->group_span_time, out->group_span_rows,
                                     out->group_trees, out->group_top_trees};
@@ -2283,11 +2295,7 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
 /* ---- which of the reconstructed traces can be trusted (tw_conf.h) -------------------------------------------------- */
 namespace {
 
-bool pass_resident(const tw_engine* e, int pass) {
-    return (pass == 1 && (e->state == ST_PASS1 || e->state == ST_MIX)) || (pass == 2 && e->state == ST_PASS2);
-}
-
-// rank, list_n and margin of the resident pass into e->C (freed with the batch); cf_ev[0] .. cf_ev[1] around the kernel
+// rank, list_n and margin of the resident pass into e->C (freed with the batch); the first two events of SE_CONF around the kernel
 int conf_decisions(tw_engine* e) {
     const Dev& P = e->P;
     ConfDev& C = e->C;
@@ -2299,12 +2307,10 @@ int conf_decisions(tw_engine* e) {
             return rc;
         }
     }
-    for (int i = 0; i < 4; i++)
-        if (e->cf_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->cf_ev[i]));
-    HIPCHK(hipEventRecord(e->cf_ev[0], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 0], e->stream));
     hipLaunchKernelGGL(k_conf_requests, dim3((unsigned)P.n_tiles), dim3((unsigned)e->tile), 0, e->stream, P, C);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->cf_ev[1], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 1], e->stream));
     return TW_OK;
 }
 
@@ -2314,25 +2320,19 @@ int tw_get_decisions(tw_engine* e, int pass, int32_t* rank, int32_t* list_n, dou
     if (e == nullptr) return TW_ERR_ARG;
     if (!pass_resident(e, pass)) return fail(e, TW_ERR_STATE, "tw_get_decisions: the results of that pass are not resident");
     HIPCHK(hipSetDevice(e->device));
-    const int rc = conf_decisions(e);
-    if (rc != TW_OK) return rc;
+    TWCHK(conf_decisions(e));
     const ConfDev& C = e->C;
     const size_t n = (size_t)e->P.n_in_total;
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-    D2H(rank, C.rank, sizeof(int32_t) * n);
-    D2H(list_n, C.list_n, sizeof(int32_t) * n);
-    D2H(margin, C.margin, sizeof(double) * n);
-#undef D2H
+    TWCHK(copy_out(e, rank, C.rank, n));
+    TWCHK(copy_out(e, list_n, C.list_n, n));
+    TWCHK(copy_out(e, margin, C.margin, n));
     HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[0], e->cf_ev[1])); e->cf_ms[0] = ms;
-    return TW_OK;
+    return stage_elapsed(e, SE_CONF, 0, 1, &e->cf_ms[0]);
 }
 
 int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
-        return fail(e, TW_ERR_STATE, "tw_score_traces needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    TWCHK(need_forest(e, "tw_score_traces"));
     if (e->stitched_pass != 1 && e->stitched_pass != 2)
         return fail(e, TW_ERR_STATE, "tw_score_traces: the forest was stitched from tw_set_parents or from the truth: it holds no decisions of this engine");
     if (!pass_resident(e, e->stitched_pass)) return fail(e, TW_ERR_STATE, "tw_score_traces: the pass the forest was stitched from is no longer resident");
@@ -2351,38 +2351,29 @@ int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* o
     const StitchDev& S = e->S;
     ConfDev& C = e->C;
     const int64_t nt = e->st_trees;
-    int rc;
     if (C.row_request == nullptr || S.n_rows > e->conf_rows_cap) {   // (freed with the batch)
-#define CALLOC(ptr) do { rc = dev_alloc(e, &(ptr), S.n_rows); if (rc != TW_OK) return rc; } while (0)
-        CALLOC(C.row_request); CALLOC(C.decisions); CALLOC(C.not_best); CALLOC(C.unassigned); CALLOC(C.weakest_row);
-        CALLOC(C.min_margin); CALLOC(C.confident);
-#undef CALLOC
+        DEV_ALLOC(C.row_request, S.n_rows); DEV_ALLOC(C.decisions, S.n_rows); DEV_ALLOC(C.not_best, S.n_rows); DEV_ALLOC(C.unassigned, S.n_rows);
+        DEV_ALLOC(C.weakest_row, S.n_rows); DEV_ALLOC(C.min_margin, S.n_rows); DEV_ALLOC(C.confident, S.n_rows);
         e->conf_rows_cap = S.n_rows;
     }
-    rc = conf_decisions(e);
-    if (rc != TW_OK) return rc;
-    e->sig_ready = false;   // (the CONFIDENT bit of the flags is rewritten: the eligible trees of a resident signature result may change)
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
-    const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), reqs((unsigned)((P.n_in_total + threads - 1) / threads));
+    TWCHK(conf_decisions(e));
+    drop_sig(e);   // (the CONFIDENT bit of the flags is rewritten: the eligible trees of a resident signature result may change)
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads), trees(flat_grid(nt, threads)), reqs(flat_grid(P.n_in_total, threads));
     HIPCHK(hipMemsetAsync(C.row_request, 0xff, sizeof(int32_t) * (size_t)S.n_rows, e->stream));
     hipLaunchKernelGGL(k_conf_scatter, reqs, tb, 0, e->stream, S, C, P.n_in_total);
-    // one wavefront per kConfTrees trees, persistent: at most 8192 workgroups of four
-    const unsigned gthreads = e->coop >= 64 ? 64u * kConfWaves : (unsigned)e->coop;
-    const int64_t want = (nt / kConfTrees + 1 + kConfWaves - 1) / kConfWaves;
-    hipLaunchKernelGGL(k_conf_trees, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, C, Q, nt);
+    const WaveShape per_tree = wave_shape(e, nt, kConfTrees, kConfWaves);
+    hipLaunchKernelGGL(k_conf_trees, per_tree.grid, per_tree.block, 0, e->stream, S, C, Q, nt);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->cf_ev[2], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 2], e->stream));
     HIPCHK(hipMemsetAsync(C.cells, 0, sizeof(unsigned long long) * kConfCells, e->stream));
     hipLaunchKernelGGL(k_conf_calib, trees, tb, 0, e->stream, S, C, Q, nt);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->cf_ev[3], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 3], e->stream));
     unsigned long long cells[kConfCells];
     HIPCHK(hipMemcpyAsync(cells, C.cells, sizeof(cells), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[0], e->cf_ev[1])); e->cf_ms[0] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[1], e->cf_ev[2])); e->cf_ms[1] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->cf_ev[2], e->cf_ev[3])); e->cf_ms[2] = ms;
+    for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_CONF, i, i + 1, &e->cf_ms[i]));
     if (summary != nullptr)
         for (int k = 0; k < 5; k++) summary[k] = (int64_t)cells[(kConfMaxEdges + 2) * kConfCalibCols + k];
     if (out != nullptr) {
@@ -2391,18 +2382,16 @@ int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* o
                 for (int c = 0; c < kConfCalibCols; c++)
                     out->calib[b * kConfCalibCols + c] = (c == 1 && !e->stitched_truth) ? -1 : (int64_t)cells[b * kConfCalibCols + c];
         const size_t n = (size_t)P.n_in_total;
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-        D2H(out->rank, C.rank, sizeof(int32_t) * n);
-        D2H(out->list_n, C.list_n, sizeof(int32_t) * n);
-        D2H(out->margin, C.margin, sizeof(double) * n);
-        D2H(out->row_request, C.row_request, sizeof(int32_t) * (size_t)S.n_rows);
-        D2H(out->tree_decisions, C.decisions, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_not_best, C.not_best, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_unassigned, C.unassigned, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_min_margin, C.min_margin, sizeof(double) * (size_t)nt);
-        D2H(out->tree_weakest_row, C.weakest_row, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_confident, C.confident, (size_t)nt);
-#undef D2H
+        TWCHK(copy_out(e, out->rank, C.rank, n));
+        TWCHK(copy_out(e, out->list_n, C.list_n, n));
+        TWCHK(copy_out(e, out->margin, C.margin, n));
+        TWCHK(copy_out(e, out->row_request, C.row_request, S.n_rows));
+        TWCHK(copy_out(e, out->tree_decisions, C.decisions, nt));
+        TWCHK(copy_out(e, out->tree_not_best, C.not_best, nt));
+        TWCHK(copy_out(e, out->tree_unassigned, C.unassigned, nt));
+        TWCHK(copy_out(e, out->tree_min_margin, C.min_margin, nt));
+        TWCHK(copy_out(e, out->tree_weakest_row, C.weakest_row, nt));
+        TWCHK(copy_out(e, out->tree_confident, C.confident, nt));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     return TW_OK;
@@ -2411,7 +2400,7 @@ int tw_score_traces(tw_engine* e, const tw_conf_query* q, const tw_confidence* o
 /* ---- per-service latency distributions and cohorts (tw_dist.h) ----------------------------------------------------- */
 int tw_set_row_cohorts(tw_engine* e, int32_t n_cohorts, const int32_t* row_cohort) {
     if (e == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_cohorts before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
+    if (!e->rows_set) return fail(e, TW_ERR_STATE, "tw_set_row_cohorts before tw_set_span_rows (tw_load_batch and tw_scale_load drop the row maps)");
     if (n_cohorts < 1) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: n_cohorts must be positive");
     if (row_cohort == nullptr && n_cohorts != 1) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: no labels with n_cohorts != 1");
     const int64_t n_rows = e->S.n_rows;
@@ -2420,15 +2409,11 @@ int tw_set_row_cohorts(tw_engine* e, int32_t n_cohorts, const int32_t* row_cohor
             if (row_cohort[r] < -1 || row_cohort[r] >= n_cohorts) return fail(e, TW_ERR_ARG, "tw_set_row_cohorts: row_cohort outside [-1, n_cohorts)");
     HIPCHK(hipSetDevice(e->device));
     DistDev& D = e->D;
-    e->dist_ready = false;
-    if (row_cohort == nullptr) {   // back to one cohort that holds every tree
-        e->cohorts_set = false;
-        return TW_OK;
-    }
+    drop_cohorts(e);
+    if (row_cohort == nullptr) return TW_OK;   // back to one cohort that holds every tree
     if (D.row_cohort == nullptr || n_rows > e->cohort_rows_cap) {   // (freed with the batch)
         int32_t* label_d;
-        const int rc = dev_alloc(e, &label_d, n_rows);
-        if (rc != TW_OK) return rc;
+        DEV_ALLOC(label_d, n_rows);
         D.row_cohort = label_d;
         e->cohort_rows_cap = n_rows;
     }
@@ -2447,7 +2432,7 @@ int dist_bits(unsigned long long x) {   // bits needed to write x
     return b;
 }
 
-// Cohorts, counts, items, sort, offsets and values of the resident attribution into e->D; ds_ev[0] .. ds_ev[2] around the two halves.
+// Cohorts, counts, items, sort, offsets and values of the resident attribution into e->D; the first three events of SE_DIST around the two halves.
 int dist_build(tw_engine* e) {
     const StitchDev& S = e->S;
     const AttrDev& A = e->A;
@@ -2455,28 +2440,24 @@ int dist_build(tw_engine* e) {
     const int64_t nt = e->st_trees;
     if (!e->cohorts_set) { D.row_cohort = nullptr; D.n_cohorts = 1; }
     D.n_seg = (int64_t)D.n_cohorts * (3 * (int64_t)A.n_groups + 1);
-    int rc;
-#define DALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
-    if (D.counters == nullptr) DALLOC(D.counters, kDistCounters);   // (all of them freed with the batch)
-    if (D.tree_cohort == nullptr || nt > e->dist_trees_cap) { DALLOC(D.tree_cohort, nt); e->dist_trees_cap = nt; }
+    if (D.counters == nullptr) DEV_ALLOC(D.counters, kDistCounters);   // (all of them freed with the batch)
+    if (D.tree_cohort == nullptr || nt > e->dist_trees_cap) { DEV_ALLOC(D.tree_cohort, nt); e->dist_trees_cap = nt; }
     if (D.seg_count == nullptr || D.n_seg > e->dist_seg_cap) {
-        DALLOC(D.seg_count, D.n_seg); DALLOC(D.seg_sum, D.n_seg); DALLOC(D.seg_off, D.n_seg + 1);
+        DEV_ALLOC(D.seg_count, D.n_seg); DEV_ALLOC(D.seg_sum, D.n_seg); DEV_ALLOC(D.seg_off, D.n_seg + 1);
         e->dist_seg_cap = D.n_seg;
     }
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const unsigned threads = flat_threads(e);
     const dim3 tb(threads);
     // workgroups stride over the rows: at most 2048 of them clear and add up an LDS table
-    const dim3 rows((unsigned)std::min<int64_t>((S.n_rows + threads - 1) / threads, 2048));
+    const dim3 rows(std::min(flat_grid(S.n_rows, threads), 2048u));
     unsigned long long counters[kDistCounters] = {0, ~0ull, 0, 0, 0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(D.counters, counters, sizeof(counters), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemsetAsync(D.seg_count, 0, sizeof(unsigned long long) * (size_t)D.n_seg, e->stream));
     HIPCHK(hipMemsetAsync(D.seg_sum, 0, sizeof(unsigned long long) * (size_t)D.n_seg, e->stream));
-    HIPCHK(hipEventRecord(e->ds_ev[0], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 0], e->stream));
     if (D.row_cohort != nullptr) {
-        // one wavefront per kDistTrees trees, persistent: at most 8192 workgroups of four
-        const unsigned gthreads = e->coop >= 64 ? 64u * kDistWaves : (unsigned)e->coop;
-        const int64_t want = (nt / kDistTrees + 1 + kDistWaves - 1) / kDistWaves;
-        hipLaunchKernelGGL(k_dist_cohort, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, D, nt);
+        const WaveShape per_tree = wave_shape(e, nt, kDistTrees, kDistWaves);
+        hipLaunchKernelGGL(k_dist_cohort, per_tree.grid, per_tree.block, 0, e->stream, S, D, nt);
     } else {
         HIPCHK(hipMemsetAsync(D.tree_cohort, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(nt, 1), e->stream));
     }
@@ -2493,46 +2474,35 @@ int dist_build(tw_engine* e) {
         K.wide = seg_bits + K.vbits > 64 ? 1 : 0;
     }
     if (D.key_a == nullptr || n_items > D.items_cap) {
-        DALLOC(D.key_a, n_items); DALLOC(D.key_b, n_items); DALLOC(D.values, n_items);
+        DEV_ALLOC(D.key_a, n_items); DEV_ALLOC(D.key_b, n_items); DEV_ALLOC(D.values, n_items);
         D.seg_a = nullptr; D.seg_b = nullptr;
         D.items_cap = std::max<int64_t>(n_items, 1);
     }
-    if (K.wide && D.seg_a == nullptr) { DALLOC(D.seg_a, D.items_cap); DALLOC(D.seg_b, D.items_cap); }
-#undef DALLOC
+    if (K.wide && D.seg_a == nullptr) { DEV_ALLOC(D.seg_a, D.items_cap); DEV_ALLOC(D.seg_b, D.items_cap); }
     if (n_items > 0) hipLaunchKernelGGL(k_dist_items<true>, rows, tb, 0, e->stream, S, A, D, K);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ds_ev[1], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 1], e->stream));
     const unsigned long long* sorted = D.key_a;
     if (n_items > 0 && !K.wide) {
         const unsigned end_bit = (unsigned)std::max(seg_bits + K.vbits, 1);
-        size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, D.key_a, D.key_b, (size_t)n_items, 0u, end_bit, e->stream));
-        rc = ensure_sort_tmp(e, bytes);
-        if (rc != TW_OK) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::radix_sort_keys(e->sort_tmp, bytes, D.key_a, D.key_b, (size_t)n_items, 0u, end_bit, e->stream));
+        TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys(tmp, bytes, D.key_a, D.key_b, (size_t)n_items, 0u, end_bit, e->stream); }));
         sorted = D.key_b;
-    } else if (n_items > 0) {   // stable: by value, then by segment
-        size_t bytes = 0, bytes2 = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.key_a, D.key_b, D.seg_a, D.seg_b, (size_t)n_items, 0u, (unsigned)K.vbits, e->stream));
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes2, D.seg_b, D.seg_a, D.key_b, D.key_a, (size_t)n_items, 0u, (unsigned)seg_bits, e->stream));
-        rc = ensure_sort_tmp(e, std::max(bytes, bytes2));
-        if (rc != TW_OK) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.key_a, D.key_b, D.seg_a, D.seg_b, (size_t)n_items, 0u, (unsigned)K.vbits, e->stream));
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.seg_b, D.seg_a, D.key_b, D.key_a, (size_t)n_items, 0u, (unsigned)seg_bits, e->stream));
+    } else if (n_items > 0) {   // stable: by value, then by segment (the temporary is sized for both before the first is queued)
+        auto by_value = [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, D.key_a, D.key_b, D.seg_a, D.seg_b, (size_t)n_items, 0u, (unsigned)K.vbits, e->stream); };
+        auto by_segment = [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, D.seg_b, D.seg_a, D.key_b, D.key_a, (size_t)n_items, 0u, (unsigned)seg_bits, e->stream); };
+        size_t bytes2 = 0;
+        HIPCHK(by_segment(nullptr, bytes2));
+        TWCHK(rocprim_call(e, by_value, bytes2));
+        TWCHK(rocprim_call(e, by_segment));
     }
     hipLaunchKernelGGL(k_dist_scan, dim3(1), tb, 0, e->stream, D);
-    if (n_items > 0) hipLaunchKernelGGL(k_dist_unpack, dim3((unsigned)((n_items + threads - 1) / threads)), tb, 0, e->stream, D, K, sorted, n_items);
+    if (n_items > 0) hipLaunchKernelGGL(k_dist_unpack, dim3(flat_grid(n_items, threads)), tb, 0, e->stream, D, K, sorted, n_items);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ds_ev[2], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 2], e->stream));
     HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (counters[7] != 0 || (int64_t)counters[6] != n_items) return fail(e, TW_ERR_DEVICE, "tw_latency_distributions: the two sweeps over the rows disagree on the number of items");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[0], e->ds_ev[1])); e->ds_ms[0] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[1], e->ds_ev[2])); e->ds_ms[1] = ms;
+    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, SE_DIST, i, i + 1, &e->ds_ms[i]));
     const int32_t* labels = e->D.row_cohort;
     const int32_t n_cohorts = e->D.n_cohorts;
     e->D = D;
@@ -2547,7 +2517,7 @@ int dist_build(tw_engine* e) {
 
 int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_distributions* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set || !e->stitched || !e->groups_set || !e->attributed)
+    if (!e->attributed)
         return fail(e, TW_ERR_STATE, "tw_latency_distributions needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
                                      "whatever drops the forest drop the attribution)");
     if (q->n_q < 0 || q->n_q > kDistMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, "tw_latency_distributions: n_q outside [0, 32]");
@@ -2567,41 +2537,35 @@ int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_dist
     const int64_t n_seg = (int64_t)(e->cohorts_set ? e->D.n_cohorts : 1) * (3 * (int64_t)e->A.n_groups + 1);
     if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_latency_distributions: more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
     HIPCHK(hipSetDevice(e->device));
-    for (int i = 0; i < 5; i++)
-        if (e->ds_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->ds_ev[i]));
-    int rc;
-    if (!e->dist_ready && (rc = dist_build(e)) != TW_OK) return rc;
+    if (!e->dist_ready) TWCHK(dist_build(e));
     DistDev& D = e->D;
     const int64_t nt = e->st_trees, n_items = e->dist_items;
     const int bins = Q.n_edges + 1;
     const bool want_q = out != nullptr && out->quantile != nullptr && Q.n_q > 0, want_h = out != nullptr && out->hist != nullptr;
     if ((want_q || want_h) && (D.quant == nullptr || n_seg > e->dist_out_cap)) {   // room for any query on these segments (freed with the batch)
-        if ((rc = dev_alloc(e, &D.quant, n_seg * kDistMaxQ)) != TW_OK || (rc = dev_alloc(e, &D.hist, n_seg * (kDistMaxEdges + 1))) != TW_OK) return rc;
+        DEV_ALLOC(D.quant, n_seg * kDistMaxQ); DEV_ALLOC(D.hist, n_seg * (kDistMaxEdges + 1));
         e->dist_out_cap = n_seg;
     }
-    const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
+    const unsigned threads = flat_threads(e);
     const dim3 tb(threads);
-    HIPCHK(hipEventRecord(e->ds_ev[3], e->stream));
-    if (want_q) hipLaunchKernelGGL(k_dist_quantiles, dim3((unsigned)((n_seg * Q.n_q + threads - 1) / threads)), tb, 0, e->stream, D, Q);
-    if (want_h) hipLaunchKernelGGL(k_dist_hist, dim3((unsigned)((n_seg * bins + threads - 1) / threads)), tb, 0, e->stream, D, Q);
+    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 3], e->stream));
+    if (want_q) hipLaunchKernelGGL(k_dist_quantiles, dim3(flat_grid(n_seg * Q.n_q, threads)), tb, 0, e->stream, D, Q);
+    if (want_h) hipLaunchKernelGGL(k_dist_hist, dim3(flat_grid(n_seg * bins, threads)), tb, 0, e->stream, D, Q);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ds_ev[4], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 4], e->stream));
     unsigned long long counters[kDistCounters];
     HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
     if (out != nullptr) {
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-        D2H(out->tree_cohort, D.tree_cohort, sizeof(int32_t) * (size_t)nt);
-        D2H(out->seg_count, D.seg_count, sizeof(int64_t) * (size_t)n_seg);
-        D2H(out->seg_sum, D.seg_sum, sizeof(int64_t) * (size_t)n_seg);
-        D2H(out->seg_off, D.seg_off, sizeof(int64_t) * (size_t)(n_seg + 1));
-        D2H(out->values, D.values, sizeof(int64_t) * (size_t)n_items);
-        if (want_q) D2H(out->quantile, D.quant, sizeof(int64_t) * (size_t)(n_seg * Q.n_q));
-        if (want_h) D2H(out->hist, D.hist, sizeof(int64_t) * (size_t)(n_seg * bins));
-#undef D2H
+        TWCHK(copy_out(e, out->tree_cohort, D.tree_cohort, nt));
+        TWCHK(copy_out(e, out->seg_count, D.seg_count, n_seg));
+        TWCHK(copy_out(e, out->seg_sum, D.seg_sum, n_seg));
+        TWCHK(copy_out(e, out->seg_off, D.seg_off, n_seg + 1));
+        TWCHK(copy_out(e, out->values, D.values, n_items));
+        if (want_q) TWCHK(copy_out(e, out->quantile, D.quant, n_seg * Q.n_q));
+        if (want_h) TWCHK(copy_out(e, out->hist, D.hist, n_seg * bins));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->ds_ev[3], e->ds_ev[4])); e->ds_ms[2] = ms;
+    TWCHK(stage_elapsed(e, SE_DIST, 3, 4, &e->ds_ms[2]));
     if (summary != nullptr) {
         summary[0] = n_items; summary[1] = (int64_t)counters[5]; summary[2] = (int64_t)counters[3]; summary[3] = (int64_t)counters[4];
     }
@@ -2611,8 +2575,7 @@ int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_dist
 /* ---- traces grouped by call-graph signature (tw_sig.h) --------------------------------------------------------------- */
 int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
-    if (e->state < ST_LOADED || !e->rows_set || !e->stitched)
-        return fail(e, TW_ERR_STATE, "tw_trace_signatures needs the forest of a tw_stitch_traces call (a load, tw_scale_load, new row maps and a new pass drop it)");
+    TWCHK(need_forest(e, "tw_trace_signatures"));
     if (!e->groups_set) return fail(e, TW_ERR_STATE, "tw_trace_signatures before tw_set_row_groups (dropped with the row maps)");
     if (q->mode != 0 && q->mode != 1) return fail(e, TW_ERR_ARG, "tw_trace_signatures: mode outside {0 levels, 1 edges}");
     if ((int64_t)e->A.n_groups > ((int64_t)1 << kSigGroupBits)) return fail(e, TW_ERR_UNSUPPORTED, "tw_trace_signatures: more than 2^20 groups (the packed key holds 20 bits of group)");
@@ -2625,68 +2588,52 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
     const int64_t nt = e->st_trees, n_rows = S.n_rows;
     const bool same_query = e->sig_ready && e->sig_q.mode == q->mode && e->sig_q.need_flags == q->need_flags && e->sig_q.skip_flags == q->skip_flags &&
                             (e->sig_q.keep_reference != 0) == (q->keep_reference != 0) && (e->sig_q.compare != 0) == (q->compare != 0);
-    int rc;
     if (!same_query) {
-        e->sig_ready = false;
-        for (int i = 0; i < 4; i++)
-            if (e->sg_ev[i] == nullptr) HIPCHK(hipEventCreate(&e->sg_ev[i]));
-#define GALLOC(ptr, count) do { rc = dev_alloc(e, &(ptr), (count)); if (rc != TW_OK) return rc; } while (0)
-        if (D.counters == nullptr) GALLOC(D.counters, kSigCounters);   // (all of them freed with the batch)
+        drop_sig(e);
+        if (D.counters == nullptr) DEV_ALLOC(D.counters, kSigCounters);   // (all of them freed with the batch)
         if (D.key_a == nullptr || n_rows > e->sig_rows_cap) {
-            GALLOC(D.row_level, n_rows); GALLOC(D.key_a, n_rows); GALLOC(D.key_b, n_rows); GALLOC(D.ent_cnt, n_rows);
-            GALLOC(D.big_begin, n_rows / kSigCap + 1); GALLOC(D.big_end, n_rows / kSigCap + 1);
+            DEV_ALLOC(D.row_level, n_rows); DEV_ALLOC(D.key_a, n_rows); DEV_ALLOC(D.key_b, n_rows); DEV_ALLOC(D.ent_cnt, n_rows);
+            DEV_ALLOC(D.big_begin, n_rows / kSigCap + 1); DEV_ALLOC(D.big_end, n_rows / kSigCap + 1);
             e->sig_rows_cap = n_rows;
         }
         if (D.hkey_a == nullptr || nt > e->sig_trees_cap) {
-            GALLOC(D.hkey_a, nt); GALLOC(D.hkey_b, nt); GALLOC(D.val_a, nt); GALLOC(D.val_b, nt); GALLOC(D.tree_ent, nt); GALLOC(D.rep, nt);
-            GALLOC(D.tree_class, nt); GALLOC(D.tree_items, nt); GALLOC(D.elig, nt); GALLOC(D.tree_same, nt); GALLOC(D.chunk_sum, nt / kSigScanItems + 2);
-            GALLOC(D.class_rep, nt); GALLOC(D.class_trees, nt); GALLOC(D.class_sum, nt); GALLOC(D.class_min, nt); GALLOC(D.class_max, nt);
-            GALLOC(D.class_off, nt + 1);
+            DEV_ALLOC(D.hkey_a, nt); DEV_ALLOC(D.hkey_b, nt); DEV_ALLOC(D.val_a, nt); DEV_ALLOC(D.val_b, nt); DEV_ALLOC(D.tree_ent, nt); DEV_ALLOC(D.rep, nt);
+            DEV_ALLOC(D.tree_class, nt); DEV_ALLOC(D.tree_items, nt); DEV_ALLOC(D.elig, nt); DEV_ALLOC(D.tree_same, nt); DEV_ALLOC(D.chunk_sum, nt / kSigScanItems + 2);
+            DEV_ALLOC(D.class_rep, nt); DEV_ALLOC(D.class_trees, nt); DEV_ALLOC(D.class_sum, nt); DEV_ALLOC(D.class_min, nt); DEV_ALLOC(D.class_max, nt);
+            DEV_ALLOC(D.class_off, nt + 1);
             e->sig_trees_cap = nt;
         }
         if (q->keep_reference != 0 && (D.ref_key == nullptr || n_rows > e->sig_ref_cap)) {
-            GALLOC(D.ref_key, n_rows); GALLOC(D.ref_cnt, n_rows); GALLOC(D.ref_n, n_rows); GALLOC(D.ref_pos, n_rows);
+            DEV_ALLOC(D.ref_key, n_rows); DEV_ALLOC(D.ref_cnt, n_rows); DEV_ALLOC(D.ref_n, n_rows); DEV_ALLOC(D.ref_pos, n_rows);
             e->sig_ref_cap = n_rows;
-            e->ref_set = false;
+            drop_ref(e);   // (new arrays: the set in the old ones is out of reach)
         }
         D.mode = q->mode; D.hash_bits = e->sig_hash_bits; D.need_flags = q->need_flags; D.skip_flags = q->skip_flags;
         D.row_group = e->A.row_group;
-        const unsigned threads = (unsigned)(e->coop >= 64 ? 256 : e->coop);
-        const dim3 tb(threads), trees((unsigned)((nt + threads - 1) / threads)), rows((unsigned)((n_rows + threads - 1) / threads));
+        const unsigned threads = flat_threads(e);
+        const dim3 tb(threads), trees(flat_grid(nt, threads)), rows(flat_grid(n_rows, threads));
         unsigned long long counters[kSigCounters] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIPCHK(hipMemsetAsync(D.counters, 0, sizeof(counters), e->stream));
-        HIPCHK(hipEventRecord(e->sg_ev[0], e->stream));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_SIG + 0], e->stream));
         hipLaunchKernelGGL(k_sig_items, rows, tb, 0, e->stream, S, D);
         hipLaunchKernelGGL(k_sig_trees, trees, tb, 0, e->stream, S, D, nt);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->sg_ev[1], e->stream));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_SIG + 1], e->stream));
         HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         if (counters[3] != 0) return fail(e, TW_ERR_UNSUPPORTED, "tw_trace_signatures: a server row lies 2^16 or more levels deep (the packed key holds 16 bits of level)");
         const int64_t n_big = (int64_t)counters[2];
         if (n_big > 0) {   // the trees beyond a wavefront's LDS table: sorted before k_sig_sign reads them
-            size_t bytes = 0;
-            HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, bytes, (const unsigned long long*)D.key_a, D.key_b, (unsigned)n_rows, (unsigned)n_big, D.big_begin,
-                                                      D.big_end, 0u, 64u, e->stream));
-            rc = ensure_sort_tmp(e, bytes);
-            if (rc != TW_OK) return rc;
-            bytes = e->sort_tmp_bytes;
-            HIPCHK(rocprim::segmented_radix_sort_keys(e->sort_tmp, bytes, (const unsigned long long*)D.key_a, D.key_b, (unsigned)n_rows, (unsigned)n_big, D.big_begin,
-                                                      D.big_end, 0u, 64u, e->stream));
+            TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) {
+                return rocprim::segmented_radix_sort_keys(tmp, bytes, (const unsigned long long*)D.key_a, D.key_b, (unsigned)n_rows, (unsigned)n_big, D.big_begin,
+                                                          D.big_end, 0u, 64u, e->stream);
+            }));
         }
-        {   // one wavefront per kSigTrees trees, persistent: at most 8192 workgroups of four
-            const unsigned gthreads = e->coop >= 64 ? 64u * kSigWaves : (unsigned)e->coop;
-            const int64_t want = (nt / kSigTrees + 1 + kSigWaves - 1) / kSigWaves;
-            hipLaunchKernelGGL(k_sig_sign, dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(gthreads), 0, e->stream, S, D, nt);
-        }
+        const WaveShape per_tree = wave_shape(e, nt, kSigTrees, kSigWaves);
+        hipLaunchKernelGGL(k_sig_sign, per_tree.grid, per_tree.block, 0, e->stream, S, D, nt);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->sg_ev[2], e->stream));
-        size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream));
-        rc = ensure_sort_tmp(e, bytes);
-        if (rc != TW_OK) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(rocprim::radix_sort_pairs(e->sort_tmp, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_SIG + 2], e->stream));
+        TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream); }));
         hipLaunchKernelGGL(k_sig_rep, trees, tb, 0, e->stream, S, D, nt);
         const int64_t n_chunks = (nt + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
         hipLaunchKernelGGL(k_sig_scan_sums, dim3((unsigned)n_chunks), tb, 0, e->stream, D, nt);
@@ -2697,28 +2644,24 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
         HIPCHK(hipStreamSynchronize(e->stream));
         const int64_t n_classes = (int64_t)(counters[6] >> 32), n_entries = (int64_t)(counters[6] & 0xffffffffull);
         if (D.class_entries == nullptr || n_entries > e->sig_ent_cap) {
-            GALLOC(D.class_entries, 4 * n_entries);
+            DEV_ALLOC(D.class_entries, 4 * n_entries);
             e->sig_ent_cap = std::max<int64_t>(n_entries, 1);
         }
-#undef GALLOC
         hipLaunchKernelGGL(k_sig_classes, trees, tb, 0, e->stream, S, D, nt);
         if (q->compare != 0) hipLaunchKernelGGL(k_sig_compare, trees, tb, 0, e->stream, S, D, nt);
         else HIPCHK(hipMemsetAsync(D.tree_same, 0xff, (size_t)nt, e->stream));
         if (q->keep_reference != 0) {   // (after the comparison: a call with both compares with the set it replaces)
-            e->ref_set = false;
+            drop_ref(e);
             HIPCHK(hipMemsetAsync(D.ref_n, 0xff, sizeof(int32_t) * (size_t)n_rows, e->stream));
             HIPCHK(hipMemcpyAsync(D.ref_key, D.key_a, sizeof(unsigned long long) * (size_t)n_rows, hipMemcpyDeviceToDevice, e->stream));
             HIPCHK(hipMemcpyAsync(D.ref_cnt, D.ent_cnt, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, e->stream));
             hipLaunchKernelGGL(k_sig_keep, trees, tb, 0, e->stream, S, D, nt);
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->sg_ev[3], e->stream));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_SIG + 3], e->stream));
         HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[0], e->sg_ev[1])); e->sg_ms[0] = ms;
-        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[1], e->sg_ev[2])); e->sg_ms[1] = ms;
-        HIPCHK(hipEventElapsedTime(&ms, e->sg_ev[2], e->sg_ev[3])); e->sg_ms[2] = ms;
+        for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_SIG, i, i + 1, &e->sg_ms[i]));
         e->sig_summary[0] = (int64_t)counters[0]; e->sig_summary[1] = n_classes; e->sig_summary[2] = (int64_t)counters[1]; e->sig_summary[3] = n_entries;
         e->sig_summary[4] = q->compare != 0 ? (int64_t)counters[4] : -1; e->sig_summary[5] = q->compare != 0 ? (int64_t)counters[5] : -1;
         if (q->keep_reference != 0) { e->ref_set = true; e->ref_mode = q->mode; }
@@ -2729,19 +2672,17 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
         for (int k = 0; k < 6; k++) summary[k] = e->sig_summary[k];
     if (out != nullptr) {
         const size_t nc = (size_t)e->sig_summary[1], ne = (size_t)e->sig_summary[3];
-#define D2H(dst, src, bytes) if ((dst) != nullptr) HIPCHK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, e->stream))
-        D2H(out->row_level, D.row_level, sizeof(int32_t) * (size_t)n_rows);
-        D2H(out->tree_class, D.tree_class, sizeof(int32_t) * (size_t)nt);
-        D2H(out->tree_items, D.tree_items, sizeof(int64_t) * (size_t)nt);
-        D2H(out->tree_same, D.tree_same, (size_t)nt);
-        D2H(out->class_rep, D.class_rep, sizeof(int32_t) * nc);
-        D2H(out->class_trees, D.class_trees, sizeof(int64_t) * nc);
-        D2H(out->class_latency_sum, D.class_sum, sizeof(int64_t) * nc);
-        D2H(out->class_latency_min, D.class_min, sizeof(int64_t) * nc);
-        D2H(out->class_latency_max, D.class_max, sizeof(int64_t) * nc);
-        D2H(out->class_off, D.class_off, sizeof(int64_t) * (nc + 1));
-        if (ne > 0) D2H(out->class_entries, D.class_entries, sizeof(int32_t) * 4 * ne);
-#undef D2H
+        TWCHK(copy_out(e, out->row_level, D.row_level, n_rows));
+        TWCHK(copy_out(e, out->tree_class, D.tree_class, nt));
+        TWCHK(copy_out(e, out->tree_items, D.tree_items, nt));
+        TWCHK(copy_out(e, out->tree_same, D.tree_same, nt));
+        TWCHK(copy_out(e, out->class_rep, D.class_rep, nc));
+        TWCHK(copy_out(e, out->class_trees, D.class_trees, nc));
+        TWCHK(copy_out(e, out->class_latency_sum, D.class_sum, nc));
+        TWCHK(copy_out(e, out->class_latency_min, D.class_min, nc));
+        TWCHK(copy_out(e, out->class_latency_max, D.class_max, nc));
+        TWCHK(copy_out(e, out->class_off, D.class_off, nc + 1));
+        if (ne > 0) TWCHK(copy_out(e, out->class_entries, D.class_entries, 4 * ne));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     return TW_OK;
@@ -2763,8 +2704,8 @@ int tw_build_distributions(tw_engine* e, int64_t n, const int64_t* start, const 
     if (s == hipSuccess) s = hipMemcpyAsync(d_d, dur, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, e->stream);
     if (s == hipSuccess) s = hipMemcpyAsync(d_e, ep, (size_t)n, hipMemcpyHostToDevice, e->stream);
     if (s == hipSuccess) {
-        const int threads = e->coop >= 64 ? 256 : e->coop;
-        hipLaunchKernelGGL(k_build_distributions, dim3((unsigned)((n + threads - 1) / threads)), dim3((unsigned)threads), 0, e->stream,
+        const unsigned threads = flat_threads(e);
+        hipLaunchKernelGGL(k_build_distributions, dim3(flat_grid(n, threads)), dim3(threads), 0, e->stream,
                            (const int64_t*)d_s, (const int64_t*)d_d, (const uint8_t*)d_e, n, large_delay, (int)E, d_k, d_v);
         s = hipGetLastError();
     }

@@ -111,6 +111,8 @@ struct tw_engine {
     int state = ST_EMPTY;
     int tile = kTile;   // incoming spans (threads) per workgroup of the per-span kernels
     int tile_threads = 2; // threads per incoming span of k_enumerate_tile (its items and tuples are spread over all of them)
+    int tile_single = 1;  // TW_TILE_SINGLE: the one-endpoint class takes the lean path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int tile_single_threads = 1;   // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
     int coop = kCoop;   // threads of the per-unit cooperative kernels
     std::vector<UnitDev> units;
     std::vector<TileDev> tiles;
@@ -486,7 +488,8 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
     if (mode == 0) {
         // cut-offs and work lists, the short enumerations: the tile kernel.  A class of few tiles: several workgroups per tile, until
         // the class fills the CUs twice over
-        const dim3 tile_block(e->tile >= 64 ? e->tile * e->tile_threads : e->tile);
+        const bool single = E == 1 && e->tile_single != 0;
+        const dim3 tile_block(e->tile >= 64 ? e->tile * (single ? e->tile_single_threads : e->tile_threads) : e->tile);
         int sub = 1;
         while (sub < e->tile_sub_max && nt * sub < 512 && (e->tile / (sub * 2)) * (sub * 2) == e->tile && e->tile / (sub * 2) >= 8) sub *= 2;
         // A class of many tiles in stretches: what a stretch's tiles listed for the wavefront kernel is enumerated on the class' second
@@ -499,9 +502,14 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
         for (int j = 0; j < ns; j++) {
             const int t0 = (int)((int64_t)nt * j / ns), t1 = (int)((int64_t)nt * (j + 1) / ns);
             const int32_t* ids = e->tile_ids + e->tile_cls_off[E] + t0;
-            if (e->tile == kTile && e->tile / sub == kSubTileSpans)   // (the instantiation with tables for a sub-tile's 16 spans: a third of the LDS)
+            const bool sub_tile = e->tile == kTile && e->tile / sub == kSubTileSpans;   // (the instantiation with tables for a sub-tile's 16 spans: a third of the LDS)
+            if constexpr (E == 1) {   // (the lean path: instantiated for one endpoint only)
+                if (single && sub_tile) hipLaunchKernelGGL((k_enumerate_tile<1, kSubTileSpans, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
+                else if (single) hipLaunchKernelGGL((k_enumerate_tile<1, kTile, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
+            }
+            if (!single && sub_tile)
                 hipLaunchKernelGGL((k_enumerate_tile<E, kSubTileSpans>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            else
+            else if (!single)
                 hipLaunchKernelGGL((k_enumerate_tile<E>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
             if (ns > 1) {
                 hipLaunchKernelGGL(k_enum_snapshot, dim3(1), dim3(1), 0, st, P, E, j + 1);
@@ -1047,6 +1055,8 @@ int tw_create(int device_id, tw_engine** out) {
     e->device = device_id;
     e->tile = std::min(std::max(env_int("TW_TILE", kTile), 1), kTile);
     e->tile_threads = std::min(std::max(env_int("TW_TILE_THREADS", 2), 1), 4);
+    e->tile_single = env_int("TW_TILE_SINGLE", 1);
+    e->tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
     e->coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
     // The engine runs its endpoint-count classes and window classes on streams of their own (up to 8 + 3 beside its own).  The
     // runtime multiplexes a process' streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default: classes that share a queue run one

@@ -24,12 +24,17 @@ __device__ __forceinline__ void raise_err(const Dev& P, int code) { atomicCAS(P.
 
 // Appends to a work list with one atomic per wavefront instead of one per lane (same-address atomics serialise
 // at ~20 ns each): the first active lane reserves slots for every lane that has an entry.  Returns the slot or -1.
-__device__ __forceinline__ int wave_append(int32_t* counter, bool pred) {
+// (lane_in: the caller's own copy of its lane number, where holding the kernel's across the whole kernel costs a register)
+__device__ __forceinline__ int wave_append(int32_t* counter, bool pred, int lane_in = -1) {
     const unsigned long long mask = __ballot(pred);
     if (mask == 0) return -1;
-    const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
+    const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63), leader = __ffsll((long long)mask) - 1;
     int base = 0;
     if (lane == leader) base = atomicAdd(counter, __popcll(mask));
+#ifndef TW_HOST_EMULATION
+    if (lane_in >= 0) base = __builtin_amdgcn_readlane(base, leader);   // (the leader is the same for all: no shuffle, which would want the kernel's lane number again)
+    else
+#endif
     base = __shfl(base, leader);
     return pred ? base + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
 }
@@ -310,7 +315,8 @@ __device__ __forceinline__ double term_gauss(double mean, double used, double lo
 
 // not inlined: the mixture term is ~1.5k instructions and is called from several places per kernel; keeping one
 // copy keeps the enumeration kernels inside the instruction cache
-__device__ __noinline__ double term_mix(int n, const double* c, double x) {
+// (term_mix_inline: the body, for a kernel that holds itself to 64 registers -- a call leaves it sixteen registers that survive it)
+__device__ __forceinline__ double term_mix_inline(int n, const double* c, double x) {
     // the per-component terms stay in registers (an array indexed by the loop counter would live in scratch memory:
     // one store and two loads per component and call); k < kMaxComp = 5
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, amax = -dinf();
@@ -329,6 +335,7 @@ __device__ __noinline__ double term_mix(int n, const double* c, double x) {
     if (s != 0.0) s = s / m;
     return (tw_log1p(s) + (m == 1.0 ? 0.0 : tw_log(m))) + amax;  // log(1.0) is exactly 0.0
 }
+__device__ __noinline__ double term_mix(int n, const double* c, double x) { return term_mix_inline(n, c, x); }
 
 __device__ __forceinline__ double score_term(const Scorer& S, int slot, int64_t t1, int64_t t2) {
     const double x = (double)(t2 - t1);
@@ -462,7 +469,7 @@ constexpr int kDeferPrefixes = TW_DEFER_PREFIXES, kDeferPrefixGrain = TW_DEFER_P
 constexpr long long kDeferListPerSpan = 64, kDeferListMin = 1ll << 22;   // entries of the arena per incoming span of the deferring classes / at least
 template <int E>
 __device__ __forceinline__ bool heavy_append(const Dev& P, bool pred, bool narrow, bool big, int unit, int i, long long prod = 0, int first_cands = 0,
-                                             bool twins = false) {
+                                             bool twins = false, int lane = -1) {
     const bool isbig = pred && big;   // narrow or wide windows: the list entry says which instantiation takes it
     const int wide_flag = (narrow ? 0 : 1 << 24) | ((twins && P.split_twins == 2) ? kPartLogFlag : 0);
     int nparts = 1, slot_base = 0;
@@ -478,9 +485,9 @@ __device__ __forceinline__ bool heavy_append(const Dev& P, bool pred, bool narro
     }
     const bool split = nparts > 1;
     if (pred && !narrow) P.any_wide[E] = 1;   // (every writer stores the same value)
-    const int sb = wave_append(&P.heavy_big_count[E], isbig && !split);
-    const int sn = wave_append(&P.heavy_in_count[E], pred && narrow && !big);
-    const int sw = wave_append(&P.heavy_in_count[kMaxEp + 1 + E], pred && !narrow && !big);
+    const int sb = wave_append(&P.heavy_big_count[E], isbig && !split, lane);
+    const int sn = wave_append(&P.heavy_in_count[E], pred && narrow && !big, lane);
+    const int sw = wave_append(&P.heavy_in_count[kMaxEp + 1 + E], pred && !narrow && !big, lane);
     if (!pred) return false;
     if (split) {
         const int base = P.heavy_big_off[E] + atomicAdd(&P.heavy_big_count[E], nparts);
@@ -1839,12 +1846,12 @@ __device__ __forceinline__ double lane_value(double v, int j) { return __longlon
 // list.sort(reverse=True) of a few (score, tuple) entries under Python's order `lt` -- a strict partial order (tuples whose first
 // differing spans start together are incomparable), so the steps of CPython's sort are followed one by one: reverse, count_run +
 // binary insertion, reverse.
-template <class LT>
-__device__ __forceinline__ void py_sort_desc(double* hs, unsigned long long* hx, int n, const LT& lt) {
+template <class X, class LT>   // X: the tuples as the caller keeps them (8-bit positions per endpoint in 64 bits; a byte for a single endpoint)
+__device__ __forceinline__ void py_sort_desc(double* hs, X* hx, int n, const LT& lt) {
     auto reverse = [&](int m) {
         for (int i = 0, j = m - 1; i < j; i++, j--) {
             const double a = hs[i]; hs[i] = hs[j]; hs[j] = a;
-            const unsigned long long b = hx[i]; hx[i] = hx[j]; hx[j] = b;
+            const X b = hx[i]; hx[i] = hx[j]; hx[j] = b;
         }
     };
     if (n < 2) return;
@@ -1858,7 +1865,7 @@ __device__ __forceinline__ void py_sort_desc(double* hs, unsigned long long* hx,
     }
     for (int start = run; start < n; start++) {
         int l = 0, r = start;
-        const double ps = hs[start]; const unsigned long long px = hx[start];
+        const double ps = hs[start]; const X px = hx[start];
         do {
             const int p = l + ((r - l) >> 1);
             if (lt(ps, px, hs[p], hx[p])) r = p; else l = p + 1;

@@ -78,6 +78,15 @@ __device__ __forceinline__ uint32_t div_small(uint32_t rest, uint32_t c) {
     return (uint32_t)(((float)rest + 0.5f) * rc);
 }
 
+// the value, as one the compiler takes for new: addresses formed from it are formed where they are used, not ahead of a loop and
+// held in registers through it
+__device__ __forceinline__ int fresh(int v) {
+#ifndef TW_HOST_EMULATION
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
 // a term from the gap itself (score_term computes x = (double)(t2 - t1) and then exactly this)
 __device__ __forceinline__ double score_term_gap(const Scorer& S, int slot, long long gap) {
     const double x = (double)gap;
@@ -112,10 +121,12 @@ __device__ __forceinline__ double score_term_gap(const Scorer& S, int slot, long
 #ifdef TW_HOST_EMULATION
 #define TW_TILE_ATTR
 #else
-#define TW_TILE_ATTR __attribute__((amdgpu_waves_per_eu(E <= 4 ? 4 : 2)))
+#define TW_TILE_ATTR __attribute__((amdgpu_waves_per_eu(SINGLE ? 8 : (E <= 4 ? 4 : 2))))
 #endif
-template <int E, int SPANS = kTile>
+// SINGLE (one endpoint only): a tuple is an item -- the lean path below, TW_TILE_SINGLE=0 launches the general one instead
+template <int E, int SPANS = kTile, bool SINGLE = false>
 __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P, int pass, const int32_t* tile_ids, int n_tiles_e, int sub_tiles) {
+    static_assert(!SINGLE || E == 1, "the lean path is the one of a single endpoint");
     if (*P.err != 0) return;  // e.g. NaN parameters (hazard H3): nothing downstream is meaningful
     typedef TileCfg<E, SPANS> C;
     constexpr int SL = C::kSlice;
@@ -315,27 +326,29 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
             const int rel = lo[e] - s_A[e], c = some ? __popcll((unsigned long long)cm[e]) : 0;
             s_lo[e][t] = (uint16_t)(some ? rel : 0);
             s_cm[e][t] = some ? cm[e] : 0u;
-            s_bits[e][t] = 0u;
+            if constexpr (!SINGLE) s_bits[e][t] = 0u;
             nitem += c;
             cnpack |= (unsigned long long)c << (8 * e);
         }
-        s_cn[t] = cnpack;
         s_is[t] = (int32_t)iso; s_ie[t] = (int32_t)ieo;
-        s_leaves[t] = (some && !ordered) ? (int)prod : 0; s_amb[t] = 0;
+        s_amb[t] = 0;
+        if constexpr (!SINGLE) { s_cn[t] = cnpack; s_leaves[t] = (some && !ordered) ? (int)prod : 0; }
     }
     {   // inclusive prefix sums of the items and of the tuple slots (a span's slots padded to a multiple of four: the rank
         // loop reads four scores a step) over the spans: wavefront scans by shuffles, then the wavefronts' totals through LDS
-        int a = live ? nitem : 0, b = (live && some) ? (((int)prod + 3) & ~3) : 0;
+        // (a single endpoint: the items are the tuples, one prefix sum)
+        int a = live ? nitem : 0, b = (!SINGLE && live && some) ? (((int)prod + 3) & ~3) : 0;
         const int lane = t & 63, wv = t >> 6;
         for (int off = 1; off < 64; off <<= 1) {
-            const int a2 = __shfl_up(a, off), b2 = __shfl_up(b, off);
-            if (lane >= off) { a += a2; b += b2; }
+            const int a2 = __shfl_up(a, off);
+            if (lane >= off) a += a2;
+            if constexpr (!SINGLE) { const int b2 = __shfl_up(b, off); if (lane >= off) b += b2; }
         }
-        if (lane == 63 || t == nt - 1) { s_wtot[wv][0] = a; s_wtot[wv][1] = b; }
+        if (lane == 63 || t == nt - 1) { s_wtot[wv][0] = a; if constexpr (!SINGLE) s_wtot[wv][1] = b; }
         group_sync();
-        for (int w = 0; w < wv; w++) { a += s_wtot[w][0]; b += s_wtot[w][1]; }
-        if (live) { s_item0[t + 1] = a; s_grid0[t + 1] = b; }
-        if (t == 0) { s_item0[0] = 0; s_grid0[0] = 0; }
+        for (int w = 0; w < wv; w++) { a += s_wtot[w][0]; if constexpr (!SINGLE) b += s_wtot[w][1]; }
+        if (live) { s_item0[t + 1] = a; if constexpr (!SINGLE) s_grid0[t + 1] = b; }
+        if (t == 0) { s_item0[0] = 0; if constexpr (!SINGLE) s_grid0[0] = 0; }
         group_sync();
     }
     TW_TILE_TICK(2);
@@ -364,6 +377,145 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
             ix[e] = it_idx[kx[e]];
         }
     };
+    // ---- a single endpoint: a tuple is an item.  No tuple slots, no decoding, one score per item in the reference's order of additions
+    // ((0.0 + root) + closing, as phase 4 forms it), the rank counted among the span's own items; 13 KB of LDS instead of 31 ---------
+    if constexpr (SINGLE) {
+        __shared__ double s_sc[C::kItems];                     // the item's score
+        __shared__ uint8_t it_span[C::kItems], it_rank[C::kItems];   // its span (tile-local), its rank
+        // (what a span's thread needs again after the scores -- its mask, its window's place in the slice, whether the span is this
+        // kernel's -- is read back from LDS where it is needed: held in registers through the term it would not fit 64 of them)
+        __shared__ uint8_t s_mine[SPANS];
+        const bool is_root = dag_np[0] == 0;
+        if (live) s_mine[t] = mine ? 1 : 0;
+        for (int seg = 0; seg < ns;) {
+            if (t == 0) { s_segend = fresh(ns); s_anyamb = 0; }   // (fresh: a copy of the constant made here, not kept from before the loop)
+            group_sync();
+            const int tq = fresh(t);
+            if (live && t >= seg && s_item0[tq + 1] - s_item0[seg] > C::kItems) atomicMin(&s_segend, t);
+            group_sync();
+            const int send = s_segend;
+            const int it0 = s_item0[seg], nIt = s_item0[send] - it0;
+            const bool here = live && t >= seg && t < send;
+            const int ks = (live ? s_item0[tq] : 0) - it0;   // the first item of this thread's span, the items (= tuples) it has
+            const int nitem1 = live ? s_item0[tq + 1] - s_item0[tq] : 0;
+            TW_TILE_TICK(2);
+            TW_TILE_COUNT(9, 1); TW_TILE_COUNT(10, nIt); TW_TILE_COUNT(11, nIt);
+            // the span's thread names its items: span and slice position (contained candidates in list order)
+            if (here) {
+                int k = ks;
+                const int rel0 = s_lo[0][tq];
+                for (uint32_t m = s_cm[0][tq]; m != 0; m &= m - 1, k++) { it_span[k] = (uint8_t)t; it_idx[k] = (uint16_t)(rel0 + __ffs((int)m) - 1); }
+            }
+            group_sync();
+            // ---- 3 + 4. the tuple's score, one item per lane ---------------------------------------------------------------
+            for (int k = t; k < nIt; k += nt) {
+                const int s = it_span[k], idx = it_idx[k];
+                S.gp = P.gparam + (U.gp_off + (int64_t)((first + s) / P.batch_size) * U.nslot) * 4;
+                // (0.0 + root) + closing: one copy of the term in the kernel, inlined, run for the root and for the closing gap
+                double sj = 0.0;
+#pragma unroll 1
+                for (int h = is_root ? 0 : 1; h < 2; h++) {
+                    const int slot = h == 0 ? slot_root(E, 0) : slot_close(E, 0);
+                    const double x = (double)(h == 0 ? (long long)sl_st[0][idx] - s_is[s] : (long long)s_ie[s] - sl_en[0][idx]);
+                    double term;
+                    if (pass == 1) { const double* g = S.gp + slot * 4; term = term_gauss(g[0], g[3], g[2], x); }
+                    else {
+                        const int n = S.mix_n[slot];
+                        const double* c = S.mix_c + (int64_t)slot * kMaxComp * 4;
+                        term = n <= 0 ? term_gauss(c[0], c[1], c[2], x) : term_mix_inline(n, c, x);
+                    }
+                    sj += term;
+                }
+                s_sc[k] = sj;
+            }
+            group_sync();
+            TW_TILE_TICK(3);
+            TW_TILE_TICK(4);
+            // ---- 5. rank of every item among the items of its span: the greater scores; on equal scores Python compares the
+            // candidates' start_mus -- equal starts: an incomparable partner, the span is undecided (a NaN score ranks nowhere) -----
+            for (int k = t; k < nIt; k += nt) {
+                const double my = s_sc[k];
+                int rank = kTopK;
+                if (my == my) {
+                    const int s = it_span[k];
+                    const int hs0 = s_item0[s] - it0, he = s_item0[s + 1] - it0;
+                    const int32_t a = sl_st[0][it_idx[k]];
+                    rank = 0;
+                    bool partner = false;
+                    for (int h = hs0; h < he && rank < kTopK; h++) {
+                        const double o = s_sc[h];
+                        if (o > my) rank++;
+                        else if (o == my && h != k) {
+                            const int32_t b = sl_st[0][it_idx[h]];
+                            if (b > a) rank++;
+                            else if (b == a) partner = true;
+                        }
+                    }
+                    if (partner && rank < kTopK) { s_amb[s] = 1; s_anyamb = 1; }
+                }
+                it_rank[k] = (uint8_t)(rank < kTopK ? rank : kTopK);
+            }
+            group_sync();
+            TW_TILE_TICK(5);
+            // ---- results: the items of rank < 5 write themselves ------------------------------------------------------------
+            for (int k = t; k < nIt; k += nt) {
+                if (it_rank[k] >= kTopK) continue;
+                const int s = it_span[k];
+                if (s_amb[s]) continue;
+                const int r = it_rank[k], si = first + s;
+                P.tk_score[tks_index(U, r, si)] = s_sc[k];
+                P.tk_idx[tk_index(U, r, 0, si)] = s_A[0] + (int)it_idx[k];
+            }
+            // ---- 5b. an undecided span: CPython's heap over the span's items in list order by the span's own thread, in registers;
+            // when every thread has read its scores (the barrier) the score and rank tables are free: kTopK + 1 slots of each per
+            // span hold the heap for CPython's list.sort
+            const int tl = fresh(t);
+            const bool replay = s_anyamb != 0 && here && s_mine[tl] && s_amb[tl] && (tl + 1) * (kTopK + 1) <= C::kItems && nitem1 <= kTileReplayMax;
+            auto start_of = [&](int, int pos) -> int32_t { return sl_st[0][it_idx[ks + pos]]; };
+            RegHeap RH;
+            RH.clear(E);
+            if (replay) {
+                for (int pos = 0; pos < nitem1; pos++) {
+                    const double sc = s_sc[ks + pos];
+                    if (!(sc == sc) || RH.below_root(sc)) continue;   // strictly below the root of a full heap: the push leaves the array as it is
+                    RH.push(sc, (unsigned long long)pos, start_of);
+                }
+            }
+            if (s_anyamb != 0) group_sync();   // (the flag is the same for all since the barrier after the ranks)
+            if (replay) {
+                double* hs = s_sc + tl * (kTopK + 1);
+                uint8_t* hx = it_rank + tl * (kTopK + 1);
+#pragma unroll
+                for (int k = 0; k < kTopK; k++) { hs[k] = RH.s[k]; hx[k] = (uint8_t)RH.x[k]; }
+                py_sort_desc(hs, hx, RH.n, [&](double sa, unsigned long long xa, double sb, unsigned long long xb) { return RH.lt(sa, xa, sb, xb, start_of); });
+                const int si = first + tl;
+                for (int k = 0; k < RH.n; k++) {
+                    P.tk_score[tks_index(U, k, si)] = hs[k];
+                    P.tk_idx[tk_index(U, k, 0, si)] = s_A[0] + (int)it_idx[ks + (int)hx[k]];
+                }
+                s_amb[tl] = 0;   // (read again only by this thread: below, and when the tile hands its undecided spans on)
+            }
+            if (here && s_mine[tl] && !s_amb[tl]) {
+                const int i1 = first + tl;
+                const int64_t g = U.in_off + i1;
+                P.tk_n[g] = nitem1 < kTopK ? nitem1 : kTopK;
+                P.leaves[g] = nitem1;
+                if (pass == 1) P.leaves0[g] = nitem1;
+                P.rep[g] = 0;
+                if (pass == 1) {
+                    P.c_bits[ie_index(U, 0, i1) * kCandWords] = (uint64_t)s_cm[0][tl];
+                    for (int w = 1; w < kCandWords; w++) P.c_bits[ie_index(U, 0, i1) * kCandWords + w] = (uint64_t)(uint32_t)fresh(0);
+                }
+            }
+            group_sync();
+            TW_TILE_TICK(6);
+            seg = send;
+        }
+        TW_TILE_FLUSH();
+        const int te = fresh(t);
+        heavy_append<E>(P, live && s_mine[te] != 0 && s_amb[te] != 0, true, false, T.unit, first + (live ? te : 0), 0, 0, false, te & 63);   // (as below)
+        return;
+    } else
     // ---- segments of the tile: as many spans as the tables hold ------------------------------------------------------
     for (int seg = 0; seg < ns;) {
         if (t == 0) { s_segend = ns; s_anyamb = 0; }

@@ -609,6 +609,59 @@ typedef struct {
 } tw_signatures;
 int tw_trace_signatures(tw_engine *e, const tw_sig_query *q, const tw_signatures *out, int64_t *summary6);
 
+/* ---- per-class latency profiles: the aggregate trace of every call-graph class (csrc/tw_prof.h) -------------------
+ *
+ * Replaces: PreparePerCGData (alibaba-analysis/analysis.py:233-292), which works on the traces of one call graph at a time.
+ * tw_trace_signatures says what a trace looks like and gives per class only the latency sum, minimum and maximum;
+ * tw_attribute_traces says where every row spends its time, but adds it up per group over all selected traces.  This is the
+ * join: of the slow traces of one shape, which call at which level is on the critical path, how long it takes and when it
+ * starts -- one node per signature entry, with times.  The call takes no query of its own; it works on what is resident:
+ * the forest of the last stitch, the row groups, the result of the last tw_trace_signatures (its mode, tree_class, class_off,
+ * class_entries) and the last tw_attribute_traces on the same forest (tree_selected, self_time, path_time).
+ *
+ * Definitions (integer microseconds; a row with end < start counts as end = start, as in the attribution):
+ *   counted     tree t is counted when tree_class[t] = c >= 0 and tree_selected[t] != 0: the attribution's selection (the
+ *               slowest X % that started after Y), split by shape.
+ *   items       of a counted tree: its signature items, the server rows with row_group >= 0.  Item row r has the key (level,
+ *               cg, g) of the resident mode; its entry is the one entry j of class c with that key (it exists: t's signature
+ *               is class c's), global entry index i = class_off[c] + j.
+ *   per entry i, over the item rows of the counted trees that map to it (int64 [n_entries], n_entries = summary6[3] of the
+ *   signature call):
+ *     rows                  count
+ *     span_time             sum of the durations
+ *     span_min, span_max    INT64_MAX / INT64_MIN where rows == 0
+ *     self_time, path_time  sums of the attribution's per-row figures
+ *     path_rows             rows on the critical path (the rows tw_attribute_traces counts in group_path_rows)
+ *     path_trees            counted trees with at least one such row at this entry
+ *     offset                sum of start[r] - start[root of t]: where in the trace the entry begins
+ *   invariant   rows[i] == class_entries[i].count * class_counted[c].
+ *   per class (int64 [n_classes], n_classes = summary6[1] of the signature call):
+ *     class_counted         counted trees of the class
+ *     class_latency         sum of tree_latency over them
+ *     class_path_time       sum of path_time over the class' entries
+ *     class_top_entry       the global index of the entry with the largest path_time among those with path_rows > 0 (ties: the
+ *                           smallest index), -1 if there is none
+ *   summary6    counted trees, classes with a counted tree, counted item rows, entries with rows > 0, trees with a class that
+ *               are not selected, selected trees without a class.
+ *
+ * Outputs are caller-allocated, any may be NULL; the sizes are those the signature call returned.  The result stays on the device
+ * until the signature result or the attribution is dropped (and whatever drops either: see both), and a second call only
+ * copies.  The call itself drops nothing: tw_latency_distributions and tw_trace_signatures answer after it what they answered
+ * before.  TW_ERR_STATE: without a resident signature result (before tw_trace_signatures, after tw_score_traces, new row groups
+ * or anything that drops the forest); without a tw_attribute_traces on the current forest.  Both calls have checked their
+ * arguments: there is no other status.
+ * Covers one engine's batch, the selected assignment and one signature query at a time (a tw_trace_signatures call with another
+ * query replaces the result and with it the profile); no quantiles per entry (tw_latency_distributions has them per group).
+ * Results do not depend on scheduling: no floating point; the atomics are integer adds, minima, maxima and exchanges -- of an
+ * exchange only "was this the first" is used, and only to count: which row counts a tree depends on scheduling, the count does
+ * not.  Timing: tw_get_timing slots 28..30 (the sweep over the rows; the per-tree and per-class pass; the copies; HIP events,
+ * ms; those of the last call that did not just copy). */
+typedef struct {
+    int64_t *rows, *span_time, *span_min, *span_max, *self_time, *path_time, *path_rows, *path_trees, *offset;
+    int64_t *class_counted, *class_latency, *class_path_time, *class_top_entry;
+} tw_class_profile;
+int tw_class_profiles(tw_engine *e, const tw_class_profile *out, int64_t *summary6);
+
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,
  * 1 + e = span of outgoing endpoint e), large_delay = the longest incoming span.  Per span: key_out = a * (E + 1) + b

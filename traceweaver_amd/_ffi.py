@@ -108,6 +108,12 @@ class Signatures(ctypes.Structure):
         "class_latency_max", "class_off", "class_entries")]
 
 
+class ClassProfile(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "rows", "span_time", "span_min", "span_max", "self_time", "path_time", "path_rows", "path_trees", "offset",
+        "class_counted", "class_latency", "class_path_time", "class_top_entry")]
+
+
 TW_TREE_CONFIDENT = 8
 TW_CONF_MAX_EDGES = 15
 TW_DIST_MAX_Q = 32
@@ -117,7 +123,7 @@ EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_
            "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
            "tw_assign_service", "tw_find_order", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
-           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_trace_signatures",
+           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_trace_signatures", "tw_class_profiles",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
            "tw_corpus_string", "tw_corpus_loop_origin", "tw_corpus_trace_names", "tw_corpus_span_table", "tw_corpus_build_units"]
 
@@ -179,6 +185,7 @@ def load(path=None):
     lib.tw_set_row_cohorts.argtypes = [vp, ctypes.c_int32, vp]
     lib.tw_latency_distributions.argtypes = [vp, ctypes.POINTER(DistQuery), ctypes.POINTER(Distributions), vp]
     lib.tw_trace_signatures.argtypes = [vp, ctypes.POINTER(SigQuery), ctypes.POINTER(Signatures), vp]
+    lib.tw_class_profiles.argtypes = [vp, ctypes.POINTER(ClassProfile), vp]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]
     lib.tw_host_free.argtypes = [vp]
     lib.tw_host_free.restype = None

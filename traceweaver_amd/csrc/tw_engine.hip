@@ -27,6 +27,7 @@
 #include "tw_conf.h"
 #include "tw_dist.h"
 #include "tw_sig.h"
+#include "tw_prof.h"
 
 using namespace tw;
 
@@ -35,7 +36,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_COUNT = 22 };   // stage events: 5 + 4 + 4 + 5 + 4
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_COUNT = 26 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -185,7 +186,7 @@ struct tw_engine {
     bool scaled_upload = false;             // the batch was uploaded with unit_time_scale (already load-scaled by the caller)
     hipEvent_t ev[EV_COUNT] = {};
     double ms[6] = {0, 0, 0, 0, 0, 0};
-    // The trace stages (tw_set_span_rows .. tw_trace_signatures).  What is resident, what it needs and what drops it: the residency
+    // The trace stages (tw_set_span_rows .. tw_class_profiles).  What is resident, what it needs and what drops it: the residency
     // model below the helpers (drop_*); the flags and capacities here are assigned there and at the one place that makes each resident.
     StitchDev S{};                          // tw_set_span_rows / tw_stitch_traces (tw_stitch.h): row maps, scratch and forest of a stitch
     int32_t* given_parent = nullptr;        // tw_set_parents: an assignment handed over by the caller (stitched as pass 0)
@@ -207,6 +208,9 @@ struct tw_engine {
     tw_sig_query sig_q{};
     int32_t ref_mode = 0, sig_hash_bits = 64;
     int64_t sig_rows_cap = 0, sig_trees_cap = 0, sig_ent_cap = 0, sig_ref_cap = 0, sig_summary[6] = {0, 0, 0, 0, 0, 0};
+    ProfDev F{};                            // tw_class_profiles (tw_prof.h); prof_ready: the profile of the resident signature result and the
+    bool prof_ready = false;                // resident attribution is resident, a further call only copies
+    int64_t prof_ent_cap = 0, prof_cls_cap = 0, prof_rows_cap = 0, prof_summary[6] = {0, 0, 0, 0, 0, 0};
     // HIP events around the parts of a stage (SE_*: a stage's first event; created by tw_create) and what tw_get_timing reports of them
     hipEvent_t stage_ev[SE_COUNT] = {};
     double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
@@ -214,6 +218,7 @@ struct tw_engine {
     double cf_ms[3] = {0, 0, 0};            // decision kernel, row map + per-tree reduction, calibration
     double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
+    double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
 };
 
@@ -321,12 +326,14 @@ int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
        items
      signature        sig_ready      tw_trace_signatures  <- forest, row groups.  Dropped by tw_score_traces (it rewrites the CONFIDENT
        result                                                bit that a query may select by) and by a call with another query
+     class profile    prof_ready     tw_class_profiles    <- signature result, attribution
    An API function drops what it is about to replace with one call, before it overwrites anything, and sets its own flag last, when
    everything has succeeded (tw_trace_signatures owns two items: its result and, with keep_reference, the reference set). */
 void drop_dist(tw_engine* e) { e->dist_ready = false; }
-void drop_sig(tw_engine* e) { e->sig_ready = false; }
+void drop_prof(tw_engine* e) { e->prof_ready = false; }
+void drop_sig(tw_engine* e) { e->sig_ready = false; drop_prof(e); }
 void drop_ref(tw_engine* e) { e->ref_set = false; }
-void drop_attribution(tw_engine* e) { e->attributed = false; drop_dist(e); }
+void drop_attribution(tw_engine* e) { e->attributed = false; drop_dist(e); drop_prof(e); }
 void drop_forest(tw_engine* e) { e->stitched = false; drop_attribution(e); drop_sig(e); }
 void drop_groups(tw_engine* e) { e->groups_set = false; drop_attribution(e); drop_sig(e); drop_ref(e); }
 void drop_cohorts(tw_engine* e) { e->cohorts_set = false; drop_dist(e); }
@@ -340,6 +347,7 @@ void drop_buffers(tw_engine* e) {
     e->C = ConfDev{}; e->conf_rows_cap = 0;                                                            // decisions, confidence
     e->D = DistDev{}; e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;   // cohort labels, items
     e->G = SigDev{}; e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;   // signatures, reference set
+    e->F = ProfDev{}; e->prof_ent_cap = 0; e->prof_cls_cap = 0; e->prof_rows_cap = 0;                  // class profile
 }
 
 bool pass_resident(const tw_engine* e, int pass) {
@@ -1870,6 +1878,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 3 && 19 + i < n; i++) ms[19 + i] = e->cf_ms[i];   // the last tw_score_traces
     for (int i = 0; i < 3 && 22 + i < n; i++) ms[22 + i] = e->ds_ms[i];   // the last tw_latency_distributions
     for (int i = 0; i < 3 && 25 + i < n; i++) ms[25 + i] = e->sg_ms[i];   // the last tw_trace_signatures that ran kernels
+    for (int i = 0; i < 3 && 28 + i < n; i++) ms[28 + i] = e->pf_ms[i];   // the last tw_class_profiles that ran kernels
     return TW_OK;
 }
 
@@ -2693,6 +2702,73 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
         TWCHK(copy_out(e, out->class_latency_max, D.class_max, nc));
         TWCHK(copy_out(e, out->class_off, D.class_off, nc + 1));
         if (ne > 0) TWCHK(copy_out(e, out->class_entries, D.class_entries, 4 * ne));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return TW_OK;
+}
+
+/* ---- per-class latency profiles (tw_prof.h) ----------------------------------------------------------------------------- */
+int tw_class_profiles(tw_engine* e, const tw_class_profile* out, int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (!e->sig_ready)
+        return fail(e, TW_ERR_STATE, "tw_class_profiles needs the result of a tw_trace_signatures call (tw_score_traces, new row groups and whatever drops the "
+                                     "forest drop it)");
+    if (!e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_class_profiles needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
+                                     "whatever drops the forest drop the attribution)");
+    HIPCHK(hipSetDevice(e->device));
+    const StitchDev& S = e->S;
+    ProfDev& P = e->F;
+    const int64_t nt = e->st_trees, n_rows = S.n_rows, nc = e->sig_summary[1], ne = e->sig_summary[3];
+    const bool built = !e->prof_ready;
+    if (built) {
+        if (P.counters == nullptr) DEV_ALLOC(P.counters, kProfCounters);   // (all of them freed with the batch)
+        if (P.cells == nullptr || ne > e->prof_ent_cap) { DEV_ALLOC(P.cells, (int64_t)kProfCols * ne); e->prof_ent_cap = std::max<int64_t>(ne, 1); }
+        if (P.seen == nullptr || n_rows > e->prof_rows_cap) { DEV_ALLOC(P.seen, n_rows); e->prof_rows_cap = n_rows; }
+        if (P.class_counted == nullptr || nc > e->prof_cls_cap) {
+            DEV_ALLOC(P.class_counted, nc); DEV_ALLOC(P.class_latency, nc); DEV_ALLOC(P.class_path_time, nc); DEV_ALLOC(P.class_top, nc);
+            e->prof_cls_cap = std::max<int64_t>(nc, 1);
+        }
+        P.n_entries = ne; P.n_classes = nc;
+        const unsigned threads = flat_threads(e);
+        const dim3 tb(threads);
+        // workgroups stride over the rows: at most 2048 of them clear and add up an LDS table
+        const dim3 sweep(std::min(flat_grid(n_rows, threads), 2048u));
+        HIPCHK(hipMemsetAsync(P.counters, 0, sizeof(unsigned long long) * kProfCounters, e->stream));
+        HIPCHK(hipEventRecord(e->stage_ev[SE_PROF + 0], e->stream));
+        hipLaunchKernelGGL(k_prof_clear, dim3(flat_grid(std::max<int64_t>({(int64_t)kProfCols * ne, n_rows, nc, 1}), threads)), tb, 0, e->stream, S, P);
+        if (n_rows > 0) hipLaunchKernelGGL(k_prof_rows, sweep, tb, 0, e->stream, S, e->A, e->G, P);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->stage_ev[SE_PROF + 1], e->stream));
+        if (nt > 0) hipLaunchKernelGGL(k_prof_trees, dim3(std::min(flat_grid(nt, threads), 2048u)), tb, 0, e->stream, S, e->A, e->G, P, nt);
+        if (nc > 0) hipLaunchKernelGGL(k_prof_classes, dim3(flat_grid(nc, threads)), tb, 0, e->stream, e->G, P);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->stage_ev[SE_PROF + 2], e->stream));
+        unsigned long long counters[kProfCounters];
+        HIPCHK(hipMemcpyAsync(counters, P.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (int k = 0; k < 6; k++) e->prof_summary[k] = (int64_t)counters[k];
+    }
+    if (summary != nullptr)
+        for (int k = 0; k < 6; k++) summary[k] = e->prof_summary[k];
+    if (out != nullptr) {
+        int64_t* cols[kProfCols] = {out->rows, out->span_time, out->span_min, out->span_max, out->self_time, out->path_time, out->path_rows, out->path_trees,
+                                    out->offset};
+        for (int c = 0; c < kProfCols; c++)
+            if (ne > 0) TWCHK(copy_out(e, cols[c], P.cells + (int64_t)c * ne, (size_t)ne));
+        if (nc > 0) {
+            TWCHK(copy_out(e, out->class_counted, P.class_counted, (size_t)nc));
+            TWCHK(copy_out(e, out->class_latency, P.class_latency, (size_t)nc));
+            TWCHK(copy_out(e, out->class_path_time, P.class_path_time, (size_t)nc));
+            TWCHK(copy_out(e, out->class_top_entry, P.class_top, (size_t)nc));
+        }
+    }
+    if (built) {
+        HIPCHK(hipEventRecord(e->stage_ev[SE_PROF + 3], e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_PROF, i, i + 1, &e->pf_ms[i]));
+        e->prof_ready = true;
+    } else if (out != nullptr) {
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     return TW_OK;

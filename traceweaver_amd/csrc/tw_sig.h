@@ -82,17 +82,22 @@ __device__ __forceinline__ unsigned long long sig_mix(unsigned long long x) {   
 }
 __device__ __forceinline__ bool sig_eligible(const SigDev& D, uint32_t f) { return (f & D.need_flags) == D.need_flags && (f & D.skip_flags) == 0; }
 
-__global__ void __launch_bounds__(256) k_sig_items(StitchDev S, SigDev D) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= S.n_rows) return;
-    const int32_t r = S.tree_rows[k];
+// The packed key of a (level, caller group + 1 -- 1 in mode 0 --, group) triple.
+__device__ __forceinline__ unsigned long long sig_pack(int32_t level, unsigned long long c, int32_t g) {
+    return ((unsigned long long)level << (kSigCallerBits + kSigGroupBits)) | (c << kSigGroupBits) | (unsigned long long)g;
+}
+
+// Level and item key of row r (k_sig_items; k_prof_rows of tw_prof.h computes a row's key again with it): kSigNone for a row that is
+// no item; `deep` is set for a server row whose level does not fit the key.
+__device__ __forceinline__ unsigned long long sig_item_key(const StitchDev& S, const SigDev& D, int32_t r, int32_t& level, bool& deep) {
     unsigned long long key = kSigNone;
-    int32_t level = -1;
+    level = -1;
+    deep = false;
     if (S.row_kind[r] == 1) {
         level = S.depth[r] >> 1;   // server rows hang under client rows and client rows under server rows: every other ancestor is one
         const int32_t g = D.row_group[r];
         if (level >= (1 << kSigLevelBits)) {
-            D.counters[3] = 1;
+            deep = true;
         } else if (g >= 0) {
             unsigned long long c = 1;
             if (D.mode == 1) {
@@ -100,9 +105,20 @@ __global__ void __launch_bounds__(256) k_sig_items(StitchDev S, SigDev D) {
                 while (p >= 0 && S.row_kind[p] != 1) p = S.link[p];
                 c = p >= 0 ? (unsigned long long)(D.row_group[p] + 1) : 0ull;
             }
-            key = ((unsigned long long)level << (kSigCallerBits + kSigGroupBits)) | (c << kSigGroupBits) | (unsigned long long)g;
+            key = sig_pack(level, c, g);
         }
     }
+    return key;
+}
+
+__global__ void __launch_bounds__(256) k_sig_items(StitchDev S, SigDev D) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= S.n_rows) return;
+    const int32_t r = S.tree_rows[k];
+    int32_t level;
+    bool deep;
+    const unsigned long long key = sig_item_key(S, D, r, level, deep);
+    if (deep) D.counters[3] = 1;
     D.row_level[r] = level;
     D.key_a[k] = key;
 }

@@ -594,6 +594,7 @@ class Engine(object):
             only = _ffi.Signatures(*([None] * 10 + [_vp(entries)]))
             self._check(self._lib.tw_trace_signatures(self._h, ctypes.byref(q), ctypes.byref(only), None))
         k, c = int(self._n_trees), int(summary[1])
+        self._sig_resident = (m, off[:c + 1].copy(), entries)         # what class_profiles() sizes and labels its result by
         return TraceSignatures(level[:n].copy(), tree_class[:k].copy(), items[:k].copy(), same[:k].copy(), rep[:c].copy(), trees[:c].copy(),
                                lsum[:c].copy(), lmin[:c].copy(), lmax[:c].copy(), off[:c + 1].copy(), entries, summary, m, self._tree_root)
 
@@ -603,6 +604,31 @@ class Engine(object):
         ms = np.zeros(28, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 28))
         return dict(zip(("items", "sort", "classes"), ms[25:28].tolist()))
+
+    def class_profiles(self):
+        """The aggregate trace of every call-graph class (tw_class_profiles): per entry of the last signatures() the rows, durations,
+        self and critical-path times and start offsets over the trees of the class that the last attribute() selected, and per
+        class the counted trees, their latency, the path time and the entry that holds most of it.  Takes no query: it joins the
+        resident signature result with the resident attribution (both on the forest of the last stitch()).  Returns
+        traces.ClassProfiles."""
+        from .traces import ClassProfiles
+
+        mode, off, entries = getattr(self, "_sig_resident", (0, np.zeros(1, dtype=np.int64), np.zeros((0, 4), dtype=np.int32)))
+        nc, ne = len(off) - 1, len(entries)
+        cap = max(int(getattr(self, "_n_rows", 0)), ne, nc, 1)        # (entries and classes never outnumber the rows)
+        arrays = [np.empty(cap, dtype=np.int64) for _ in range(13)]
+        summary = np.zeros(6, dtype=np.int64)
+        out = _ffi.ClassProfile(*[_vp(a) for a in arrays])
+        self._check(self._lib.tw_class_profiles(self._h, ctypes.byref(out), _vp(summary)))
+        return ClassProfiles(*([a[:ne].copy() for a in arrays[:9]] + [a[:nc].copy() for a in arrays[9:]] + [summary]),
+                             class_off=off, class_entries=entries, mode=mode)
+
+    def profiles_timing(self):
+        """The last class_profiles() that ran kernels on the device (HIP events, ms): the sweep over the rows; the per-tree and
+        per-class pass; the copies."""
+        ms = np.zeros(31, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 31))
+        return dict(zip(("sweep", "classes", "copies"), ms[28:31].tolist()))
 
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):

@@ -116,6 +116,12 @@ def parse_args(argv=None):
                          "the true call graph) to this .npz and print the most frequent call graphs.  Needs --stitch_out's conditions")
     ap.add_argument("--signature_mode", type=q, default="levels", choices=("levels", "edges"),
                     help="--signatures_out: levels = the services per level; edges = the caller -> callee edges per level")
+    ap.add_argument("--profiles_out", type=q, default=None,
+                    help="the aggregate trace of every call graph (tw_class_profiles): per entry of the call-graph signatures "
+                         "(--signature_mode) the rows, durations, self and critical-path times and start offsets over the traces of that "
+                         "shape which the delay-culprit query selects (--query_percentile, --query_after), for the predicted and for the "
+                         "true traces; write both to this .npz and print the largest classes with the call that holds most of their "
+                         "critical path.  Needs --stitch_out's conditions")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
                          "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
@@ -175,6 +181,10 @@ def unsupported(args):
         problems.append("--cohort_service without --latency_out")
     if args.signatures_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--signatures_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.profiles_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--profiles_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.profiles_out and not 0.0 <= args.query_percentile < 1.0:
+        problems.append("--query_percentile outside [0, 1)")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--confidence_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.confidence_out and args.fit != "device-batch":
@@ -254,6 +264,8 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         attribute_out(args, eng, st, corpus, table)
     if args.signatures_out:
         signatures_out(args, eng, corpus, table, 2 if solved is not None else 0)
+    if args.profiles_out:
+        profiles_out(args, eng, corpus, table, 2 if solved is not None else 0)
     eng.close()
     if not args.stitch_out:
         return
@@ -292,6 +304,36 @@ def signatures_out(args, eng, corpus, table, pass_, has_truth=True):
         print("  %6d traces, mean %.1f us (min %d, max %d): %s" % (
             row["trees"], row["mean_latency"], row["min_latency"], row["max_latency"],
             " | ".join("L%d %s%s x%d" % (lv, "%s>" % cg if cg is not None else "", g, k) for lv, cg, g, k in row["signature"]) or "(no service)"))
+
+
+def profiles_out(args, eng, corpus, table, pass_, has_truth=True):
+    """--profiles_out: on the true and on the predicted forest stitch -> signatures -> the delay-culprit query -> class profiles;
+    groups by service.  Without ground truth the predicted side alone."""
+    from . import traces
+
+    group, names = traces.groups_from_table(table, corpus)
+    eng.set_row_groups(group, len(names))
+    sides = []
+    for truth in ([True] if has_truth else []) + [False]:
+        if truth:
+            eng.stitch(truth=True)
+        else:
+            eng.stitch(pass_)
+        eng.signatures(args.signature_mode)
+        eng.attribute(percentile=args.query_percentile, start_min=args.query_after)
+        sides.append(eng.class_profiles())
+    pred, true = sides[-1], sides[0] if has_truth else None
+    traces.write_profiles_npz(args.profiles_out, names, pred, true)
+    print("Class profiles (%s): %d traces of %d call graphs counted, %d rows in %d entries%s" % (
+        args.signature_mode, pred.summary[0], pred.summary[1], pred.summary[2], pred.summary[3],
+        "; true traces: %d of %d" % (true.summary[0], true.summary[1]) if true is not None else ""))
+    for row in pred.table([str(x) for x in names])[:3 if not args.verbose else None]:
+        if row["top"] is None:
+            print("  class %d: %d traces, mean %.1f us; no service on the path" % (row["class"], row["counted"], row["mean_latency"]))
+            continue
+        lv, cg, g = row["top"]
+        print("  class %d: %d traces, mean %.1f us; on the path most: L%d %s%s, %.1f %% of the path time, in %.1f %% of the traces" % (
+            row["class"], row["counted"], row["mean_latency"], lv, "%s>" % cg if cg is not None else "", g, 100.0 * row["top_share"], 100.0 * row["top_trees"]))
 
 
 def culprit_line(a, names, head="Delay culprit"):
@@ -535,7 +577,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out:
+            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out or args.profiles_out:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
                            solved=solved)
         else:

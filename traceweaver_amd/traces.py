@@ -22,6 +22,10 @@ tests, `compare_distributions` sets two results side by side (predicted against 
 Engine.signatures (tw_trace_signatures, csrc/tw_sig.h) groups the stitched traces by call-graph signature: `TraceSignatures` is the
 result, `signatures_host` restates the definitions with dictionaries of tuples for the tests, `compare_signatures` cross-checks
 tree_same on the host and gives the share of traces with the true signature, `write_signatures_npz` stores results.
+
+Engine.class_profiles (tw_class_profiles, csrc/tw_prof.h) joins the last two: per class and signature entry the times of the selected
+trees of that shape -- the aggregate trace of a class.  `ClassProfiles` is the result, `class_profiles_host` restates the definitions
+with dictionaries from the host results of `signatures_host` and `attribute_host`, `write_profiles_npz` stores results.
 """
 import sys
 
@@ -740,5 +744,160 @@ def write_signatures_npz(path, names, pred, true=None):
         out["true_tree_root"] = true.tree_root
         compared, same = int(pred.summary[4]), int(pred.summary[5])
         out["shape_accuracy"] = np.float64(float(same) / compared if compared > 0 else float("nan"))
+    with open(path, "wb") as f:
+        np.savez_compressed(f, **out)
+
+
+PROFILE_TABLE_CELLS = 512            # TW_PROF_TABLE_CELLS of csrc/tw_prof.h: entries a workgroup of the sweep keeps in LDS; beyond it, global cells
+PROFILE_ENTRY_FIELDS = ("rows", "span_time", "span_min", "span_max", "self_time", "path_time", "path_rows", "path_trees", "offset")
+PROFILE_CLASS_FIELDS = ("class_counted", "class_latency", "class_path_time", "class_top_entry")
+
+
+class ClassProfiles(object):
+    """The aggregate trace of every call-graph class (include/traceweaver_amd.h has the definitions), over the counted trees = the
+    trees with a class that the attribution selected.  Per entry of the signatures' class_entries (int64 [n_entries]): rows,
+    span_time, span_min / span_max (INT64_MAX / INT64_MIN without a row), self_time, path_time, path_rows (rows on the critical
+    path), path_trees (counted trees with such a row at the entry), offset (sum of the rows' starts less their tree's).  Per class
+    (int64 [n_classes]): class_counted, class_latency, class_path_time, class_top_entry (the global index of the entry with the
+    largest path_time among those with a row on the path, -1 none).  summary = counted trees, classes with one, counted item rows,
+    entries with a row, classed trees that are not selected, selected trees without a class.  class_off / class_entries / mode
+    (not compared by same_as) are those of the signature result the profile belongs to."""
+
+    FIELDS = PROFILE_ENTRY_FIELDS + PROFILE_CLASS_FIELDS + ("summary",)
+
+    def __init__(self, rows, span_time, span_min, span_max, self_time, path_time, path_rows, path_trees, offset, class_counted, class_latency,
+                 class_path_time, class_top_entry, summary, class_off=None, class_entries=None, mode=0):
+        self.rows, self.span_time, self.span_min, self.span_max, self.self_time = rows, span_time, span_min, span_max, self_time
+        self.path_time, self.path_rows, self.path_trees, self.offset = path_time, path_rows, path_trees, offset
+        self.class_counted, self.class_latency, self.class_path_time, self.class_top_entry = class_counted, class_latency, class_path_time, class_top_entry
+        self.summary = np.asarray(summary, dtype=np.int64)
+        self.class_off = np.zeros(len(class_counted) + 1, dtype=np.int64) if class_off is None else np.asarray(class_off, dtype=np.int64)
+        self.class_entries = np.asarray(() if class_entries is None else class_entries, dtype=np.int32).reshape(-1, 4)
+        self.mode = int(mode)
+
+    n_entries = property(lambda self: len(self.rows))
+    n_classes = property(lambda self: len(self.class_counted))
+    n_counted = property(lambda self: int(self.summary[0]))
+
+    def entry(self, i):
+        """Entry i (global index): its class, (level, caller group, group, count) and PROFILE_ENTRY_FIELDS, as a dict."""
+        i = int(i)
+        if not 0 <= i < self.n_entries:
+            raise IndexError(i)
+        lv, cg, g, k = (int(x) for x in self.class_entries[i])
+        out = {"entry": i, "class": int(np.searchsorted(self.class_off, i, side="right")) - 1, "level": lv, "caller": cg, "group": g, "count": k}
+        out.update({f: int(getattr(self, f)[i]) for f in PROFILE_ENTRY_FIELDS})
+        return out
+
+    def profile(self, c):
+        """The aggregate trace of class c: its entries in signature order, each as entry() gives it."""
+        c = int(c)
+        if not 0 <= c < self.n_classes:
+            raise IndexError(c)
+        return [self.entry(i) for i in range(int(self.class_off[c]), int(self.class_off[c + 1]))]
+
+    def table(self, names=None):
+        """One dict per class with a counted tree, sorted by class_counted descending (ties: the class number): class, counted,
+        mean_latency, path_time, top_entry (global index, -1 none), top = (level, caller, service) of that entry with the groups'
+        names (the caller None in mode "levels"), top_share = its share of the class' path time, top_trees = path_trees /
+        class_counted of it: in how many of the class' counted traces the entry is on the critical path."""
+        name = lambda g: g if names is None or g < 0 else names[g]
+        rows = []
+        for c in sorted(np.flatnonzero(np.asarray(self.class_counted) > 0).tolist(), key=lambda c: (-int(self.class_counted[c]), c)):
+            n, i, total = int(self.class_counted[c]), int(self.class_top_entry[c]), int(self.class_path_time[c])
+            row = {"class": c, "counted": n, "mean_latency": float(self.class_latency[c]) / n, "path_time": total, "top_entry": i, "top": None,
+                   "top_share": 0.0, "top_trees": 0.0}
+            if i >= 0:
+                lv, cg, g, _ = (int(x) for x in self.class_entries[i])
+                row.update({"top": (lv, name(cg) if self.mode == 1 else None, name(g)), "top_share": float(self.path_time[i]) / total if total else 0.0,
+                            "top_trees": float(self.path_trees[i]) / n})
+            rows.append(row)
+        return rows
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def class_profiles_host(stitched, signatures, attribution, link, row_kind, row_start, row_end, row_group):
+    """What tw_class_profiles computes, restated from the definitions with dictionaries, for the tests.  signatures, attribution: the
+    host results of signatures_host and attribute_host on the same forest and groups (tree_class, row_level, the entries and the
+    mode of the first; tree_selected, self_time and path_time of the second); nothing the device computed is read."""
+    link = [int(x) for x in link]
+    kind = [int(x) for x in row_kind]
+    group = [int(x) for x in row_group]
+    start = [int(x) for x in row_start]
+    end = [max(int(e), s) for e, s in zip(row_end, start)]
+    children = [[] for _ in link]
+    for c, p in enumerate(link):
+        if p >= 0:
+            children[p].append(c)
+    _, walked = critical_paths_host(children, start, end, stitched.tree_root)   # the rows attribute_host counts in group_path_rows
+    sig, mode = signatures, signatures.mode
+    ne, nc = len(sig.class_entries), sig.n_classes
+    index = {}
+    for c in range(nc):
+        for j, (lv, cg, g, _) in enumerate(sig.signature(c)):
+            index[(c, lv, cg, g)] = int(sig.class_off[c]) + j
+    cells = {f: {} for f in PROFILE_ENTRY_FIELDS}
+    counted, latency = {}, {}
+    add = lambda f, i, v: cells[f].__setitem__(i, cells[f].get(i, 0) + v)
+    idle = loose = n_rows = 0
+    for t in range(stitched.n_trees):
+        c, sel = int(sig.tree_class[t]), int(attribution.tree_selected[t]) != 0
+        idle += 1 if c >= 0 and not sel else 0
+        loose += 1 if c < 0 and sel else 0
+        if c < 0 or not sel:
+            continue
+        counted[c] = counted.get(c, 0) + 1
+        latency[c] = latency.get(c, 0) + int(stitched.tree_latency[t])
+        root, on_path = int(stitched.tree_root[t]), set()
+        for r in stitched.tree_rows[int(stitched.tree_off[t]):int(stitched.tree_off[t + 1])].tolist():
+            if kind[r] != 1 or group[r] < 0:
+                continue
+            cg = 0
+            if mode == 1:
+                p = link[r]
+                while p >= 0 and kind[p] != 1:
+                    p = link[p]
+                cg = group[p] if p >= 0 else -1
+            i = index[(c, int(sig.row_level[r]), cg, group[r])]
+            d = end[r] - start[r]
+            n_rows += 1
+            add("rows", i, 1)
+            add("span_time", i, d)
+            cells["span_min"][i] = min(cells["span_min"].get(i, d), d)
+            cells["span_max"][i] = max(cells["span_max"].get(i, d), d)
+            add("self_time", i, int(attribution.self_time[r]))
+            add("offset", i, start[r] - start[root])
+            if walked[r]:
+                add("path_time", i, int(attribution.path_time[r]))
+                add("path_rows", i, 1)
+                on_path.add(i)
+        for i in on_path:
+            add("path_trees", i, 1)
+    empty = {"span_min": np.iinfo(np.int64).max, "span_max": np.iinfo(np.int64).min}
+    arrays = [np.array([cells[f].get(i, empty.get(f, 0)) for i in range(ne)], dtype=np.int64) for f in PROFILE_ENTRY_FIELDS]
+    rows, path_time, path_rows = arrays[0], arrays[5], arrays[6]
+    class_path_time, class_top = np.zeros(nc, dtype=np.int64), np.full(nc, -1, dtype=np.int64)
+    for c in range(nc):
+        a, b = int(sig.class_off[c]), int(sig.class_off[c + 1])
+        assert rows[a:b].tolist() == [int(k) * counted.get(c, 0) for k in sig.class_entries[a:b, 3]], c     # the invariant
+        class_path_time[c] = path_time[a:b].sum()
+        on = [i for i in range(a, b) if path_rows[i] > 0]
+        if on:
+            class_top[c] = min(on, key=lambda i: (-int(path_time[i]), i))
+    summary = [sum(counted.values()), len(counted), n_rows, int((rows > 0).sum()), idle, loose]
+    return ClassProfiles(*(arrays + [np.array([counted.get(c, 0) for c in range(nc)], dtype=np.int64),
+                                     np.array([latency.get(c, 0) for c in range(nc)], dtype=np.int64), class_path_time, class_top, summary]),
+                         class_off=sig.class_off, class_entries=sig.class_entries, mode=mode)
+
+
+def write_profiles_npz(path, names, pred, true=None):
+    """The class profiles as one .npz: the arrays of ClassProfiles of the predicted forest (and, prefixed true_, of the true one), the
+    entries they belong to (class_off, class_entries), the mode and the group names."""
+    out = {"mode": np.array(SIGNATURE_MODES[pred.mode]), "group_names": np.array([str(x) for x in names])}
+    for prefix, p in (("", pred), ("true_", true)):
+        if p is not None:
+            out.update({prefix + k: getattr(p, k) for k in ClassProfiles.FIELDS + ("class_off", "class_entries")})
     with open(path, "wb") as f:
         np.savez_compressed(f, **out)

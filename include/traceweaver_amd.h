@@ -253,7 +253,7 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * (tw_get_decisions alone writes ms[19]).
  * The last tw_latency_distributions (HIP events): ms[22] cohorts + the two sweeps over the rows (counts, items; incl. the host's
  * read of the item count), ms[23] sort, offsets and values, ms[24] quantiles and histogram (22 and 23: of the call that built
- * the items). */
+ * the items).  ms[25..30]: tw_trace_signatures and tw_class_profiles (see there).  ms[31]: the kernel of the last tw_order_bound. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -266,6 +266,44 @@ int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 int tw_find_order(tw_engine *e, int32_t n_units, const int64_t *unit_in_off, const int32_t *unit_E,
                   const int64_t *ep_off, const int64_t *out_start, const int64_t *out_end,
                   const int32_t *true_child, uint8_t *dag_out);
+
+/* ---- the call-order DAG without ground truth (traceweaver_amd/csrc/tw_order.h, traceweaver_amd/order.py) ----------
+ *
+ * Replaces: FindConstraintsUsingFit (executor.py:152-212), the reference's answer for a user who has spans but no true
+ * assignment: a greedy search over the ordered endpoint pairs (a, b) in partition-key order -- skip the pair if b -> a is in
+ * the graph, else add a -> b, run FindAssignments, keep the edge iff cnt_unassigned <= 0 -- at up to E(E-1) full solves per
+ * service.  The loop itself lives in traceweaver_amd/order.py (E^2 small decisions per unit; the refit between the passes is
+ * the caller's choice, as everywhere); it runs every unit's next candidate in one batch per round.  The three calls below
+ * are what makes a round cheap.  One difference to the reference: a pair that would close a cycle longer than two raises
+ * in the reference (nx.topological_sort, traceweaver_v1.py:39); here it is rejected and logged as such.
+ *
+ * tw_order_bound: a necessary condition from the timestamps alone, on host arrays before any load, like tw_find_order
+ * (endpoints in partition-key order, every list sorted by (start, end): TW_ERR_ARG otherwise; E > TW_MAX_EP:
+ * TW_ERR_UNSUPPORTED).  viol_out[sum_u E_u*E_u], per unit [E][E]: viol[a][b] = the number of requests r for which no pair
+ * (x of a, y of b) has both spans contained in r (in_start <= start, end <= in_end) and end_a[x] <= start_b[y], every
+ * comparison non-strict; the diagonal is 0.  Such a request has no feasible tuple under any graph with the
+ * edge a -> b and is counted in cnt_unassigned (traceweaver_v3.py:1201-1217): viol[a][b] > 0 proves that the reference's
+ * test of a -> b fails, and the solve is not needed.  Lightly interleaved requests: viol == 0 is FindOrder's relation; under
+ * load it is an upper bound of it.  Integer arithmetic; independent of scheduling.  Timing: tw_get_timing slot 31 (HIP
+ * events, ms, the kernel alone).
+ *
+ * tw_order_stage: uploads the span table of a no-skip batch once, endpoints in partition-key order, into a staging copy the
+ * engine owns (b->dag and b->key_rank are not read).  TW_ERR_UNSUPPORTED: a skip-mode batch (tw_batch.skip, or an endpoint
+ * whose span count differs from the unit's requests), load-scaled units (unit_time_scale), split services (unit_part),
+ * E > TW_MAX_EP.  The copy lives until the next tw_order_stage or tw_destroy; loads do not touch it.
+ *
+ * tw_order_load: loads the staged units active_units[0..n_active) (ascending indices into the staged batch) under the
+ * candidate graphs dag_key (concatenated E*E matrices of the listed units, endpoints in key order, dag[a*E+b] = 1 <=> edge
+ * a -> b; need not be transitively closed).  Per unit: the topological order nx.topological_sort gives for nodes inserted in
+ * key order and a node's out-edges in ascending key order (the order the search adds them in); the staged endpoint segments
+ * gathered into that order on the device; dag and key_rank (= the endpoint's key index) in that order; then tw_load_batch(...,
+ * spans_on_device = 1).  Afterwards the engine is in exactly the state tw_load_batch leaves it in, with the listed units as
+ * units 0..n_active-1.  TW_ERR_STATE before tw_order_stage; TW_ERR_ARG for a graph with a cycle. */
+int tw_order_bound(tw_engine *e, int32_t n_units, const int64_t *unit_in_off, const int32_t *unit_E, const int64_t *ep_off,
+                   const int64_t *in_start, const int64_t *in_end, const int64_t *out_start, const int64_t *out_end,
+                   int64_t *viol_out);
+int tw_order_stage(tw_engine *e, const tw_batch *b);
+int tw_order_load(tw_engine *e, int32_t n_active, const int32_t *active_units, const uint8_t *dag_key);
 
 /* Ground truth of the loaded batch for tw_evaluate: true_child in the layout of tw_results.parent;
  * in_trace[n_in_total] (may be NULL) = trace number in [0, n_traces) of every incoming span, for the per-trace

@@ -121,7 +121,7 @@ TW_DIST_MAX_EDGES = 63
 
 EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_pass1", "tw_get_gaps", "tw_set_gaps",
            "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
-           "tw_assign_service", "tw_find_order", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
+           "tw_assign_service", "tw_find_order", "tw_order_bound", "tw_order_stage", "tw_order_load", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
            "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_trace_signatures", "tw_class_profiles",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
@@ -171,6 +171,9 @@ def load(path=None):
     lib.tw_assign_service.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp,
                                       ctypes.POINTER(Results)]
     lib.tw_find_order.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    lib.tw_order_bound.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tw_order_stage.argtypes = [vp, ctypes.POINTER(Batch)]
+    lib.tw_order_load.argtypes = [vp, ctypes.c_int32, vp, vp]
     lib.tw_set_truth.argtypes = [vp, vp, vp, ctypes.c_int64]
     lib.tw_evaluate.argtypes = [vp, vp, vp, vp]
     lib.tw_measure_hbm_copy.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]

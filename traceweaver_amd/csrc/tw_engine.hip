@@ -28,6 +28,7 @@
 #include "tw_dist.h"
 #include "tw_sig.h"
 #include "tw_prof.h"
+#include "tw_order.h"
 
 using namespace tw;
 
@@ -220,6 +221,18 @@ struct tw_engine {
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
+    // tw_order_stage / tw_order_load (tw_order.h): the span table of a batch in partition-key order, staged once, and the buffers a
+    // candidate's permuted copy is gathered into before tw_load_batch takes it device to device.  Owned by the engine, not by a
+    // load: free_all leaves them alone, tw_order_stage replaces them, tw_destroy frees them.
+    int64_t* ord_stage[4] = {};             // in_start, in_end, out_start, out_end as staged
+    int64_t* ord_gather[4] = {};            // ... of the units of the last tw_order_load, endpoints in topological order
+    int64_t* ord_seg = nullptr;             // segment descriptors of k_order_gather: src, dst, len [ord_seg_cap each]
+    int64_t ord_seg_cap = 0;
+    bool ord_staged = false;
+    std::vector<int64_t> ord_in_off, ord_ep_off, ord_ep_base;
+    std::vector<int32_t> ord_E;
+    int32_t ord_batch_size = 0, ord_batch_mis = 0;
+    double ob_ms = 0;                       // the last k_order_bound (HIP events)
 };
 
 namespace {
@@ -382,6 +395,16 @@ int arena_commit(tw_engine* e) {
     for (const auto& r : e->arena_req) { r.first((char*)e->arena + off); off += r.second; }
     e->arena_req.clear();
     return TW_OK;
+}
+
+void order_unstage(tw_engine* e) {   // (the staged table of tw_order_stage: not a load's, free_all leaves it alone)
+    for (int k = 0; k < 4; k++) {
+        if (e->ord_stage[k]) (void)hipFree(e->ord_stage[k]);
+        if (e->ord_gather[k]) (void)hipFree(e->ord_gather[k]);
+        e->ord_stage[k] = e->ord_gather[k] = nullptr;
+    }
+    if (e->ord_seg) (void)hipFree(e->ord_seg);
+    e->ord_seg = nullptr; e->ord_seg_cap = 0; e->ord_staged = false;
 }
 
 void free_all(tw_engine* e) {
@@ -1127,6 +1150,7 @@ void tw_destroy(tw_engine* e) {
     if (e == nullptr) return;
     (void)hipSetDevice(e->device);
     free_all(e);
+    order_unstage(e);
     if (e->arena != nullptr) (void)hipFree(e->arena);
     for (int i = 0; i < EV_COUNT; i++)
         if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -1879,6 +1903,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 3 && 22 + i < n; i++) ms[22 + i] = e->ds_ms[i];   // the last tw_latency_distributions
     for (int i = 0; i < 3 && 25 + i < n; i++) ms[25 + i] = e->sg_ms[i];   // the last tw_trace_signatures that ran kernels
     for (int i = 0; i < 3 && 28 + i < n; i++) ms[28 + i] = e->pf_ms[i];   // the last tw_class_profiles that ran kernels
+    if (n > 31) ms[31] = e->ob_ms;                                        // the last tw_order_bound
     return TW_OK;
 }
 
@@ -1957,6 +1982,199 @@ int tw_find_order(tw_engine* e, int32_t n_units, const int64_t* unit_in_off, con
         di += E * E;
     }
     return TW_OK;
+}
+
+int tw_order_bound(tw_engine* e, int32_t n_units, const int64_t* unit_in_off, const int32_t* unit_E, const int64_t* ep_off,
+                   const int64_t* in_start, const int64_t* in_end, const int64_t* out_start, const int64_t* out_end, int64_t* viol_out) {
+    if (e == nullptr || n_units <= 0 || !unit_in_off || !unit_E || !ep_off || !in_start || !in_end || !out_start || !out_end || !viol_out) return TW_ERR_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    std::vector<int64_t> ep_base((size_t)n_units), viol_off((size_t)n_units);
+    int64_t epi = 0, vi = 0, max_n = 0;
+    auto sorted = [](const int64_t* s, const int64_t* t, int64_t a, int64_t b) {   // by (start, end)
+        for (int64_t i = a + 1; i < b; i++)
+            if (s[i - 1] > s[i] || (s[i - 1] == s[i] && t[i - 1] > t[i])) return false;
+        return true;
+    };
+    for (int u = 0; u < n_units; u++) {
+        const int E = unit_E[u];
+        if (E < 1 || E > TW_MAX_EP) return fail(e, TW_ERR_UNSUPPORTED, "unit has E outside [1, TW_MAX_EP]");
+        const int64_t n = unit_in_off[u + 1] - unit_in_off[u];
+        if (n < 0) return fail(e, TW_ERR_ARG, "tw_order_bound: unit_in_off is not ascending");
+        if (!sorted(in_start, in_end, unit_in_off[u], unit_in_off[u + 1])) return fail(e, TW_ERR_ARG, "tw_order_bound: incoming spans are not sorted by (start, end)");
+        for (int k = 0; k < E; k++) {
+            if (ep_off[epi + k + 1] < ep_off[epi + k]) return fail(e, TW_ERR_ARG, "tw_order_bound: ep_off is not ascending");
+            if (!sorted(out_start, out_end, ep_off[epi + k], ep_off[epi + k + 1])) return fail(e, TW_ERR_ARG, "tw_order_bound: an endpoint's spans are not sorted by (start, end)");
+        }
+        ep_base[(size_t)u] = epi; viol_off[(size_t)u] = vi;
+        epi += E; vi += (int64_t)E * E;
+        max_n = std::max(max_n, n);
+    }
+    if (unit_in_off[0] != 0 || ep_off[0] != 0) return fail(e, TW_ERR_ARG, "tw_order_bound: offsets start at 0");
+    const int64_t n_in = unit_in_off[n_units], n_out = ep_off[epi];
+    std::vector<void*> tmp;
+    auto up = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
+        hipError_t s = hipMalloc(dst, std::max<size_t>(bytes, 8));
+        if (s != hipSuccess) return s;
+        tmp.push_back(*dst);
+        return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, e->stream) : hipSuccess;
+    };
+    void *d_io, *d_E, *d_eb, *d_eo, *d_vo, *d_is, *d_ie, *d_os, *d_oe, *d_v = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t s = up(unit_in_off, sizeof(int64_t) * (size_t)(n_units + 1), &d_io);
+    if (s == hipSuccess) s = up(unit_E, sizeof(int32_t) * (size_t)n_units, &d_E);
+    if (s == hipSuccess) s = up(ep_base.data(), sizeof(int64_t) * (size_t)n_units, &d_eb);
+    if (s == hipSuccess) s = up(ep_off, sizeof(int64_t) * (size_t)(epi + 1), &d_eo);
+    if (s == hipSuccess) s = up(viol_off.data(), sizeof(int64_t) * (size_t)n_units, &d_vo);
+    if (s == hipSuccess) s = up(in_start, sizeof(int64_t) * (size_t)n_in, &d_is);
+    if (s == hipSuccess) s = up(in_end, sizeof(int64_t) * (size_t)n_in, &d_ie);
+    if (s == hipSuccess) s = up(out_start, sizeof(int64_t) * (size_t)n_out, &d_os);
+    if (s == hipSuccess) s = up(out_end, sizeof(int64_t) * (size_t)n_out, &d_oe);
+    if (s == hipSuccess) { s = hipMalloc(&d_v, sizeof(unsigned long long) * (size_t)vi); if (s == hipSuccess) tmp.push_back(d_v); }
+    if (s == hipSuccess) s = hipMemsetAsync(d_v, 0, sizeof(unsigned long long) * (size_t)vi, e->stream);
+    if (s == hipSuccess) s = hipEventCreate(&ev0);
+    if (s == hipSuccess) s = hipEventCreate(&ev1);
+    if (s == hipSuccess) {
+        OrderBoundDev O{};
+        O.unit_in_off = (const int64_t*)d_io; O.unit_E = (const int32_t*)d_E; O.ep_base = (const int64_t*)d_eb; O.ep_off = (const int64_t*)d_eo;
+        O.viol_off = (const int64_t*)d_vo; O.in_start = (const int64_t*)d_is; O.in_end = (const int64_t*)d_ie;
+        O.out_start = (const int64_t*)d_os; O.out_end = (const int64_t*)d_oe; O.viol = (unsigned long long*)d_v;
+        const int threads = (int)flat_threads(e);
+        const unsigned bx = (unsigned)std::max<int64_t>((max_n + threads - 1) / threads, 1);   // a lane per request
+        s = hipEventRecord(ev0, e->stream);
+        for (int u0 = 0; u0 < n_units && s == hipSuccess; u0 += 32768) {  // grid.y is limited to 65535
+            OrderBoundDev Q = O;
+            Q.unit_in_off += u0; Q.unit_E += u0; Q.ep_base += u0; Q.viol_off += u0;
+            hipLaunchKernelGGL(k_order_bound, dim3(bx, (unsigned)std::min(n_units - u0, 32768)), dim3((unsigned)threads), 0, e->stream, Q);
+            s = hipGetLastError();
+        }
+        if (s == hipSuccess) s = hipEventRecord(ev1, e->stream);
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "viol table");
+        if (s == hipSuccess) s = hipMemcpyAsync(viol_out, d_v, sizeof(int64_t) * (size_t)vi, hipMemcpyDeviceToHost, e->stream);
+        if (s == hipSuccess) s = hipStreamSynchronize(e->stream);
+        float ms = 0.f;
+        if (s == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) e->ob_ms = (double)ms;
+    }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    for (void* q : tmp) (void)hipFree(q);
+    if (s != hipSuccess) return fail(e, TW_ERR_DEVICE, std::string("tw_order_bound: ") + hipGetErrorString(s));
+    return TW_OK;
+}
+
+int tw_order_stage(tw_engine* e, const tw_batch* b) {
+    if (e == nullptr || b == nullptr) return TW_ERR_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    if (b->n_units <= 0 || !b->unit_in_off || !b->unit_E || !b->ep_off || !b->in_start || !b->in_end || !b->out_start || !b->out_end)
+        return fail(e, TW_ERR_ARG, "tw_order_stage: incomplete batch");
+    if (b->skip != nullptr) return fail(e, TW_ERR_UNSUPPORTED, "tw_order_stage: skip-mode batches are not searched (one pass, no cnt_unassigned test of a candidate)");
+    if (b->unit_time_scale != nullptr) return fail(e, TW_ERR_UNSUPPORTED, "tw_order_stage: load-scaled units (unit_time_scale) are not supported");
+    if (b->unit_part != nullptr) return fail(e, TW_ERR_UNSUPPORTED, "tw_order_stage: split services (unit_part) are not supported");
+    if (b->topk != TW_TOPK) return fail(e, TW_ERR_UNSUPPORTED, "topk must be 5 (traceweaver_v3.py:1109)");
+    if (b->batch_size <= 0 || b->batch_size_mis <= 0) return fail(e, TW_ERR_ARG, "batch sizes must be positive");
+    if (b->unit_in_off[0] != 0 || b->ep_off[0] != 0) return fail(e, TW_ERR_ARG, "tw_order_stage: offsets start at 0");
+    int64_t epi = 0;
+    std::vector<int64_t> ep_base((size_t)b->n_units);
+    for (int u = 0; u < b->n_units; u++) {
+        const int E = b->unit_E[u];
+        if (E < 1 || E > TW_MAX_EP) return fail(e, TW_ERR_UNSUPPORTED, "unit has E outside [1, TW_MAX_EP]");
+        const int64_t n = b->unit_in_off[u + 1] - b->unit_in_off[u];
+        if (n < 2) return fail(e, TW_ERR_ARG, "a unit needs at least 2 incoming spans");
+        for (int k = 0; k < E; k++)
+            if (b->ep_off[epi + k + 1] - b->ep_off[epi + k] != n)
+                return fail(e, TW_ERR_UNSUPPORTED, "tw_order_stage: an endpoint's span count differs from the number of incoming spans (a skip-mode unit)");
+        ep_base[(size_t)u] = epi;
+        epi += E;
+    }
+    const int64_t n_in = b->unit_in_off[b->n_units], n_out = b->ep_off[epi];
+    if (n_in >= (1ll << 31) || n_out >= (1ll << 31)) return fail(e, TW_ERR_ARG, "batch exceeds 2^31 spans");
+    order_unstage(e);
+    const int64_t counts[4] = {n_in, n_in, n_out, n_out};
+    const int64_t* src[4] = {b->in_start, b->in_end, b->out_start, b->out_end};
+    for (int k = 0; k < 4; k++) {
+        HIPCHK(hipMalloc((void**)&e->ord_stage[k], sizeof(int64_t) * (size_t)std::max<int64_t>(counts[k], 1)));
+        HIPCHK(hipMalloc((void**)&e->ord_gather[k], sizeof(int64_t) * (size_t)std::max<int64_t>(counts[k], 1)));
+        HIPCHK(hipMemcpyAsync(e->ord_stage[k], src[k], sizeof(int64_t) * (size_t)counts[k], hipMemcpyHostToDevice, e->stream));
+    }
+    e->ord_seg_cap = std::max<int64_t>(epi, b->n_units);
+    HIPCHK(hipMalloc((void**)&e->ord_seg, sizeof(int64_t) * 3 * (size_t)e->ord_seg_cap));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->ord_in_off.assign(b->unit_in_off, b->unit_in_off + b->n_units + 1);
+    e->ord_ep_off.assign(b->ep_off, b->ep_off + epi + 1);
+    e->ord_E.assign(b->unit_E, b->unit_E + b->n_units);
+    e->ord_ep_base = ep_base;
+    e->ord_batch_size = b->batch_size; e->ord_batch_mis = b->batch_size_mis;
+    e->ord_staged = true;
+    return TW_OK;
+}
+
+int tw_order_load(tw_engine* e, int32_t n_active, const int32_t* active_units, const uint8_t* dag_key) {
+    if (e == nullptr || n_active <= 0 || active_units == nullptr || dag_key == nullptr) return TW_ERR_ARG;
+    if (!e->ord_staged) return fail(e, TW_ERR_STATE, "tw_order_load before tw_order_stage");
+    HIPCHK(hipSetDevice(e->device));
+    const int32_t n_staged = (int32_t)e->ord_E.size();
+    std::vector<int64_t> in_off{0}, ep_off{0}, seg_in_src, seg_in_dst, seg_in_len, seg_out_src, seg_out_dst, seg_out_len;
+    std::vector<int32_t> unit_E, key_rank;
+    std::vector<uint8_t> dag;
+    int64_t di = 0, max_len = 0;
+    for (int k = 0; k < n_active; k++) {
+        const int32_t u = active_units[k];
+        if (u < 0 || u >= n_staged || (k > 0 && u <= active_units[k - 1])) return fail(e, TW_ERR_ARG, "tw_order_load: active_units must be ascending indices of staged units");
+        const int E = e->ord_E[(size_t)u];
+        const uint8_t* dk = dag_key + di;
+        // nx.topological_sort (traceweaver_v1.py:37-39) on arrays: generation after generation, a generation in the order in which
+        // its nodes lost their last predecessor -- the nodes in insertion (key) order, a node's successors in the order its edges
+        // were added, which is ascending key order for the search (it walks the pairs (a, b) in key order)
+        int indeg[TW_MAX_EP] = {}, order[TW_MAX_EP], n_ord = 0;
+        for (int a = 0; a < E; a++)
+            for (int c = 0; c < E; c++)
+                if (dk[a * E + c]) {
+                    if (a == c) return fail(e, TW_ERR_ARG, "tw_order_load: the candidate graph has a self loop");
+                    indeg[c]++;
+                }
+        for (int a = 0; a < E; a++) if (indeg[a] == 0) order[n_ord++] = a;
+        for (int h = 0; h < n_ord; h++)
+            for (int c = 0; c < E; c++)
+                if (dk[order[h] * E + c] && --indeg[c] == 0) order[n_ord++] = c;
+        if (n_ord != E) return fail(e, TW_ERR_ARG, "tw_order_load: the candidate graph has a cycle");
+        const int64_t n = e->ord_in_off[(size_t)u + 1] - e->ord_in_off[(size_t)u];
+        seg_in_src.push_back(e->ord_in_off[(size_t)u]); seg_in_dst.push_back(in_off.back()); seg_in_len.push_back(n);
+        in_off.push_back(in_off.back() + n);
+        max_len = std::max(max_len, n);
+        const int64_t eb = e->ord_ep_base[(size_t)u];
+        for (int p = 0; p < E; p++) {
+            const int64_t a = e->ord_ep_off[(size_t)(eb + order[p])], len = e->ord_ep_off[(size_t)(eb + order[p] + 1)] - a;
+            seg_out_src.push_back(a); seg_out_dst.push_back(ep_off.back()); seg_out_len.push_back(len);
+            ep_off.push_back(ep_off.back() + len);
+            key_rank.push_back(order[p]);
+            for (int q = 0; q < E; q++) dag.push_back(dk[order[p] * E + order[q]]);
+        }
+        unit_E.push_back(E);
+        di += (int64_t)E * E;
+    }
+    const unsigned threads = flat_threads(e);
+    const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_len + threads - 1) / threads, 1), 1024);
+    auto gather = [&](const std::vector<int64_t>& src, const std::vector<int64_t>& dst, const std::vector<int64_t>& len, int first) -> int {
+        const int64_t n_seg = (int64_t)src.size();   // (<= ord_seg_cap: the listed units are distinct staged units)
+        HIPCHK(hipMemcpyAsync(e->ord_seg, src.data(), sizeof(int64_t) * (size_t)n_seg, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->ord_seg + e->ord_seg_cap, dst.data(), sizeof(int64_t) * (size_t)n_seg, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->ord_seg + 2 * e->ord_seg_cap, len.data(), sizeof(int64_t) * (size_t)n_seg, hipMemcpyHostToDevice, e->stream));
+        for (int64_t g0 = 0; g0 < n_seg; g0 += 32768) {  // grid.y is limited to 65535
+            OrderGatherDev G{e->ord_seg + g0, e->ord_seg + e->ord_seg_cap + g0, e->ord_seg + 2 * e->ord_seg_cap + g0,
+                             e->ord_stage[first], e->ord_stage[first + 1], e->ord_gather[first], e->ord_gather[first + 1]};
+            hipLaunchKernelGGL(k_order_gather, dim3(bx, (unsigned)std::min<int64_t>(n_seg - g0, 32768)), dim3(threads), 0, e->stream, G);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipStreamSynchronize(e->stream));   // (the descriptor block is written again by the next call)
+        return TW_OK;
+    };
+    TWCHK(gather(seg_in_src, seg_in_dst, seg_in_len, 0));
+    TWCHK(gather(seg_out_src, seg_out_dst, seg_out_len, 2));
+    tw_batch b{};
+    b.n_units = n_active;
+    b.unit_in_off = in_off.data(); b.unit_E = unit_E.data(); b.ep_off = ep_off.data(); b.dag = dag.data(); b.key_rank = key_rank.data();
+    b.in_start = e->ord_gather[0]; b.in_end = e->ord_gather[1]; b.out_start = e->ord_gather[2]; b.out_end = e->ord_gather[3];
+    b.batch_size = e->ord_batch_size; b.batch_size_mis = e->ord_batch_mis; b.topk = TW_TOPK;
+    return tw_load_batch(e, &b, 1);
 }
 
 int tw_set_truth(tw_engine* e, const int32_t* true_child, const int32_t* in_trace, int64_t n_traces) {

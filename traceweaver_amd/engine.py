@@ -702,6 +702,89 @@ class Engine(object):
             p += int(e) * int(e)
         return out
 
+    # ------------------------------------------------------------------------------------------
+    # the call-order DAG without ground truth (csrc/tw_order.h; the search itself: traceweaver_amd/order.py)
+    @staticmethod
+    def _soa(units):
+        """The descriptor and span arrays of tw_batch for a list of units (their dag / key_rank left out)."""
+        in_off = np.zeros(len(units) + 1, dtype=np.int64)
+        np.cumsum([u.n_in for u in units], out=in_off[1:])
+        unit_E = np.array([u.E for u in units], dtype=np.int32)
+        ep_off, base = [0], 0
+        for u in units:
+            ep_off.extend((base + u.out_off[1:]).tolist())
+            base += int(u.out_off[-1])
+        cat = lambda name: np.ascontiguousarray(np.concatenate([getattr(u, name) for u in units]), dtype=np.int64)
+        return in_off, unit_E, np.array(ep_off, dtype=np.int64), cat("in_start"), cat("in_end"), cat("out_start"), cat("out_end")
+
+    def order_bound(self, units):
+        """tw_order_bound for units that need not be loaded, endpoints in partition-key order: per unit the int64 [E, E] table
+        viol[a, b] = requests in which no call to a that lies inside the request ends before (or when) some call to b inside
+        it starts.  viol[a, b] > 0 proves that a solve under any graph with the edge a -> b leaves a request unassigned."""
+        units = list(units)
+        in_off, unit_E, ep_off, i_s, i_e, o_s, o_e = self._soa(units)
+        viol = np.zeros(int(sum(int(e) * int(e) for e in unit_E)), dtype=np.int64)
+        self._check(self._lib.tw_order_bound(self._h, len(units), _vp(in_off), _vp(unit_E), _vp(ep_off), _vp(i_s), _vp(i_e), _vp(o_s), _vp(o_e), _vp(viol)))
+        out, p = [], 0
+        for e in unit_E:
+            out.append(viol[p:p + int(e) * int(e)].reshape(int(e), int(e)).copy())
+            p += int(e) * int(e)
+        return out
+
+    def order_bound_ms(self):
+        """The last order_bound's kernel on the device (HIP events, ms)."""
+        ms = np.zeros(32, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 32))
+        return float(ms[31])
+
+    def order_stage(self, units, batch_size=100, batch_size_mis=30, skip=None):
+        """Upload the span table of a no-skip batch once, endpoints in partition-key order (the units' dag / key_rank are not
+        read), for order_load (tw_order_stage).  Skip-mode batches (`skip`, or an endpoint short of spans), load-scaled units
+        and parts of a split service are refused (TW_ERR_UNSUPPORTED)."""
+        units = list(units)
+        in_off, unit_E, ep_off, i_s, i_e, o_s, o_e = self._soa(units)
+        scaled = [u.time_scale is not None for u in units]
+        ts = np.array([u.time_scale if s else 1.0 for u, s in zip(units, scaled)], dtype=np.float64) if any(scaled) else None
+        part = np.array([u.part for u in units], dtype=np.uint8) if any(u.part for u in units) else None
+        skip_arr = (_ffi.SkipUnit * len(units))() if skip is not None else None
+        b = _ffi.Batch(len(units), _vp(in_off), _vp(unit_E), _vp(ep_off), None, None, _vp(i_s), _vp(i_e), _vp(o_s), _vp(o_e),
+                       batch_size, batch_size_mis, _ffi.TW_TOPK, _vp(ts),
+                       ctypes.cast(skip_arr, ctypes.c_void_p) if skip_arr is not None else ctypes.c_void_p(0), _vp(part))
+        self._check(self._lib.tw_order_stage(self._h, ctypes.byref(b)))
+        self._staged = units
+        self._stage_sizes = (int(batch_size), int(batch_size_mis))
+
+    def order_load(self, active, dags):
+        """Load the staged units `active` (ascending indices into the staged batch) under the candidate graphs `dags` (per
+        listed unit uint8 [E, E] in key order, dag[a, b] = 1 <=> a -> b): the topological order on the host, the endpoint
+        segments gathered into it on the device, then the usual load (tw_order_load).  Afterwards the engine -- and self.units,
+        the permuted units with dag and key_rank in that order -- is as after load() of those units."""
+        from .order import permuted_unit
+
+        active = np.ascontiguousarray(active, dtype=np.int32)
+        staged = getattr(self, "_staged", None)
+        if staged is None:
+            raise EngineError(-4, "order_load before order_stage")
+        if len(dags) != len(active):
+            raise ValueError("one candidate graph per listed unit")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(d, dtype=np.uint8).ravel() for d in dags]), dtype=np.uint8)
+        if any(k < 0 or k >= len(staged) for k in active.tolist()) or len(flat) != sum(staged[k].E ** 2 for k in active.tolist()):
+            raise ValueError("candidate graphs do not match the staged units")
+        self._check(self._lib.tw_order_load(self._h, len(active), _vp(active), _vp(flat)))
+        units = [permuted_unit(staged[k], d, lazy=True) for k, d in zip(active.tolist(), dags)]
+        self.units = units
+        self.skip_mode = False
+        self._keep = None
+        self._n_cohorts = 1
+        self._last_pass, self._n_rows = 0, 0
+        batch_size = self._stage_sizes[0]
+        self._in_off = np.concatenate([[0], np.cumsum([u.n_in for u in units])]).astype(np.int64)
+        self._ie_off = np.concatenate([[0], np.cumsum([u.n_in * u.E for u in units])]).astype(np.int64)
+        self._slot_off = np.concatenate([[0], np.cumsum([u.nslot for u in units])]).astype(np.int64)
+        self._gap_off = np.concatenate([[0], np.cumsum([u.nslot * u.n_in for u in units])]).astype(np.int64)
+        self._nblk = [(u.n_in + batch_size - 1) // batch_size for u in units]
+        self._gp_off = np.concatenate([[0], np.cumsum([nb * u.nslot for nb, u in zip(self._nblk, units)])]).astype(np.int64)
+
     def build_distributions(self, start, dur, ep, large_delay, E):
         """The sweep of BuildDistributions (traceweaver_v3.py:120-169) on the device: per span of the merged, start-ordered
         list the pair index a * (E + 1) + b its delay sample belongs to (-1 none) and the sample."""

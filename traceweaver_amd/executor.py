@@ -131,6 +131,12 @@ def parse_args(argv=None):
                     help="--confidence_out: a trace is confident when every decision in it is the best of its list by at least this margin")
     ap.add_argument("--query_confident", type=int, default=0, choices=[0, 1],
                     help="1: --attribute_out asks for whole AND confident traces only (needs --confidence_out)")
+    ap.add_argument("--infer_order", type=int, default=0, choices=[0, 1],
+                    help="1: solve every service under a call-order graph inferred from its spans alone (the reference's "
+                         "FindConstraintsUsingFit, executor.py:152-212, as traceweaver_amd/order.py runs it: all services of the run in one "
+                         "batch per candidate round) instead of FindOrder's, which reads the true assignments; prints per service whether "
+                         "the two graphs are equal (the reference's cg_booleans).  Not with --cache_rate > 0 or --compress_factor > 1.  "
+                         "Default: off, nothing changes")
     ap.add_argument("--engine_library", type=q, default=None, help=argparse.SUPPRESS)   # tests: host-emulation build
     args = ap.parse_args(argv)
     if args.relative_path is None and args.absolute_path is None:
@@ -192,6 +198,8 @@ def unsupported(args):
                         "other fits solve the services one after the other)")
     if args.confidence_out and args.min_margin != args.min_margin:
         problems.append("--min_margin nan")
+    if args.infer_order and (args.cache_rate > 0 or args.compress_factor > 1):
+        problems.append("--infer_order 1 with --cache_rate > 0 or --compress_factor > 1 (the search covers neither skip-mode nor load-scaled services)")
     if args.query_confident and not (args.confidence_out and args.attribute_out):
         problems.append("--query_confident 1 without --confidence_out and --attribute_out")
     return problems
@@ -223,6 +231,34 @@ def scale_load(units, args, trace_id, corpus):
         out.append(IngestedUnit(s.arrays, s.true_parent, u.in_trace[s.in_perm], u.service, u.in_ep, u.out_eps, u.in_rows[s.in_perm],
                                 [r[p] for r, p in zip(u.out_rows, s.out_perm)], u.process_id))
     return out, factors, ranks
+
+
+def infer_order(units, args):
+    """--infer_order 1: the call-order graph of every service from its spans alone, all services in one batch per round
+    (traceweaver_amd/order.py); every unit is handed on with its endpoints in the topological order of the inferred graph.
+    Returns (units, cg_booleans): per service whether the inferred graph equals FindOrder's (executor.py:205-206)."""
+    from . import order
+    from .engine import Engine
+    from .ingest import IngestedUnit
+
+    keyed = [order.key_order_unit(u.arrays) for u in units]
+    eng = Engine(args.device, lib_path=args.engine_library)
+    t0 = time.time()
+    found = order.infer_order(eng, [k[0] for k in keyed], seeds=[args.seed + j for j in range(len(units))])
+    eng.close()
+    print("Inferred the call order of %d services in %.2f s: %d rounds, %d candidate graphs solved" % (len(units), time.time() - t0, found.rounds, found.solves))
+    out, same = [], []
+    for j, (u, (ku, perm)) in enumerate(zip(units, keyed)):
+        same.append(bool(np.array_equal(found.dags[j], u.arrays.dag[np.ix_(perm, perm)])))
+        how = {h: sum(1 for x in found.logs[j] if x[2] == h) for h in order.DECIDED_BY}
+        print("Call graph of service %s: %s (%d edges; pairs decided by solve %d, bound %d, reverse %d, cycle %d)" % (
+            u.service, "identical to FindOrder's" if same[-1] else "differs from FindOrder's", int(found.dags[j].sum()),
+            how["solve"], how["bound"], how["reverse"], how["cycle"]))
+        arrays = order.permuted_unit(ku, found.dags[j])
+        src = [perm[k] for k in arrays.key_rank.tolist()]           # the ingested unit's endpoint at every new position
+        out.append(IngestedUnit(arrays, u.true_parent[src], u.in_trace, u.service, u.in_ep, [u.out_eps[e] for e in src], u.in_rows,
+                                [u.out_rows[e] for e in src], u.process_id))
+    return out, same
 
 
 CONFIDENCE_EDGES = (0.0, 1.0, 2.0, 5.0)   # --confidence_out: bucket edges of the calibration table (differences of log scores)
@@ -434,6 +470,9 @@ def run(args):
     table = corpus.span_table()
     names = corpus.trace_names()
     trace_id = lambda k: corpus.string(names[k])
+    cg_booleans = None
+    if args.infer_order:                                           # executor.py:152-212 in place of FindOrder (:1143)
+        units, cg_booleans = infer_order(units, args)
     resident = None
     if args.compress_factor > 1:                                   # executor.py:1086-1097,1146-1148
         resident = units                                           # the device scales its own copy of the table (tw_scale_load)
@@ -613,6 +652,8 @@ def run(args):
         print("End-to-end accuracy for method %s: %.3f%%" % (k, v))
     if lost:
         confidence["left_out"] = dict(lost)
+    if cg_booleans is not None:
+        print("Inferred call graphs identical to FindOrder's: %d of %d" % (sum(cg_booleans), len(cg_booleans)))
 
     os.makedirs(os.path.dirname(args.results_directory) or ".", exist_ok=True)   # the name is used as a prefix, like the reference does
     suffix = "_%s_%s_%s_%s_%s.pickle" % (args.test_name, args.load_level, int(args.compress_factor), int(args.repeat_factor), args.cache_rate)

@@ -106,6 +106,7 @@ class TraceWeaverGPU(object):
                                         # (executor.py:1015-1023) may call one predictor instance from several threads
         self.last_timing = {}
         self.last_stats = {}            # counters of the last call, incl. budget_windows (selection not proven optimal)
+        self.last_order = None          # order.InferredOrder of the last call that was given no invocation graph
         self._time_windows = []         # the reference never clears self.time_windows between services (SURVEY.md hazard H8)
 
     # ------------------------------------------------------------------------------------------
@@ -166,7 +167,9 @@ class TraceWeaverGPU(object):
 
     # ------------------------------------------------------------------------------------------
     def FindAssignments(self, method, process, in_span_partitions, out_span_partitions, parallel, instrumented_hops,
-                        true_assignments, invocation_graph, true_skips=False, true_dist=False):
+                        true_assignments, invocation_graph=None, true_skips=False, true_dist=False):
+        """invocation_graph=None: the graph is inferred for this service first (FindConstraintsUsingFit, executor.py:152-212, as
+        traceweaver_amd/order.py runs it; `last_order` keeps the log) and the service is solved with it."""
         with self._lock:
             return self._find_assignments(method, process, in_span_partitions, out_span_partitions, parallel, instrumented_hops,
                                           true_assignments, invocation_graph, true_skips, true_dist)
@@ -240,6 +243,23 @@ class TraceWeaverGPU(object):
         self.last_stats = {k: r[k] for k in ("not_best_count", "cnt_unassigned", "n_windows", "repaired_windows", "budget_windows")}
         return all_assignments, all_topk_assignments, r["not_best_count"], n_in, per_span_candidates, r["cnt_unassigned"]
 
+    def _infer_graph(self, in_spans, out_span_partitions):
+        """The call-order DAG of one service from its spans alone (order.infer_order, default seeded refit)."""
+        import networkx as nx
+
+        from . import order
+
+        keys = list(out_span_partitions.keys())
+        if any(len(out_span_partitions[ep]) != len(in_spans) for ep in keys):
+            raise NotImplementedError("the call order of a skip-mode service (an endpoint short of spans) is not inferred: pass invocation_graph")
+        empty = nx.DiGraph()
+        empty.add_nodes_from(keys)
+        unit = pack_unit(in_spans, out_span_partitions, keys, empty)   # endpoints in partition-key order
+        if unit.time_scale is not None:
+            raise NotImplementedError("the call order of a load-scaled service is not inferred: pass invocation_graph")
+        self.last_order = order.infer_order(self._engine, [unit])
+        return self.last_order.graph(0, keys)
+
     def _find_assignments(self, method, process, in_span_partitions, out_span_partitions, parallel, instrumented_hops,
                           true_assignments, invocation_graph, true_skips=False, true_dist=False):
         assert len(in_span_partitions) == 1                       # traceweaver_v3.py:1088
@@ -248,6 +268,8 @@ class TraceWeaverGPU(object):
         import networkx as nx
 
         in_ep, in_spans = list(in_span_partitions.items())[0]
+        if invocation_graph is None:
+            invocation_graph = self._infer_graph(in_spans, out_span_partitions)
         out_eps = list(nx.topological_sort(invocation_graph))     # traceweaver_v1.py:39
         n_in = len(in_spans)
         unit = pack_unit(in_spans, out_span_partitions, out_eps, invocation_graph)

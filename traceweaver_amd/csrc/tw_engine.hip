@@ -114,6 +114,7 @@ struct tw_engine {
     int tile = kTile;   // incoming spans (threads) per workgroup of the per-span kernels
     int tile_threads = 2; // threads per incoming span of k_enumerate_tile (its items and tuples are spread over all of them)
     int tile_single = 1;  // TW_TILE_SINGLE: the one-endpoint class takes the lean path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int block_params = 1; // TW_BLOCK_PARAMS: pass-1 block parameters by a wavefront per group of blocks (0 = the thread-per-slot kernel: A/B runs, bisection)
     int tile_single_threads = 1;   // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
     int coop = kCoop;   // threads of the per-unit cooperative kernels
     std::vector<UnitDev> units;
@@ -165,6 +166,8 @@ struct tw_engine {
     int32_t* ctr = nullptr;
     int64_t ctr_round_ints = 0, ctr_pass_ints = 0;
     int32_t tile_cls_off[kMaxEp + 2] = {};  // class E owns tile_ids[tile_cls_off[E] .. tile_cls_off[E+1])
+    BlockRef* blk_tab = nullptr;            // the groups of blocks k_block_params_wave is launched over (a wavefront each), in unit order: those of every unit, then class by class
+    int32_t blk_cls_off[kMaxEp + 2] = {};   // slot 0 (every unit) and class E own blk_tab[blk_cls_off[E] .. blk_cls_off[E+1])
     uint32_t *seg_gap = nullptr, *seg_gap_end = nullptr, *seg_gap_dst = nullptr;
     unsigned long long *comp_a = nullptr, *comp_b = nullptr;  // composite keys of sort_rows
     int64_t comp_cap = 0, n_gap_scored = 0;
@@ -452,6 +455,20 @@ int sort_ends(tw_engine* e, const TileSet& S, hipStream_t st) {   // (the counte
     return TW_OK;
 }
 
+// ComputeEpPairDistParams3 behind sort_ends: the blocks of every unit (cls = 0) or of the units of one endpoint-count class
+void launch_block_params(tw_engine* e, int cls, hipStream_t st) {
+    const Dev& P = e->P;
+    if (e->block_params == 0) {
+        const int64_t total = e->n_gp;
+        hipLaunchKernelGGL(k_block_params, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, total, cls);
+        return;
+    }
+    const int n = e->blk_cls_off[cls + 1] - e->blk_cls_off[cls];
+    if (n <= 0) return;
+    const int threads = e->coop >= 64 ? 64 * std::min(e->coop / 64, kParamWaves) : e->coop, waves = std::max(threads / 64, 1);
+    hipLaunchKernelGGL(k_block_params_wave, dim3((unsigned)((n + waves - 1) / waves)), dim3(threads), 0, st, P, (const BlockRef*)(e->blk_tab + e->blk_cls_off[cls]), n);
+}
+
 // mode 0: first solve on all spans (per-thread kernel, then the wavefront kernel for the spans it deferred);
 // mode 1: the spans listed by k_detect_gone, without the candidate spans earlier windows took
 // The classes (units of one endpoint count) are independent of one another and every class' kernels end in a long tail
@@ -513,8 +530,7 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
     if (mode == 0 && pass == 1 && e->class_params) {   // the class' sorted end times and block parameters (run_pass)
         const TileSet S = class_tiles(e, E);
         (void)sort_ends(e, S, st);
-        const int64_t total = e->n_gp;
-        hipLaunchKernelGGL(k_block_params, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, total, E);
+        launch_block_params(e, E, st);
     }
     if (mode == 0) {
         // cut-offs and work lists, the short enumerations: the tile kernel.  A class of few tiles: several workgroups per tile, until
@@ -828,8 +844,7 @@ int run_pass(tw_engine* e, int pass) {
         else {
             int rc = sort_ends(e, all_tiles_host(e), e->stream);
             if (rc != TW_OK) return rc;
-            const int64_t total = e->n_gp;
-            hipLaunchKernelGGL(k_block_params, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, P, total, 0);
+            launch_block_params(e, 0, e->stream);
         }
     }
     if (e->skip_mode) {
@@ -1087,6 +1102,7 @@ int tw_create(int device_id, tw_engine** out) {
     e->tile = std::min(std::max(env_int("TW_TILE", kTile), 1), kTile);
     e->tile_threads = std::min(std::max(env_int("TW_TILE_THREADS", 2), 1), 4);
     e->tile_single = env_int("TW_TILE_SINGLE", 1);
+    e->block_params = env_int("TW_BLOCK_PARAMS", 1);
     e->tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
     e->coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
     // The engine runs its endpoint-count classes and window classes on streams of their own (up to 8 + 3 beside its own).  The
@@ -1288,6 +1304,14 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
             if (e->units[(size_t)u].E == cls) heavy_off_h[cls + 1] += e->units[(size_t)u].n_in;
     }
     e->tile_cls_off[kMaxEp + 1] = (int32_t)tile_ids_h.size();
+    std::vector<BlockRef> blk_tab_h;   // (8 B per group of blocks and table: every unit's groups, then each class' own)
+    for (int cls = 0; cls <= kMaxEp; cls++) {
+        e->blk_cls_off[cls] = (int32_t)blk_tab_h.size();
+        for (int u = 0; u < b->n_units; u++)
+            if (cls == 0 || e->units[(size_t)u].E == cls)
+                for (int k = 0; k < e->units[(size_t)u].nblk; k += param_group(e->units[(size_t)u].E)) blk_tab_h.push_back(BlockRef{u, k});
+    }
+    e->blk_cls_off[kMaxEp + 1] = (int32_t)blk_tab_h.size();
     for (int cls = 1; cls <= kMaxEp; cls++)
         if (e->tile_cls_off[cls + 1] > e->tile_cls_off[cls]) {
             int rs = ensure_class_stream(e, cls); if (rs != TW_OK) return rs;
@@ -1379,6 +1403,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     DEV_ALLOC(P.owner, n_out_total);
     DEV_ALLOC(P.gaps, gaps);
     DEV_ALLOC(e->tile_ids, (int64_t)tile_ids_h.size());
+    DEV_ALLOC(e->blk_tab, (int64_t)blk_tab_h.size());
     DEV_ALLOC(P.heavy_in_unit, n_in_total); DEV_ALLOC(P.heavy_in_idx, n_in_total);
     {   // long enumerations: a list entry per span plus the extra entries of the split ones (an eighth of the class + 64), two
         // scratch slots per extra entry
@@ -1515,6 +1540,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     HIPCHK(hipMemcpyAsync(e->seg_in, seg_in.data(), sizeof(uint32_t) * seg_in.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->seg_out, seg_out.data(), sizeof(uint32_t) * seg_out.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->tile_ids, tile_ids_h.data(), sizeof(int32_t) * tile_ids_h.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->blk_tab, blk_tab_h.data(), sizeof(BlockRef) * blk_tab_h.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->slot_unit, slot_unit_h.data(), sizeof(int32_t) * slot_unit_h.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->seg_gap, seg_gap_h.data(), sizeof(uint32_t) * seg_gap_h.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->seg_gap_end, seg_gap_end_h.data(), sizeof(uint32_t) * seg_gap_end_h.size(), hipMemcpyHostToDevice, e->stream));

@@ -2,7 +2,8 @@
 //
 // Kernel map (reference function -> kernel), paths under
 // /root/reference/src/trace_reconstructor/ports/python/algorithms/:
-//   k_block_params      ComputeEpPairDistParams3            traceweaver_v3.py:580-646
+//   k_block_params_wave (k_block_params)
+//                       ComputeEpPairDistParams3            traceweaver_v3.py:580-646
 //   k_enumerate_tile (tw_tile.h) / k_enumerate_heavy
 //                       FindCutoffs + DfsTraverseX/3 + ScoreAssignmentAsPerInvocationGraph + heap top-5
 //                                                           traceweaver_v3.py:182-351, traceweaver_v1.py:259-361
@@ -206,8 +207,53 @@ __global__ void k_place_ends(Dev P, TileSet S, const int32_t* d_in, const int32_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Pass-1 Gaussian parameters: one thread per (unit, 100-span block, slot).
+// Pass-1 Gaussian parameters of a (unit, 100-span block, slot):
 // mean = (sum t2 - sum t1)/n over rank-aligned sorted arrays, std = sqrt(ceil(n/10)) * tstd(batch means).
+// The arrays a unit's slots subtract, by number: 0 in_start, 1 in_end_sorted, 2 + 2e out_start and 3 + 2e out_end_sorted of endpoint e.
+constexpr int kParamArrays = 2 + 2 * kMaxEp;
+__device__ __forceinline__ const int64_t* param_array(const Dev& P, const UnitDev& U, int id) {
+    if (id < 2) return (id == 0 ? P.in_start : P.in_end_sorted) + U.in_off;
+    return ((id & 1) ? P.out_end_sorted : P.out_start) + U.ep_off[(id - 2) >> 1];
+}
+// slot q scores t2 - t1 of the arrays a2, a1; false: the slot is not scored
+__device__ __forceinline__ bool param_slot(const UnitDev& U, int q, int& a1, int& a2) {
+    const int E = U.E;
+    if (q < E) {  // root(in -> e): only when e has no DAG predecessor
+        a1 = 0; a2 = 2 + 2 * q;
+        return U.npred[q] == 0;
+    }
+    if (q < E + E * E) {
+        const int p = (q - E) / E, e = (q - E) % E;
+        bool prim = false;
+        for (int j = 0; j < U.npred[e]; j++) prim |= (U.pred_list[e][j] == p && U.pred_prim[e][j]);
+        a1 = 3 + 2 * p; a2 = 2 + 2 * e;
+        return prim;
+    }
+    a1 = 3 + 2 * (q - E - E * E); a2 = 1;
+    return true;
+}
+// Load-scaled unit: Python's sum() over floats adds left to right in binary64 (helpers/transforms.py:21,30 make every timestamp
+// a float); the timestamps are exact images of those floats, and scaling by a power of two commutes with every rounding of the
+// parameters, so the scale is applied once at the end.  The order is part of the result: one thread walks the block.
+__device__ __forceinline__ int param_sums_float(const int64_t* t1, const int64_t* t2, int a, int len, int bs, double* bm, double& mean) {
+    double s1 = 0.0, s2 = 0.0;
+    int m = 0;
+    for (int kb = 0; kb < 10; kb++) {
+        const int st = kb * bs, en = min((kb + 1) * bs, len);
+        if (en - st <= 0) continue;
+        double u1 = 0.0, u2 = 0.0;
+        for (int i = a + st; i < a + en; i++) {
+            const double v1 = (double)t1[i], v2 = (double)t2[i];
+            u1 += v1; u2 += v2; s1 += v1; s2 += v2;
+        }
+        bm[m++] = (u2 - u1) / (double)(en - st);
+    }
+    mean = (s2 - s1) / (double)len;
+    return m;
+}
+__device__ __forceinline__ void param_finish(const Dev& P, const UnitDev& U, const double* bm, int m, int bs, double mean, double* out);
+
+// One thread per (unit, block, slot) of the whole batch (TW_BLOCK_PARAMS=0: A/B runs, bisection; k_block_params_wave is what runs).
 __global__ void k_block_params(Dev P, int64_t total, int cls) {   // cls > 0: only the units of that endpoint count (a class' launch on its own stream)
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -220,22 +266,11 @@ __global__ void k_block_params(Dev P, int64_t total, int cls) {   // cls > 0: on
     const UnitDev& U = P.units[lo];
     if (cls > 0 && U.E != cls) return;
     const int64_t r = g - U.gp_off;
-    const int b = (int)(r / U.nslot), q = (int)(r % U.nslot), E = U.E;
+    const int b = (int)(r / U.nslot), q = (int)(r % U.nslot);
     double* out = P.gparam + g * 4;
-    const int64_t *t1 = nullptr, *t2 = nullptr;
-    if (q < E) {  // root(in -> e): only when e has no DAG predecessor
-        if (U.npred[q] == 0) { t1 = P.in_start + U.in_off; t2 = P.out_start + U.ep_off[q]; }
-    } else if (q < E + E * E) {
-        const int p = (q - E) / E, e = (q - E) % E;
-        bool prim = false;
-        for (int j = 0; j < U.npred[e]; j++) prim |= (U.pred_list[e][j] == p && U.pred_prim[e][j]);
-        if (prim) { t1 = P.out_end_sorted + U.ep_off[p]; t2 = P.out_start + U.ep_off[e]; }
-    } else {
-        const int e = q - E - E * E;
-        t1 = P.out_end_sorted + U.ep_off[e];
-        t2 = P.in_end_sorted + U.in_off;
-    }
-    if (t1 == nullptr) { out[0] = out[1] = out[2] = out[3] = dnan(); return; }
+    int a1, a2;
+    if (!param_slot(U, q, a1, a2)) { out[0] = out[1] = out[2] = out[3] = dnan(); return; }
+    const int64_t *t1 = param_array(P, U, a1), *t2 = param_array(P, U, a2);
     const int a = b * P.batch_size, z = min(a + P.batch_size, U.n_in), len = z - a;
     double bm[10], mean;
     const int bs = (len + 9) / 10;
@@ -251,22 +286,12 @@ __global__ void k_block_params(Dev P, int64_t total, int cls) {   // cls > 0: on
             bm[m++] = (double)(u2 - u1) / (double)(en - st);
         }
         mean = (double)(s2 - s1) / (double)len;
-    } else {  // load-scaled unit: Python's sum() over floats adds left to right in binary64 (helpers/transforms.py:21,30
-              // make every timestamp a float); the timestamps are exact images of those floats, and scaling by a power
-              // of two commutes with every rounding below, so the scale is applied once at the end
-        double s1 = 0.0, s2 = 0.0;
-        for (int kb = 0; kb < 10; kb++) {
-            const int st = kb * bs, en = min((kb + 1) * bs, len);
-            if (en - st <= 0) continue;
-            double u1 = 0.0, u2 = 0.0;
-            for (int i = a + st; i < a + en; i++) {
-                const double v1 = (double)t1[i], v2 = (double)t2[i];
-                u1 += v1; u2 += v2; s1 += v1; s2 += v2;
-            }
-            bm[m++] = (u2 - u1) / (double)(en - st);
-        }
-        mean = (s2 - s1) / (double)len;
-    }
+    } else m = param_sums_float(t1, t2, a, len, bs, bm, mean);
+    param_finish(P, U, bm, m, bs, mean, out);
+}
+
+// Batch means -> what the scorer reads (both kernels: the same operations in the same order)
+__device__ __forceinline__ void param_finish(const Dev& P, const UnitDev& U, const double* bm, int m, int bs, double mean, double* out) {
     const double mu = np_sum(bm, m) / (double)m;
     double d2[10];
     for (int kb = 0; kb < m; kb++) { const double d = bm[kb] - mu; d2[kb] = d * d; }
@@ -278,6 +303,108 @@ __global__ void k_block_params(Dev P, int64_t total, int cls) {   // cls > 0: on
     // bit for bit when tscale is a power of two, so the mean stays in timestamp units and the divisor is rescaled;
     // tw_get_gauss_params reports the mean in microseconds.
     out[0] = mean; out[1] = sd; out[2] = tw_log(used); out[3] = used / U.tscale;
+}
+
+// One wavefront per group of consecutive blocks of a unit, from a table built at load (tw_load_batch: the groups of every unit, then
+// those of each endpoint-count class, in unit order -- a class' launch starts its own wavefronts only, nothing is searched).  The lanes
+// go over a block's spans: every array the block's slots subtract is read once, neighbouring lanes neighbouring spans, and added into
+// the array's ten sub-batch sums in LDS -- exact integers, so the order of the adds is free.  Then one lane per (block of the group,
+// slot) finishes its slot from the sums with param_finish: a group is as many blocks as fill the wavefront's lanes with slots or its
+// table of sums, whichever is fewer (a wavefront that finishes the 3 slots of a single-endpoint block issues the whole division /
+// square root / logarithm sequence for 3 lanes).  (The thread-per-slot kernel walked two arrays per live slot, 800 B between
+// neighbouring lanes, and two thirds of its threads had no slot to score or belonged to another class.)  A load-scaled unit keeps its
+// left-to-right binary64 sums: a lane per live slot walks the block.  Runs with any number of lanes per wavefront (host emulation: one).
+constexpr int kParamWaves = 4;     // wavefronts per workgroup
+constexpr int kParamSums = 256;    // sums (8 B) of LDS per wavefront: at least one block of kMaxEp endpoints
+static_assert(kParamArrays * 10 <= kParamSums, "a block's sums fit the wavefront's table");
+static_assert(kMaxEp * kMaxEp + 2 * kMaxEp <= 128, "a lane finishes at most two slots");
+__host__ __device__ inline int param_group(int E) {   // blocks per wavefront of a unit with E endpoints
+    const int by_lanes = 64 / (E * E + 2 * E), by_sums = kParamSums / ((2 + 2 * E) * 10), g = by_lanes < by_sums ? by_lanes : by_sums;
+    return g > 1 ? g : 1;
+}
+struct BlockRef {   // the blocks blk .. blk + param_group(E) - 1 of a unit, as far as it has them
+    int32_t unit, blk;
+};
+
+// Slot q of a block from the block's sub-batch sums (a load-scaled unit: from its spans)
+__device__ __forceinline__ void param_slot_finish(const Dev& P, const UnitDev& U, const unsigned long long* sum, int q, int a, int len, int bs, double* out) {
+    int a1, a2;
+    if (!param_slot(U, q, a1, a2)) { out[0] = out[1] = out[2] = out[3] = dnan(); return; }
+    double bm[10], mean;
+    int m = 0;
+    if (!U.float_time) {  // integer microseconds: Python sums ints exactly, one correctly rounded division
+        int64_t s1 = 0, s2 = 0;
+        for (int kb = 0; kb < 10; kb++) {
+            const int st = kb * bs, en = min((kb + 1) * bs, len);
+            if (en - st <= 0) continue;
+            const int64_t u1 = (int64_t)sum[a1 * 10 + kb], u2 = (int64_t)sum[a2 * 10 + kb];
+            s1 += u1; s2 += u2;
+            bm[m++] = (double)(u2 - u1) / (double)(en - st);
+        }
+        mean = (double)(s2 - s1) / (double)len;
+    } else m = param_sums_float(param_array(P, U, a1), param_array(P, U, a2), a, len, bs, bm, mean);
+    param_finish(P, U, bm, m, bs, mean, out);
+}
+// ... of the group's t-th (block, slot)
+__device__ __forceinline__ void param_group_finish(const Dev& P, const UnitDev& U, const unsigned long long* sum, int blk0, int t) {
+    const int g = t / U.nslot, q = t - g * U.nslot;
+    const int a = (blk0 + g) * P.batch_size, len = min(a + P.batch_size, U.n_in) - a;
+    param_slot_finish(P, U, sum + g * (2 + 2 * U.E) * 10, q, a, len, (len + 9) / 10, P.gparam + (U.gp_off + (int64_t)(blk0 + g) * U.nslot + q) * 4);
+}
+
+// One span of every array of a unit with N endpoints into its sub-batch sums (sum: the sub-batch's entry of array 0): the incoming
+// spans' (p = 0), then every endpoint's -- starts and sorted ends share their index.  N is a compile-time constant so that all
+// 2 (N + 1) loads are issued before the first add (as a loop over the unit's endpoints every pair of loads was waited for on its own).
+template <int N>
+__device__ __forceinline__ void param_add_spans(const Dev& P, const UnitDev& U, int E, int i, unsigned long long* sum) {
+    if (E != N) {
+        if constexpr (N < kMaxEp) param_add_spans<N + 1>(P, U, E, i, sum);
+        return;
+    }
+    int64_t v[2 * (N + 1)];
+#pragma unroll
+    for (int p = 0; p <= N; p++) {
+        const int64_t at = (p == 0 ? U.in_off : U.ep_off[p == 0 ? 0 : p - 1]) + i;
+        v[2 * p] = (p == 0 ? P.in_start : P.out_start)[at];
+        v[2 * p + 1] = (p == 0 ? P.in_end_sorted : P.out_end_sorted)[at];
+    }
+#pragma unroll
+    for (int p = 0; p <= N; p++) {
+        atomicAdd(&sum[(2 * p) * 10], (unsigned long long)v[2 * p]);
+        atomicAdd(&sum[(2 * p + 1) * 10], (unsigned long long)v[2 * p + 1]);
+    }
+}
+
+__global__ void __launch_bounds__(64 * kParamWaves) k_block_params_wave(Dev P, const BlockRef* groups, int n_groups) {
+    __shared__ unsigned long long sh_sum[kParamWaves][kParamSums];
+    const int W = min((int)blockDim.x, 64), wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+    const int64_t item = (int64_t)blockIdx.x * (blockDim.x >= 64 ? blockDim.x / 64 : 1) + wave;
+    if (wave >= kParamWaves || item >= n_groups) return;   // (the whole wavefront)
+    // (the wavefront's group as scalars: the unit's descriptor is then read by scalar loads, once, instead of by every lane where it is used)
+    const int unit = __builtin_amdgcn_readfirstlane(groups[item].unit), blk0 = __builtin_amdgcn_readfirstlane(groups[item].blk);
+    const UnitDev& U = P.units[unit];
+    const int E = U.E, na = 2 + 2 * E, nb = min(param_group(E), U.nblk - blk0);
+    unsigned long long* sum = sh_sum[wave];
+    if (!U.float_time) {
+        for (int k = lane; k < nb * na * 10; k += W) sum[k] = 0ull;
+        wave_sync();
+        for (int g = 0; g < nb; g++) {
+            const int a = (blk0 + g) * P.batch_size, len = min(a + P.batch_size, U.n_in) - a, bs = (len + 9) / 10;
+            for (int i = lane; i < len; i += W)   // (len <= batch_size, whatever that is: a lane takes spans lane, lane + W, ...)
+                param_add_spans<1>(P, U, E, a + i, sum + g * na * 10 + i / bs);
+        }
+        wave_sync();
+    }
+    const int n_fin = nb * U.nslot;   // at most 64, or the slots of one block
+#ifdef TW_HOST_EMULATION   // (any number of lanes)
+    for (int t = lane; t < n_fin; t += W) param_group_finish(P, U, sum, blk0, t);
+#else
+    // Two slots a lane at the most, written out: as a loop over the slots the constants of the division, square root and logarithm
+    // sequences stayed in registers across it, 126 registers where the code needs 80 -- and a wavefront of 126 finds no room on a SIMD
+    // that the tile kernels of the other classes have filled.
+    if (lane < n_fin) param_group_finish(P, U, sum, blk0, lane);
+    if (lane + 64 < n_fin) param_group_finish(P, U, sum, blk0, lane + 64);
+#endif
 }
 
 // Mixture constants for pass 2: [slot][comp] = mean * prec_chol, prec_chol * tscale, log(prec_chol), log(weight).

@@ -43,6 +43,10 @@ VARIANTS = {
     "lean2": ["-DTW_LEAN_ATTR=__attribute__((amdgpu_waves_per_eu(2,2)))"],
     "dp96": ["-DTW_DP_CAP=96", "-DTW_DP_SLOTS=128"],       # round 6: tables of k_select_dp (states a level, hash slots): LDS per workgroup 69 -> 34 / 46 KB
     "dp192": ["-DTW_DP_CAP=192", "-DTW_DP_SLOTS=256"],
+    "rank24": ["-DTW_TILE_RANK_DIRECT=24"],                # round 9: spans of more than 24 / 64 tuple slots ranked among their survivors (default 32; 24 is the least the layout holds)
+    "rank64": ["-DTW_TILE_RANK_DIRECT=64"],
+    "tile1024": ["-DTW_TILE_MAX=1024"],                    # ... and the tile limit again, now that ranks are linear (a span per segment of 1024 slots)
+    "proftile4": ["-DTW_PROFILE_TILE"],                    # phase times of a four-endpoint tile
 }
 
 

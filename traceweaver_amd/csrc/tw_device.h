@@ -173,6 +173,7 @@ struct Dev {
     int32_t lean_min_e;        // classes from this many endpoints on are enumerated by k_enumerate_lean (TW_LEAN_MIN_E, default 5; 9 = none)
     int32_t tile_max_deep;     // ... and take over from the tile kernel from this many tuples on (TW_TILE_MAX_DEEP <= kTileMax)
     int32_t lean_grid;         // ... which walks enumerations of up to this many grid points as a grid and lists the others (TW_LEAN_GRID)
+    int32_t tile_rank;         // k_enumerate_tile ranks the long spans of a segment among their compacted survivors (TW_TILE_RANK, default 1; 0 = every tuple scans its span: A/B runs, bisection)
     // pair-term tables that do not fit the wavefront's (small) LDS pool: slots of kPairSpill doubles in global memory, claimed by the
     // wavefronts that need one (pool_acquire), kept until the wavefront ends
     double* pair_pool;

@@ -114,6 +114,7 @@ struct tw_engine {
     int tile = kTile;   // incoming spans (threads) per workgroup of the per-span kernels
     int tile_threads = 2; // threads per incoming span of k_enumerate_tile (its items and tuples are spread over all of them)
     int tile_single = 1;  // TW_TILE_SINGLE: the one-endpoint class takes the lean path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int tile_rank = 1;    // TW_TILE_RANK: the general path of k_enumerate_tile ranks long spans among their compacted survivors (0 = the all-pairs loop: A/B runs, bisection)
     int block_params = 1; // TW_BLOCK_PARAMS: pass-1 block parameters by a wavefront per group of blocks (0 = the thread-per-slot kernel: A/B runs, bisection)
     int tile_single_threads = 1;   // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
     int coop = kCoop;   // threads of the per-unit cooperative kernels
@@ -1103,6 +1104,7 @@ int tw_create(int device_id, tw_engine** out) {
     e->tile_threads = std::min(std::max(env_int("TW_TILE_THREADS", 2), 1), 4);
     e->tile_single = env_int("TW_TILE_SINGLE", 1);
     e->block_params = env_int("TW_BLOCK_PARAMS", 1);
+    e->tile_rank = env_int("TW_TILE_RANK", 1) != 0 ? 1 : 0;
     e->tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
     e->coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
     // The engine runs its endpoint-count classes and window classes on streams of their own (up to 8 + 3 beside its own).  The
@@ -1376,6 +1378,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     P.lean_min_e = env_int("TW_LEAN_MIN_E", 5);
     P.lean_grid = std::max(env_int("TW_LEAN_GRID", TW_LEAN_GRID), 1);
     P.tile_max_deep = std::min(std::max(env_int("TW_TILE_MAX_DEEP", kTileMax), 0), kTileMax);
+    P.tile_rank = e->tile_rank;
     int rc;
     e->arena_req.clear();
     e->arena_open = true;

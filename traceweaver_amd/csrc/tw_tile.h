@@ -24,7 +24,8 @@
 //      the tuples of rank < 5, in rank order, whenever none of those is incomparable with another tuple of equal score:
 //      such a tuple is comparable with everything, so whenever it is the root of the six-entry heap it is its true minimum,
 //      has five greater tuples and rank >= 5 -- a tuple of rank < 5 is never popped.  A span where a tuple of rank < 5 has
-//      an incomparable partner goes to the wavefront kernel, which replays CPython's heap push by push.
+//      an incomparable partner goes to the wavefront kernel, which replays CPython's heap push by push.  A span of more than
+//      kRankDirect slots is counted among its survivors only: the tuples that reach a lower bound of its fifth-largest score.
 // Spans whose enumeration is longer than kTileMax tuples, whose windows are wider than 32 spans or reach beyond the staged
 // slice, or that are too long for 32-bit offsets go to the work lists of k_enumerate_heavy, as before.
 #pragma once
@@ -39,6 +40,21 @@ constexpr int kTileMax = TW_TILE_MAX;   // largest enumeration (product of the c
 #define TW_TILE_REPLAY_MAX 256
 #endif
 constexpr int kTileReplayMax = TW_TILE_REPLAY_MAX;   // most feasible tuples of a span whose heap its own thread replays (phase 5b); the others go to the wavefront kernel
+// Phase 5 ranks a span of more than kRankDirect (padded) tuple slots among its survivors only: the feasible tuples whose score reaches a
+// lower bound L of the span's fifth-largest score.  Shorter spans keep the in-place loop over all their slots.
+#ifndef TW_TILE_RANK_DIRECT
+#define TW_TILE_RANK_DIRECT 32
+#endif
+constexpr int kRankDirect = TW_TILE_RANK_DIRECT;
+constexpr int kRankMinLong = (kRankDirect & ~3) + 4;   // fewest slots of a long span (slot counts are multiples of four): the long spans of a segment start at least this far apart
+constexpr int kRankBuckets = 5;                        // = kTopK disjoint subsets of a span's slots; L = the smallest of their maxima
+static_assert(kRankDirect >= 24, "the maxima and counters of a segment's long spans lie in one byte per tuple slot");
+// the upper half of a score's order-preserving unsigned key (-0.0 taken for +0.0 first): a score with a smaller key is strictly
+// smaller, scores with equal keys may differ; no score has the key 0
+__device__ __forceinline__ uint32_t score_key32(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
+    return (uint32_t)(((u >> 63) ? ~u : (u | (1ull << 63))) >> 32);
+}
 // items of a span before those of endpoint e (contained candidates per endpoint, 8 bits each, in pk)
 __device__ __forceinline__ int pos_base(unsigned long long pk, int e) {
     int acc = 0;
@@ -153,7 +169,8 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
     __shared__ double t_root[C::kItems], t_close[C::kItems];
     __shared__ uint16_t it_idx[C::kItems];                // slice position of the item's candidate
     __shared__ double g_sc[C::kGrid];
-    __shared__ uint8_t g_span[C::kGrid], g_rank[C::kGrid];   // the tuple's span (tile-local) / its rank; an infeasible grid point has score NaN
+    __shared__ uint8_t g_span[C::kGrid];                   // the tuple's span (tile-local); an infeasible grid point has score NaN
+    __shared__ uint32_t g_aux[C::kGrid / 4];               // phase 5 of a segment: the long spans' subset maxima and survivor counts (the ranks themselves: in t_root)
     __shared__ int32_t s_segend, s_anyamb;                 // ... any span of the segment whose top five the ranks do not decide (phase 5b)
     const bool live = t < ns;
     const int i = first + (live ? t : 0);
@@ -518,6 +535,24 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
     } else
     // ---- segments of the tile: as many spans as the tables hold ------------------------------------------------------
     for (int seg = 0; seg < ns;) {
+        // Phase 5 ranks a long span (more than kRankDirect slots) among its survivors only.  Its slots fall into five subsets by slot
+        // number mod 5; L = the smallest of the subsets' largest feasible scores (none: everything survives), taken on 32-bit keys as
+        // phase 4 forms the scores.  Five distinct tuples reach L, so a tuple whose key is below L has five strictly greater ones: rank
+        // >= 5, which is all that is ever stored of it.  A tuple that reaches L survives, and so does every tuple that is greater than or
+        // equal to it: its count of greater tuples, its equal partners and their comparisons are those of the whole span.  The survivors
+        // (about eleven of a span, all of them when the scores are equal) are listed twice: per span from the span's own first slot on,
+        // to be scanned, and in one list of the segment, a lane each.  The term tables are free between phase 4 and phase 5b: t_root
+        // holds the ranks, t_close the two lists of 16-bit slot numbers.  A long span is found by its first slot / kRankMinLong.
+        constexpr int kLong = (C::kGrid - kRankMinLong) / kRankMinLong + 1;
+        constexpr bool kRankFits = kLong * (kRankBuckets + 1) + 1 <= C::kGrid / 4 && C::kGrid * 4 <= C::kItems * 8 && C::kGrid <= 65536;
+        static_assert(kRankBuckets == kTopK && C::kGrid <= C::kItems * 8, "a subset of slots per entry of the list; a rank per slot in t_root");
+        uint32_t* const r_max = g_aux;                                                     // [kLong][kRankBuckets] keys, 0: no feasible tuple
+        int32_t* const r_cnt = reinterpret_cast<int32_t*>(g_aux + kLong * kRankBuckets);   // [kLong] survivors of the span, [kLong]: of the segment
+        uint8_t* const g_rank = reinterpret_cast<uint8_t*>(t_root);                        // [kGrid] the tuple's rank (from phase 5 on)
+        uint16_t* const r_sub = reinterpret_cast<uint16_t*>(t_close);                      // [kGrid] a span's survivors from its first slot on
+        uint16_t* const r_all = r_sub + C::kGrid;                                          // [kGrid] the survivors of the segment
+        const bool compact = kRankFits && P.tile_rank != 0;   // (an instantiation whose tables do not hold the lists keeps the loop over all slots)
+        if (compact) for (int x = fresh(t); x < kLong * (kRankBuckets + 1) + 1; x += nt) g_aux[x] = 0u;
         if (t == 0) { s_segend = ns; s_anyamb = 0; }
         group_sync();
         if (live && t >= seg && (s_item0[t + 1] - s_item0[seg] > C::kItems || s_grid0[t + 1] - s_grid0[seg] > C::kGrid)) atomicMin(&s_segend, t);
@@ -602,16 +637,74 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
             }
             g_sc[g] = ok ? sj : dnan();
             g_span[g] = (uint8_t)s;
+            if (compact && ok && s_grid0[s + 1] - s_grid0[s] > kRankDirect) {   // a long span: the largest key of the slot's subset
+                uint32_t* b = r_max + ((g - gi) / kRankMinLong) * kRankBuckets + gi % kRankBuckets;
+                const uint32_t key = score_key32(sj);
+                if (key > *(volatile uint32_t*)b) atomicMax(b, key);   // (most lanes find a greater one there already)
+            }
         }
         group_sync();
         TW_TILE_TICK(4);
         // ---- 5. rank of every tuple among the tuples of its span ------------------------------------------------------
+        // Python's order of two tuples of a span with equal scores: start_mus of the first differing span (spans.py:51-52).
+        // +1: the other one (slot hrel of the span) is greater, -1: smaller, 0: incomparable
+        auto order_equal = [&](int s, const int32_t (&ia)[E], int hrel) -> int {
+            int32_t kb[E], ib[E];
+            decode(s, hrel, it0, kb, ib);
+            int ord = 0;
+            bool done = false;
+#pragma unroll
+            for (int e = 0; e < E; e++)
+                if (!done && ia[e] != ib[e]) {
+                    const int32_t a = sl_st[e][ia[e]], b = sl_st[e][ib[e]];
+                    ord = b > a ? 1 : (b < a ? -1 : 0);
+                    done = true;
+                }
+            return ord;
+        };
+        if (compact) {
+            const int tr = fresh(t);   // (what the lists' addresses are formed from: here, not ahead of the segment loop)
+            for (int gb = 0; gb < nG; gb += nt) {   // (the same trips for every lane: the appends are the wavefront's)
+                const int g = gb + tr, lane = tr & 63;
+                bool surv = false;
+                int sub0 = 0;   // a survivor: the first slot of its span
+                if (g < nG) {
+                    const double my = g_sc[g];
+                    const int s = g_span[g];
+                    const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
+                    if (ge - gs > kRankDirect && my == my) {
+                        const uint32_t* b = r_max + (gs / kRankMinLong) * kRankBuckets;
+                        uint32_t lk = b[0];
+#pragma unroll
+                        for (int j = 1; j < kRankBuckets; j++) lk = b[j] < lk ? b[j] : lk;
+                        surv = score_key32(my) >= lk;   // (lk = 0, a subset without a feasible tuple: everything survives)
+                        sub0 = gs;
+                    }
+                }
+                const int at = wave_append(&r_cnt[kLong], surv, lane);
+                if (surv) r_all[at] = (uint16_t)g;
+                // the span's own list: one atomic per wavefront and span that has survivors among the lanes
+                unsigned long long todo = __ballot(surv);
+                while (todo != 0ull) {
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const int lead0 = __shfl(sub0, leader);
+                    const bool with = surv && sub0 == lead0;
+                    const unsigned long long m = __ballot(with);
+                    int base = 0;
+                    if (lane == leader) base = atomicAdd(&r_cnt[lead0 / kRankMinLong], __popcll(m));
+                    base = __shfl(base, leader);
+                    if (with) r_sub[lead0 + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)g;
+                    todo &= ~m;
+                }
+            }
+        }
         for (int g = t; g < nG; g += nt) {
             const double my = g_sc[g];
             int rank = kTopK;
+            const int s = g_span[g];
+            const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
+            if (compact && ge - gs > kRankDirect) { g_rank[g] = (uint8_t)kTopK; continue; }   // (a survivor's own rank follows behind the barrier)
             if (my == my) {
-                const int s = g_span[g];
-                const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
                 rank = 0;
                 bool partner = false;
                 // four scores a step (the span's slots are padded to a multiple of four with NaN, which compares as neither
@@ -629,17 +722,7 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
                     decode(s, g - gs, it0, ka, ia);
                     for (int h = gs; h < ge; h++) {
                         if (h == g || !(g_sc[h] == my)) continue;
-                        int32_t kb[E], ib[E];
-                        decode(s, h - gs, it0, kb, ib);
-                        int ord = 0;   // +1: h is greater
-                        bool done = false;
-#pragma unroll
-                        for (int e = 0; e < E; e++)
-                            if (!done && ia[e] != ib[e]) {
-                                const int32_t a = sl_st[e][ia[e]], b = sl_st[e][ib[e]];
-                                ord = b > a ? 1 : (b < a ? -1 : 0);
-                                done = true;
-                            }
+                        const int ord = order_equal(s, ia, h - gs);
                         if (ord > 0) rank++;
                         else if (ord == 0) partner = true;
                     }
@@ -647,6 +730,38 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
                 if (partner && rank < kTopK) { s_amb[s] = 1; s_anyamb = 1; }
             }
             g_rank[g] = (uint8_t)(rank < kTopK ? rank : kTopK);
+        }
+        if (compact) {   // a survivor per lane: the greater ones, the equal ones, among the survivors of its span
+            group_sync();
+            const int nsv = r_cnt[kLong];
+            for (int k = fresh(t); k < nsv; k += nt) {
+                const int g = r_all[k];
+                const double my = g_sc[g];
+                const int s = g_span[g];
+                const int gs = s_grid0[s] - g0;
+                const int n = r_cnt[gs / kRankMinLong];
+                const uint16_t* sub = r_sub + gs;
+                int rank = 0, eq = 0;
+                for (int h = 0; h < n && rank < kTopK; h++) {
+                    const double o = g_sc[sub[h]];
+                    rank += (o > my);
+                    eq += (o == my);
+                }
+                bool partner = false;
+                if (eq > 1 && rank < kTopK) {
+                    int32_t ka[E], ia[E];
+                    decode(s, g - gs, it0, ka, ia);
+                    for (int h = 0; h < n; h++) {
+                        const int hg = sub[h];
+                        if (hg == g || !(g_sc[hg] == my)) continue;
+                        const int ord = order_equal(s, ia, hg - gs);
+                        if (ord > 0) rank++;
+                        else if (ord == 0) partner = true;
+                    }
+                }
+                if (partner && rank < kTopK) { s_amb[s] = 1; s_anyamb = 1; }
+                g_rank[g] = (uint8_t)(rank < kTopK ? rank : kTopK);
+            }
         }
         group_sync();
         TW_TILE_TICK(5);

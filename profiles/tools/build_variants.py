@@ -47,6 +47,8 @@ VARIANTS = {
     "rank64": ["-DTW_TILE_RANK_DIRECT=64"],
     "tile1024": ["-DTW_TILE_MAX=1024"],                    # ... and the tile limit again, now that ranks are linear (a span per segment of 1024 slots)
     "proftile4": ["-DTW_PROFILE_TILE"],                    # phase times of a four-endpoint tile
+    "proftile2": ["-DTW_PROFILE_TILE", "-DTW_PROFILE_TILE_E=2"],   # round 10: ... of a two-endpoint tile (TW_TILE_PAIR=0: on the general path)
+    "pair5": ["-DTW_TILE_PAIR_WAVES=5"],                   # ... the pair path compiled for five wavefronts per SIMD (96 registers; default 4)
 }
 
 

@@ -117,6 +117,8 @@ struct tw_engine {
     int tile_rank = 1;    // TW_TILE_RANK: the general path of k_enumerate_tile ranks long spans among their compacted survivors (0 = the all-pairs loop: A/B runs, bisection)
     int block_params = 1; // TW_BLOCK_PARAMS: pass-1 block parameters by a wavefront per group of blocks (0 = the thread-per-slot kernel: A/B runs, bisection)
     int tile_single_threads = 1;   // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
+    int tile_pair = 1;    // TW_TILE_PAIR: the two-endpoint class takes the pair path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int tile_pair_threads = 2;   // TW_TILE_PAIR_THREADS: threads per incoming span on that path (1 or 2)
     int coop = kCoop;   // threads of the per-unit cooperative kernels
     std::vector<UnitDev> units;
     std::vector<TileDev> tiles;
@@ -537,7 +539,8 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
         // cut-offs and work lists, the short enumerations: the tile kernel.  A class of few tiles: several workgroups per tile, until
         // the class fills the CUs twice over
         const bool single = E == 1 && e->tile_single != 0;
-        const dim3 tile_block(e->tile >= 64 ? e->tile * (single ? e->tile_single_threads : e->tile_threads) : e->tile);
+        const bool pair = E == 2 && e->tile_pair != 0;
+        const dim3 tile_block(e->tile >= 64 ? e->tile * (single ? e->tile_single_threads : (pair ? e->tile_pair_threads : e->tile_threads)) : e->tile);
         int sub = 1;
         while (sub < e->tile_sub_max && nt * sub < 512 && (e->tile / (sub * 2)) * (sub * 2) == e->tile && e->tile / (sub * 2) >= 8) sub *= 2;
         // A class of many tiles in stretches: what a stretch's tiles listed for the wavefront kernel is enumerated on the class' second
@@ -555,9 +558,14 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
                 if (single && sub_tile) hipLaunchKernelGGL((k_enumerate_tile<1, kSubTileSpans, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
                 else if (single) hipLaunchKernelGGL((k_enumerate_tile<1, kTile, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
             }
-            if (!single && sub_tile)
+            if constexpr (E == 2) {   // (the pair path: instantiated for two endpoints only)
+                if (pair && sub_tile) hipLaunchKernelGGL((k_enumerate_tile<2, kSubTileSpans, false, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
+                else if (pair) hipLaunchKernelGGL((k_enumerate_tile<2, kTile, false, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
+            }
+            if (single || pair) {}
+            else if (sub_tile)
                 hipLaunchKernelGGL((k_enumerate_tile<E, kSubTileSpans>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            else if (!single)
+            else
                 hipLaunchKernelGGL((k_enumerate_tile<E>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
             if (ns > 1) {
                 hipLaunchKernelGGL(k_enum_snapshot, dim3(1), dim3(1), 0, st, P, E, j + 1);
@@ -1106,6 +1114,8 @@ int tw_create(int device_id, tw_engine** out) {
     e->block_params = env_int("TW_BLOCK_PARAMS", 1);
     e->tile_rank = env_int("TW_TILE_RANK", 1) != 0 ? 1 : 0;
     e->tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
+    e->tile_pair = env_int("TW_TILE_PAIR", 1);
+    e->tile_pair_threads = std::min(std::max(env_int("TW_TILE_PAIR_THREADS", 2), 1), 2);
     e->coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
     // The engine runs its endpoint-count classes and window classes on streams of their own (up to 8 + 3 beside its own).  The
     // runtime multiplexes a process' streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default: classes that share a queue run one

@@ -71,16 +71,24 @@ __device__ __forceinline__ int pos_base(unsigned long long pk, int e) {
 // while smaller ones -- the wavefront kernels of the other classes -- keep taking what becomes free: the classes' tile kernels ran one
 // after the other.)
 constexpr int kSubTileSpans = kTile / 8;
-template <int E, int SPANS = kTile>
+#ifndef TW_TILE_PAIR_ITEMS
+#define TW_TILE_PAIR_ITEMS 512
+#define TW_TILE_PAIR_GRID 1024
+#endif
+// PAIR: the tables of the two-endpoint path (a span has at most 64 items; its tuple slots are not padded) -- a tile of the media
+// shape holds about 420 items and 430 tuples, one segment.  As many slots as the general path: a tile of the saturated nodejs shape
+// (840 items, 1 800 tuples) took 2.9 segments with 768 slots where the general path takes 2.4 -- every segment pays its barriers, a
+// last trip of mostly idle lanes and a replay phase as long as its longest replay (profiles/HISTORY.md, "Round 10").  31.5 KB of LDS
+template <int E, int SPANS = kTile, bool PAIR = false>
 struct TileCfg {
 #ifdef TW_TILE_SMALL   // host-emulation build of the tests: tiny tables, so that segments and slice overflows occur
-    static constexpr int kSlice = 24, kItems = kMaxEp * 32, kGrid = kTileMax > 64 ? kTileMax : 64;
+    static constexpr int kSlice = 24, kItems = PAIR ? 2 * 32 : kMaxEp * 32, kGrid = kTileMax > 64 ? kTileMax : 64;
 #else
     static constexpr int kSlice = SPANS < kTile ? 64 : (E <= 4 ? 192 : 160);   // outgoing spans staged per endpoint
-    static constexpr int kItems = SPANS < kTile ? kMaxEp * 32 : TW_TILE_ITEMS;   // (span, endpoint, candidate) items per segment of the tile
-    static constexpr int kGrid = SPANS < kTile ? (kTileMax > 512 ? kTileMax : 512) : TW_TILE_GRID;   // tuple slots per segment (a span's slots are padded to a multiple of four)
+    static constexpr int kItems = SPANS < kTile ? kMaxEp * 32 : (PAIR ? TW_TILE_PAIR_ITEMS : TW_TILE_ITEMS);   // (span, endpoint, candidate) items per segment of the tile
+    static constexpr int kGrid = SPANS < kTile ? (kTileMax > 512 ? kTileMax : 512) : (PAIR ? TW_TILE_PAIR_GRID : TW_TILE_GRID);   // tuple slots per segment (a span's slots are padded to a multiple of four; PAIR: not padded)
 #endif
-    static_assert(kItems >= kMaxEp * 32 && kGrid >= ((kTileMax + 3) & ~3) && kGrid % 4 == 0, "a single span must fit a segment");
+    static_assert(kItems >= (PAIR ? 2 : kMaxEp) * 32 && kGrid >= ((kTileMax + 3) & ~3) && kGrid % 4 == 0, "a single span must fit a segment");
 };
 
 // rest / c for 0 <= rest <= 4096, 1 <= c <= 64: (rest + 0.5) / c is at least 0.5 / c away from an integer, far more than the
@@ -102,6 +110,107 @@ __device__ __forceinline__ int fresh(int v) {
 #endif
     return v;
 }
+
+// Phase 5 of a segment for its long spans (more than kRankDirect slots), shared by the general and the two-endpoint path.  A long
+// span's slots fall into five subsets by slot number mod 5; L = the smallest of the subsets' largest feasible scores (none: everything
+// survives), taken on 32-bit keys as phase 4 forms the scores.  Five distinct tuples reach L, so a tuple whose key is below L has five
+// strictly greater ones: rank >= 5, which is all that is ever stored of it.  A tuple that reaches L survives, and so does every tuple
+// that is greater than or equal to it: its count of greater tuples, its equal partners and their comparisons are those of the whole
+// span.  The survivors (about eleven of a span, all of them when the scores are equal) are listed twice: per span from the span's own
+// first slot on, to be scanned, and in one list of the segment, a lane each.  A long span is found by its first slot / MINLONG (the
+// fewest slots of a long span: the long spans of a segment start at least that far apart).
+template <int GRID, int MINLONG>
+struct SurvivorRanks {
+    static constexpr int kLong = (GRID - MINLONG) / MINLONG + 1;
+    static constexpr int kAuxWords = kLong * (kRankBuckets + 1) + 1;
+    uint32_t* aux;          // [kLong][kRankBuckets] keys, 0: no feasible tuple; then [kLong] survivors of the span, [1]: of the segment
+    uint8_t* g_rank;        // [GRID] the tuple's rank
+    uint16_t* r_sub;        // [GRID] a span's survivors from its first slot on
+    uint16_t* r_all;        // [GRID] the survivors of the segment
+    const double* g_sc;     // [GRID] the scores of phase 4 (NaN: infeasible)
+    const uint8_t* g_span;  // [GRID] the slot's span
+    const int32_t* s_grid0; // prefix sums of the slots over the spans
+    int g0;                 // ... of the segment's first span
+    __device__ __forceinline__ uint32_t* r_max() const { return aux; }
+    __device__ __forceinline__ int32_t* r_cnt() const { return reinterpret_cast<int32_t*>(aux + kLong * kRankBuckets); }
+    __device__ __forceinline__ void clear(int t, int nt) const { for (int x = t; x < kAuxWords; x += nt) aux[x] = 0u; }
+    // phase 4, a feasible tuple of a long span (slot g, the gi-th of its span): the largest key of the slot's subset
+    __device__ __forceinline__ void note(int g, int gi, double sj) const {
+        uint32_t* b = r_max() + ((g - gi) / MINLONG) * kRankBuckets + gi % kRankBuckets;
+        const uint32_t key = score_key32(sj);
+        if (key > *(volatile uint32_t*)b) atomicMax(b, key);   // (most lanes find a greater one there already)
+    }
+    // the survivors of the long spans into the two lists (the same trips for every lane: the appends are the wavefront's)
+    __device__ __forceinline__ void collect(int nG, int tr, int nt) const {
+        for (int gb = 0; gb < nG; gb += nt) {
+            const int g = gb + tr, lane = tr & 63;
+            bool surv = false;
+            int sub0 = 0;   // a survivor: the first slot of its span
+            if (g < nG) {
+                const double my = g_sc[g];
+                const int s = g_span[g];
+                const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
+                if (ge - gs > kRankDirect && my == my) {
+                    const uint32_t* b = r_max() + (gs / MINLONG) * kRankBuckets;
+                    uint32_t lk = b[0];
+#pragma unroll
+                    for (int j = 1; j < kRankBuckets; j++) lk = b[j] < lk ? b[j] : lk;
+                    surv = score_key32(my) >= lk;   // (lk = 0, a subset without a feasible tuple: everything survives)
+                    sub0 = gs;
+                }
+            }
+            const int at = wave_append(&r_cnt()[kLong], surv, lane);
+            if (surv) r_all[at] = (uint16_t)g;
+            // the span's own list: one atomic per wavefront and span that has survivors among the lanes
+            unsigned long long todo = __ballot(surv);
+            while (todo != 0ull) {
+                const int leader = __ffsll((long long)todo) - 1;
+                const int lead0 = __shfl(sub0, leader);
+                const bool with = surv && sub0 == lead0;
+                const unsigned long long m = __ballot(with);
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&r_cnt()[lead0 / MINLONG], __popcll(m));
+                base = __shfl(base, leader);
+                if (with) r_sub[lead0 + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)g;
+                todo &= ~m;
+            }
+        }
+    }
+    // a survivor per lane (behind a barrier after collect): the greater ones, the equal ones, among the survivors of its span.
+    // mine_of(s, gi): what order(s, mine, hrel) needs of the tuple itself; order: +1 the other one (slot hrel of the span) is greater
+    // under Python's order of equal scores, -1 smaller, 0 incomparable; undecided(s): a tuple of rank < 5 has an incomparable partner
+    template <class MINE, class ORDER, class UNDECIDED>
+    __device__ __forceinline__ void rank(int t, int nt, const MINE& mine_of, const ORDER& order, const UNDECIDED& undecided) const {
+        const int nsv = r_cnt()[kLong];
+        for (int k = t; k < nsv; k += nt) {
+            const int g = r_all[k];
+            const double my = g_sc[g];
+            const int s = g_span[g];
+            const int gs = s_grid0[s] - g0;
+            const int n = r_cnt()[gs / MINLONG];
+            const uint16_t* sub = r_sub + gs;
+            int rank = 0, eq = 0;
+            for (int h = 0; h < n && rank < kTopK; h++) {
+                const double o = g_sc[sub[h]];
+                rank += (o > my);
+                eq += (o == my);
+            }
+            bool partner = false;
+            if (eq > 1 && rank < kTopK) {
+                const auto mine = mine_of(s, g - gs);
+                for (int h = 0; h < n; h++) {
+                    const int hg = sub[h];
+                    if (hg == g || !(g_sc[hg] == my)) continue;
+                    const int ord = order(s, mine, hg - gs);
+                    if (ord > 0) rank++;
+                    else if (ord == 0) partner = true;
+                }
+            }
+            if (partner && rank < kTopK) undecided(s);
+            g_rank[g] = (uint8_t)(rank < kTopK ? rank : kTopK);
+        }
+    }
+};
 
 // a term from the gap itself (score_term computes x = (double)(t2 - t1) and then exactly this)
 __device__ __forceinline__ double score_term_gap(const Scorer& S, int slot, long long gap) {
@@ -137,14 +246,23 @@ __device__ __forceinline__ double score_term_gap(const Scorer& S, int slot, long
 #ifdef TW_HOST_EMULATION
 #define TW_TILE_ATTR
 #else
-#define TW_TILE_ATTR __attribute__((amdgpu_waves_per_eu(SINGLE ? 8 : (E <= 4 ? 4 : 2))))
+#ifndef TW_TILE_PAIR_WAVES
+// wavefronts per SIMD the two-endpoint path is compiled for.  5 fits (96 registers, no scratch, five workgroups per CU by its LDS) and makes the
+// kernel itself shortest, but the step is shorter with 4 (the compiler then takes 97 registers): the class' tile kernel shares the SIMDs with the four-endpoint
+// one, whose chain is the pass, and at five wavefronts it takes them from it (profiles/HISTORY.md, "Round 10")
+#define TW_TILE_PAIR_WAVES 4
+#endif
+#define TW_TILE_ATTR __attribute__((amdgpu_waves_per_eu(SINGLE ? 8 : (PAIR ? TW_TILE_PAIR_WAVES : (E <= 4 ? 4 : 2)))))
 #endif
 // SINGLE (one endpoint only): a tuple is an item -- the lean path below, TW_TILE_SINGLE=0 launches the general one instead
-template <int E, int SPANS = kTile, bool SINGLE = false>
+// PAIR (two endpoints only): items named by their span's thread, a tuple decoded by one division, unpadded slots, tables sized for
+// the class -- the second lean path below, TW_TILE_PAIR=0 launches the general one instead
+template <int E, int SPANS = kTile, bool SINGLE = false, bool PAIR = false>
 __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P, int pass, const int32_t* tile_ids, int n_tiles_e, int sub_tiles) {
     static_assert(!SINGLE || E == 1, "the lean path is the one of a single endpoint");
+    static_assert(!PAIR || (E == 2 && !SINGLE), "the pair path is the one of two endpoints");
     if (*P.err != 0) return;  // e.g. NaN parameters (hazard H3): nothing downstream is meaningful
-    typedef TileCfg<E, SPANS> C;
+    typedef TileCfg<E, SPANS, PAIR> C;
     constexpr int SL = C::kSlice;
     // sub_tiles > 1: a class of few tiles (the deep call graphs of a small batch: 57 tiles on 256 CUs, each a millisecond of
     // segments one after the other) is launched with sub_tiles workgroups per tile, each serving a stretch of the tile's spans
@@ -168,7 +286,7 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
     __shared__ int32_t s_wtot[4 * kTile / 64][2];
     __shared__ double t_root[C::kItems], t_close[C::kItems];
     __shared__ uint16_t it_idx[C::kItems];                // slice position of the item's candidate
-    __shared__ double g_sc[C::kGrid];
+    __shared__ double g_sc[C::kGrid + (PAIR ? 4 : 0)];    // (PAIR: the rank loop reads four scores a step without padding)
     __shared__ uint8_t g_span[C::kGrid];                   // the tuple's span (tile-local); an infeasible grid point has score NaN
     __shared__ uint32_t g_aux[C::kGrid / 4];               // phase 5 of a segment: the long spans' subset maxima and survivor counts (the ranks themselves: in t_root)
     __shared__ int32_t s_segend, s_anyamb;                 // ... any span of the segment whose top five the ranks do not decide (phase 5b)
@@ -198,7 +316,12 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
     TW_TILE_T0();
     // ---- 1. cut-offs ------------------------------------------------------------------------------------------------
     int32_t lo[E], hi[E];
-    if (pass == 1) {   // FindCutoffs (traceweaver_v3.py:182-217), reverse topological order
+    // (a wavefront none of whose threads owns a span -- the upper half of a workgroup of two threads per span -- does none of the
+    // per-span work: empty windows, which nothing below searches, reads back, tests for containment or stores)
+    if ((t & ~63) >= ns) {
+#pragma unroll
+        for (int e = 0; e < E; e++) { lo[e] = 0; hi[e] = -1; }
+    } else if (pass == 1) {   // FindCutoffs (traceweaver_v3.py:182-217), reverse topological order
 #pragma unroll
         for (int e = E - 1; e >= 0; e--) {
             const int n = (int)(U.ep_off[e + 1] - U.ep_off[e]);
@@ -354,7 +477,8 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
     {   // inclusive prefix sums of the items and of the tuple slots (a span's slots padded to a multiple of four: the rank
         // loop reads four scores a step) over the spans: wavefront scans by shuffles, then the wavefronts' totals through LDS
         // (a single endpoint: the items are the tuples, one prefix sum)
-        int a = live ? nitem : 0, b = (!SINGLE && live && some) ? (((int)prod + 3) & ~3) : 0;
+        // (two endpoints: the tuples as they are, no padding)
+        int a = live ? nitem : 0, b = (!SINGLE && live && some) ? (PAIR ? (int)prod : (((int)prod + 3) & ~3)) : 0;
         const int lane = t & 63, wv = t >> 6;
         for (int off = 1; off < 64; off <<= 1) {
             const int a2 = __shfl_up(a, off);
@@ -532,33 +656,236 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
         const int te = fresh(t);
         heavy_append<E>(P, live && s_mine[te] != 0 && s_amb[te] != 0, true, false, T.unit, first + (live ? te : 0), 0, 0, false, te & 63);   // (as below)
         return;
+    } else if constexpr (PAIR) {
+        // ---- two endpoints.  The endpoints are in topological order of the DAG (tw_load_batch refuses anything else): endpoint 0 is a
+        // root, endpoint 1 is a root too (no call order: every grid point is a tuple) or follows endpoint 0, block-uniformly.  A span's
+        // thread names its items and its tuple slots, a tuple finds its two items by one division and keeps their slice positions as two
+        // bytes for the ranks and the results; nothing searches the prefix sums.  The slots are the tuples (no padding), the tables are
+        // sized for the class.  The score is phase 4's of the general path for E = 2 in its order of additions ---------------------------
+        static_assert(SL <= 256, "the slice positions of a tuple's two candidates lie in a byte each");
+        __shared__ uint8_t it_span[C::kItems];   // the item's span (tile-local); its endpoint is bit 15 of it_idx
+        __shared__ uint16_t g_ix[C::kGrid];      // the slice positions of the tuple's candidates: endpoint 0 | endpoint 1 << 8
+        // (what a span's thread needs again behind the tuples -- whether the span is this kernel's, its first item, its candidates --
+        // is read back from LDS where it is needed, from a fresh copy of the thread's number: held in registers through the segment
+        // it would not fit the 96 registers of five wavefronts per SIMD)
+        __shared__ uint8_t s_mine[SPANS];
+        if (live) s_mine[t] = mine ? 1 : 0;
+        typedef SurvivorRanks<C::kGrid, kRankDirect + 1> SR;   // (unpadded: a long span has at least kRankDirect + 1 slots)
+        constexpr bool kRankFits = SR::kAuxWords <= C::kGrid / 4 && C::kGrid * 4 <= C::kItems * 8 && C::kGrid <= 65536;
+        static_assert(C::kGrid <= C::kItems * 8, "a rank per slot in t_root");
+        uint8_t* const g_rank = reinterpret_cast<uint8_t*>(t_root);   // [kGrid] the tuple's rank (from phase 5 on; the term tables are free by then)
+        const bool compact = kRankFits && P.tile_rank != 0;
+        const bool prim = dag_np[1] != 0 && (dag_pl[1] & 8u) != 0;   // the call-order edge 0 -> 1 is scored per tuple
+        for (int seg = 0; seg < ns;) {
+            if (compact) SR{g_aux, g_rank, nullptr, nullptr, g_sc, g_span, s_grid0, 0}.clear(t, nt);
+            if (t == 0) { s_segend = ns; s_anyamb = 0; }
+            group_sync();
+            if (live && t >= seg && (s_item0[t + 1] - s_item0[seg] > C::kItems || s_grid0[t + 1] - s_grid0[seg] > C::kGrid)) atomicMin(&s_segend, t);
+            group_sync();
+            const int send = s_segend;
+            const int it0 = s_item0[seg], nIt = s_item0[send] - it0, g0 = s_grid0[seg], nG = s_grid0[send] - g0;
+            const SR sr{g_aux, g_rank, reinterpret_cast<uint16_t*>(t_close), reinterpret_cast<uint16_t*>(t_close) + C::kGrid, g_sc, g_span, s_grid0, g0};
+            const int tq = fresh(t);
+            const bool here = tq < ns && tq >= seg && tq < send;
+            TW_TILE_TICK(2);
+            TW_TILE_COUNT(9, 1); TW_TILE_COUNT(10, nIt); TW_TILE_COUNT(11, nG);
+            // the span's thread names its items (span, endpoint, slice position; contained candidates in list order) and its slots
+            if (here) {
+                int k = s_item0[tq] - it0;
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const int rel = s_lo[e][tq];
+                    for (uint32_t m = s_cm[e][tq]; m != 0; m &= m - 1, k++) { it_span[k] = (uint8_t)tq; it_idx[k] = (uint16_t)((rel + __ffs((int)m) - 1) | (e << 15)); }
+                }
+                for (int g = s_grid0[tq] - g0, ge = s_grid0[tq + 1] - g0; g < ge; g++) g_span[g] = (uint8_t)tq;
+            }
+            group_sync();
+            // ---- 3. root / closing terms, one item per lane -------------------------------------------------------------------
+            for (int k = t; k < nIt; k += nt) {
+                const int s = it_span[k], e = it_idx[k] >> 15, idx = it_idx[k] & 0x7fff;
+                const int32_t st = sl_st[e][idx], en = sl_en[e][idx];
+                const bool is_root = (e == 0 ? dag_np[0] : dag_np[1]) == 0;
+                S.gp = P.gparam + (U.gp_off + (int64_t)((first + s) / P.batch_size) * U.nslot) * 4;
+                t_root[k] = is_root ? score_term_gap(S, slot_root(E, e), (long long)st - s_is[s]) : 0.0;
+                t_close[k] = score_term_gap(S, slot_close(E, e), (long long)s_ie[s] - en);
+            }
+            group_sync();
+            TW_TILE_TICK(3);
+            // ---- 4. tuples, one per lane (last endpoint fastest, the reference's order): feasibility and score -------------------
+            for (int g = t; g < nG; g += nt) {
+                const int s = g_span[g];
+                const int gi = g - (s_grid0[s] - g0);
+                const uint32_t pk = (uint32_t)s_cn[s], n0 = pk & 255u, n1 = (pk >> 8) & 255u;
+                const uint32_t k0 = n1 == 1 ? (uint32_t)gi : div_small((uint32_t)gi, n1), k1 = (uint32_t)gi - k0 * n1;
+                const int kx0 = s_item0[s] - it0 + (int)k0, kx1 = s_item0[s] - it0 + (int)(n0 + k1);
+                const int ix0 = it_idx[kx0], ix1 = it_idx[kx1] & 0x7fff;
+                const int32_t st0 = sl_st[0][ix0], en0 = sl_en[0][ix0], st1 = sl_st[1][ix1], en1 = sl_en[1][ix1];
+                const bool ok = !((dag_pm[1] & 1u) && en0 > st1);   // traceweaver_v3.py:343-347
+                double sj = 0.0;
+                if (ok) {
+                    // ScoreAssignmentAsPerInvocationGraph, no-skip branch (traceweaver_v1.py:305-361)
+                    const bool last1 = en1 > en0;
+                    if (dag_np[0] == 0) sj += t_root[kx0];
+                    if (!last1) sj += t_close[kx0];
+                    if (prim) {
+                        S.gp = P.gparam + (U.gp_off + (int64_t)((first + s) / P.batch_size) * U.nslot) * 4;
+                        sj += score_term_gap(S, slot_prim(E, 0, 1), (long long)st1 - en0);
+                    }
+                    if (dag_np[1] == 0) sj += t_root[kx1];
+                    if (last1) sj += t_close[kx1];
+                    if (ordered) {
+                        atomicAdd(&s_leaves[s], 1);
+                        if (pass == 1) { atomicOr(&s_bits[0][s], 1u << (ix0 - (int)s_lo[0][s])); atomicOr(&s_bits[1][s], 1u << (ix1 - (int)s_lo[1][s])); }
+                    }
+                }
+                g_sc[g] = ok ? sj : dnan();
+                g_ix[g] = (uint16_t)(ix0 | (ix1 << 8));
+                if (compact && ok && s_grid0[s + 1] - s_grid0[s] > kRankDirect) sr.note(g, gi, sj);   // a long span: the largest key of the slot's subset
+            }
+            group_sync();
+            TW_TILE_TICK(4);
+            // ---- 5. rank of every tuple among the tuples of its span.  Python's order of two tuples with equal scores: start_mus of
+            // the first differing span (spans.py:51-52).  +1: the other one is greater, -1: smaller, 0: incomparable
+            auto order_equal = [&](uint32_t a, uint32_t b) -> int {
+                const int e = (a & 255u) != (b & 255u) ? 0 : 1;
+                const int32_t sa = sl_st[e][(a >> (8 * e)) & 255u], sb = sl_st[e][(b >> (8 * e)) & 255u];
+                return sb > sa ? 1 : (sb < sa ? -1 : 0);
+            };
+            if (compact) sr.collect(nG, t, nt);
+            for (int g = t; g < nG; g += nt) {
+                const double my = g_sc[g];
+                int rank = kTopK;
+                const int s = g_span[g];
+                const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
+                if (compact && ge - gs > kRankDirect) { g_rank[g] = (uint8_t)kTopK; continue; }   // (a survivor's own rank follows behind the barrier)
+                if (my == my) {   // (a NaN score ranks nowhere)
+                    rank = 0;
+                    bool partner = false;
+                    // four scores a step: how many are greater, how many are equal -- the tuple itself is one of the equal ones.  (No
+                    // padding: what lies behind the span's last slot is another span's or nobody's, and is not counted; g_sc has
+                    // three entries to spare behind the segment's last)
+                    int eq = 0;
+                    for (int h0 = gs; h0 < ge && rank < kTopK; h0 += 4) {
+                        const double o0 = g_sc[h0], o1 = g_sc[h0 + 1], o2 = g_sc[h0 + 2], o3 = g_sc[h0 + 3];
+                        const bool in1 = h0 + 1 < ge, in2 = h0 + 2 < ge, in3 = h0 + 3 < ge;
+                        rank += (o0 > my) + (in1 && o1 > my) + (in2 && o2 > my) + (in3 && o3 > my);
+                        eq += (o0 == my) + (in1 && o1 == my) + (in2 && o2 == my) + (in3 && o3 == my);
+                    }
+                    if (eq > 1 && rank < kTopK) {   // equal scores (millisecond-granular data): the equal ones that are greater, one that is incomparable
+                        const uint32_t mine_ix = g_ix[g];
+                        for (int h = gs; h < ge; h++) {
+                            if (h == g || !(g_sc[h] == my)) continue;
+                            const int ord = order_equal(mine_ix, g_ix[h]);
+                            if (ord > 0) rank++;
+                            else if (ord == 0) partner = true;
+                        }
+                    }
+                    if (partner && rank < kTopK) { s_amb[s] = 1; s_anyamb = 1; }
+                }
+                g_rank[g] = (uint8_t)(rank < kTopK ? rank : kTopK);
+            }
+            if (compact) {   // a survivor per lane: the greater ones, the equal ones, among the survivors of its span
+                group_sync();
+                sr.rank(t, nt,
+                        [&](int s, int gi) -> uint32_t { return g_ix[s_grid0[s] - g0 + gi]; },
+                        [&](int s, uint32_t mine_ix, int hrel) { return order_equal(mine_ix, g_ix[s_grid0[s] - g0 + hrel]); },
+                        [&](int s) { s_amb[s] = 1; s_anyamb = 1; });
+            }
+            group_sync();
+            TW_TILE_TICK(5);
+            // ---- results: the tuples of rank < 5 write themselves; then one thread per span ---------------------------------------
+            for (int g = t; g < nG; g += nt) {
+                if (g_rank[g] >= kTopK) continue;
+                const int s = g_span[g];
+                if (s_amb[s]) continue;
+                const int k = g_rank[g], si = first + s;
+                const uint32_t ix = g_ix[g];
+                P.tk_score[tks_index(U, k, si)] = g_sc[g];
+                P.tk_idx[tk_index(U, k, 0, si)] = s_A[0] + (int)(ix & 255u);
+                P.tk_idx[tk_index(U, k, 1, si)] = s_A[1] + (int)(ix >> 8);
+            }
+            // ---- 5b. a span whose top five the ranks do not decide: CPython's heap over the span's tuples in enumeration order by the
+            // span's own thread, in registers, on the scores of phase 4.  Behind the barrier the term tables (the ranks, the survivor
+            // lists) and the position table are free: kTopK + 1 slots per span hold the heap for CPython's list.sort -- the scores of
+            // the lower half of the spans in t_root, of the upper half in t_close, the tuples in g_ix
+            if (s_anyamb != 0) group_sync();   // (the flag is the same for all since the barrier after the ranks; the lanes above skip the tuples of undecided spans: s_amb is cleared only when all have passed)
+            const int tl = fresh(t);
+            const bool mine_here = tl < ns && tl >= seg && tl < send && s_mine[tl] != 0;
+            const int th = tl < SPANS / 2 ? tl : tl - SPANS / 2;
+            const bool replay = s_anyamb != 0 && mine_here && s_amb[tl] && (th + 1) * (kTopK + 1) <= C::kItems && (tl + 1) * (kTopK + 1) <= C::kGrid && s_leaves[tl] <= kTileReplayMax;
+            if (replay) {
+                const int ks = s_item0[tl] - it0;                       // the first item of this thread's span
+                const int c0 = (int)((uint32_t)s_cn[tl] & 255u);        // ... its candidates of endpoint 0
+                auto start_of = [&](int e, int pos) -> int32_t { return sl_st[e][it_idx[ks + (e != 0 ? c0 : 0) + pos] & 0x7fff]; };
+                RegHeap RH;
+                RH.clear(E);
+                const int gs = s_grid0[tl] - g0, nT = s_grid0[tl + 1] - s_grid0[tl];
+                const uint32_t n1 = ((uint32_t)s_cn[tl] >> 8) & 255u;
+                uint32_t k0 = 0, k1 = 0;
+                for (int gi = 0; gi < nT; gi++) {
+                    const double sc = g_sc[gs + gi];
+                    const unsigned long long x = (unsigned long long)(k0 | (k1 << 8));   // positions among the span's candidates, 8 bits per endpoint
+                    if (++k1 == n1) { k1 = 0; k0++; }
+                    if (!(sc == sc) || RH.below_root(sc)) continue;   // infeasible / strictly below the root of a full heap: the push leaves the array as it is
+                    RH.push(sc, x, start_of);
+                }
+                double* hs = (tl < SPANS / 2 ? t_root : t_close) + th * (kTopK + 1);
+                uint16_t* hx = g_ix + tl * (kTopK + 1);
+#pragma unroll
+                for (int k = 0; k < kTopK; k++) { hs[k] = RH.s[k]; hx[k] = (uint16_t)RH.x[k]; }
+                py_sort_desc(hs, hx, RH.n, [&](double sa, unsigned long long xa, double sb, unsigned long long xb) { return RH.lt(sa, xa, sb, xb, start_of); });
+                const int si = first + tl;
+                for (int k = 0; k < RH.n; k++) {
+                    P.tk_score[tks_index(U, k, si)] = hs[k];
+                    P.tk_idx[tk_index(U, k, 0, si)] = s_A[0] + (int)it_idx[ks + (int)(hx[k] & 255u)];
+                    P.tk_idx[tk_index(U, k, 1, si)] = s_A[1] + (int)(it_idx[ks + c0 + (int)(hx[k] >> 8)] & 0x7fff);
+                }
+                s_amb[tl] = 0;   // (read again only by this thread: below, and when the tile hands its undecided spans on)
+            }
+            if (mine_here && !s_amb[tl]) {
+                const int i = first + tl;
+                // a span's list has min(5, feasible tuples) entries in every pass; the unused entries keep the -1 / NaN
+                // pattern of tw_load_batch and are never written
+                const int64_t g = U.in_off + i;
+                const int leaves = s_leaves[tl];
+                P.tk_n[g] = leaves < kTopK ? leaves : kTopK;
+                P.leaves[g] = leaves;
+                if (pass == 1) P.leaves0[g] = leaves;
+                P.rep[g] = 0;
+                if (pass == 1) {
+#pragma unroll
+                    for (int e = 0; e < 2; e++) {
+                        P.c_bits[ie_index(U, e, i) * kCandWords] = (uint64_t)(ordered ? s_bits[e][tl] : s_cm[e][tl]);
+                        for (int w = 1; w < kCandWords; w++) P.c_bits[ie_index(U, e, i) * kCandWords + w] = 0;
+                    }
+                }
+            }
+            group_sync();
+            TW_TILE_TICK(6);
+            seg = send;
+        }
+        TW_TILE_FLUSH();
+        const int te = fresh(t);
+        heavy_append<E>(P, te < ns && s_mine[te] != 0 && s_amb[te] != 0, true, false, T.unit, first + (te < ns ? te : 0), 0, 0, false, te & 63);
+        return;
     } else
     // ---- segments of the tile: as many spans as the tables hold ------------------------------------------------------
     for (int seg = 0; seg < ns;) {
-        // Phase 5 ranks a long span (more than kRankDirect slots) among its survivors only.  Its slots fall into five subsets by slot
-        // number mod 5; L = the smallest of the subsets' largest feasible scores (none: everything survives), taken on 32-bit keys as
-        // phase 4 forms the scores.  Five distinct tuples reach L, so a tuple whose key is below L has five strictly greater ones: rank
-        // >= 5, which is all that is ever stored of it.  A tuple that reaches L survives, and so does every tuple that is greater than or
-        // equal to it: its count of greater tuples, its equal partners and their comparisons are those of the whole span.  The survivors
-        // (about eleven of a span, all of them when the scores are equal) are listed twice: per span from the span's own first slot on,
-        // to be scanned, and in one list of the segment, a lane each.  The term tables are free between phase 4 and phase 5b: t_root
-        // holds the ranks, t_close the two lists of 16-bit slot numbers.  A long span is found by its first slot / kRankMinLong.
-        constexpr int kLong = (C::kGrid - kRankMinLong) / kRankMinLong + 1;
-        constexpr bool kRankFits = kLong * (kRankBuckets + 1) + 1 <= C::kGrid / 4 && C::kGrid * 4 <= C::kItems * 8 && C::kGrid <= 65536;
+        // Phase 5 ranks a long span (more than kRankDirect slots) among its survivors only (SurvivorRanks).  The term tables are free
+        // between phase 4 and phase 5b: t_root holds the ranks, t_close the two lists of 16-bit slot numbers.
+        typedef SurvivorRanks<C::kGrid, kRankMinLong> SR;
+        constexpr bool kRankFits = SR::kAuxWords <= C::kGrid / 4 && C::kGrid * 4 <= C::kItems * 8 && C::kGrid <= 65536;
         static_assert(kRankBuckets == kTopK && C::kGrid <= C::kItems * 8, "a subset of slots per entry of the list; a rank per slot in t_root");
-        uint32_t* const r_max = g_aux;                                                     // [kLong][kRankBuckets] keys, 0: no feasible tuple
-        int32_t* const r_cnt = reinterpret_cast<int32_t*>(g_aux + kLong * kRankBuckets);   // [kLong] survivors of the span, [kLong]: of the segment
         uint8_t* const g_rank = reinterpret_cast<uint8_t*>(t_root);                        // [kGrid] the tuple's rank (from phase 5 on)
-        uint16_t* const r_sub = reinterpret_cast<uint16_t*>(t_close);                      // [kGrid] a span's survivors from its first slot on
-        uint16_t* const r_all = r_sub + C::kGrid;                                          // [kGrid] the survivors of the segment
         const bool compact = kRankFits && P.tile_rank != 0;   // (an instantiation whose tables do not hold the lists keeps the loop over all slots)
-        if (compact) for (int x = fresh(t); x < kLong * (kRankBuckets + 1) + 1; x += nt) g_aux[x] = 0u;
+        if (compact) SR{g_aux, g_rank, nullptr, nullptr, g_sc, g_span, s_grid0, 0}.clear(fresh(t), nt);
         if (t == 0) { s_segend = ns; s_anyamb = 0; }
         group_sync();
         if (live && t >= seg && (s_item0[t + 1] - s_item0[seg] > C::kItems || s_grid0[t + 1] - s_grid0[seg] > C::kGrid)) atomicMin(&s_segend, t);
         group_sync();
         const int send = s_segend;
         const int it0 = s_item0[seg], nIt = s_item0[send] - it0, g0 = s_grid0[seg], nG = s_grid0[send] - g0;
+        const SR sr{g_aux, g_rank, reinterpret_cast<uint16_t*>(t_close), reinterpret_cast<uint16_t*>(t_close) + C::kGrid, g_sc, g_span, s_grid0, g0};
         TW_TILE_TICK(2);
         TW_TILE_COUNT(9, 1); TW_TILE_COUNT(10, nIt); TW_TILE_COUNT(11, nG);
         // ---- 3. root / closing terms, one (span, endpoint, candidate) per lane ----------------------------------------
@@ -637,11 +964,7 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
             }
             g_sc[g] = ok ? sj : dnan();
             g_span[g] = (uint8_t)s;
-            if (compact && ok && s_grid0[s + 1] - s_grid0[s] > kRankDirect) {   // a long span: the largest key of the slot's subset
-                uint32_t* b = r_max + ((g - gi) / kRankMinLong) * kRankBuckets + gi % kRankBuckets;
-                const uint32_t key = score_key32(sj);
-                if (key > *(volatile uint32_t*)b) atomicMax(b, key);   // (most lanes find a greater one there already)
-            }
+            if (compact && ok && s_grid0[s + 1] - s_grid0[s] > kRankDirect) sr.note(g, gi, sj);   // a long span: the largest key of the slot's subset
         }
         group_sync();
         TW_TILE_TICK(4);
@@ -662,42 +985,7 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
                 }
             return ord;
         };
-        if (compact) {
-            const int tr = fresh(t);   // (what the lists' addresses are formed from: here, not ahead of the segment loop)
-            for (int gb = 0; gb < nG; gb += nt) {   // (the same trips for every lane: the appends are the wavefront's)
-                const int g = gb + tr, lane = tr & 63;
-                bool surv = false;
-                int sub0 = 0;   // a survivor: the first slot of its span
-                if (g < nG) {
-                    const double my = g_sc[g];
-                    const int s = g_span[g];
-                    const int gs = s_grid0[s] - g0, ge = s_grid0[s + 1] - g0;
-                    if (ge - gs > kRankDirect && my == my) {
-                        const uint32_t* b = r_max + (gs / kRankMinLong) * kRankBuckets;
-                        uint32_t lk = b[0];
-#pragma unroll
-                        for (int j = 1; j < kRankBuckets; j++) lk = b[j] < lk ? b[j] : lk;
-                        surv = score_key32(my) >= lk;   // (lk = 0, a subset without a feasible tuple: everything survives)
-                        sub0 = gs;
-                    }
-                }
-                const int at = wave_append(&r_cnt[kLong], surv, lane);
-                if (surv) r_all[at] = (uint16_t)g;
-                // the span's own list: one atomic per wavefront and span that has survivors among the lanes
-                unsigned long long todo = __ballot(surv);
-                while (todo != 0ull) {
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int lead0 = __shfl(sub0, leader);
-                    const bool with = surv && sub0 == lead0;
-                    const unsigned long long m = __ballot(with);
-                    int base = 0;
-                    if (lane == leader) base = atomicAdd(&r_cnt[lead0 / kRankMinLong], __popcll(m));
-                    base = __shfl(base, leader);
-                    if (with) r_sub[lead0 + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)g;
-                    todo &= ~m;
-                }
-            }
-        }
+        if (compact) sr.collect(nG, fresh(t), nt);   // (fresh: what the lists' addresses are formed from, here, not ahead of the segment loop)
         for (int g = t; g < nG; g += nt) {
             const double my = g_sc[g];
             int rank = kTopK;
@@ -733,35 +1021,11 @@ __global__ void __launch_bounds__(4 * kTile) TW_TILE_ATTR k_enumerate_tile(Dev P
         }
         if (compact) {   // a survivor per lane: the greater ones, the equal ones, among the survivors of its span
             group_sync();
-            const int nsv = r_cnt[kLong];
-            for (int k = fresh(t); k < nsv; k += nt) {
-                const int g = r_all[k];
-                const double my = g_sc[g];
-                const int s = g_span[g];
-                const int gs = s_grid0[s] - g0;
-                const int n = r_cnt[gs / kRankMinLong];
-                const uint16_t* sub = r_sub + gs;
-                int rank = 0, eq = 0;
-                for (int h = 0; h < n && rank < kTopK; h++) {
-                    const double o = g_sc[sub[h]];
-                    rank += (o > my);
-                    eq += (o == my);
-                }
-                bool partner = false;
-                if (eq > 1 && rank < kTopK) {
-                    int32_t ka[E], ia[E];
-                    decode(s, g - gs, it0, ka, ia);
-                    for (int h = 0; h < n; h++) {
-                        const int hg = sub[h];
-                        if (hg == g || !(g_sc[hg] == my)) continue;
-                        const int ord = order_equal(s, ia, hg - gs);
-                        if (ord > 0) rank++;
-                        else if (ord == 0) partner = true;
-                    }
-                }
-                if (partner && rank < kTopK) { s_amb[s] = 1; s_anyamb = 1; }
-                g_rank[g] = (uint8_t)(rank < kTopK ? rank : kTopK);
-            }
+            struct Mine { int32_t ia[E]; };
+            sr.rank(fresh(t), nt,
+                    [&](int s, int gi) { Mine m; int32_t ka[E]; decode(s, gi, it0, ka, m.ia); return m; },
+                    [&](int s, const Mine& m, int hrel) { return order_equal(s, m.ia, hrel); },
+                    [&](int s) { s_amb[s] = 1; s_anyamb = 1; });
         }
         group_sync();
         TW_TILE_TICK(5);

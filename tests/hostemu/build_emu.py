@@ -1,5 +1,18 @@
 """Builds libtwgpu_emu.so: the engine source compiled with g++ against the host-emulation shim.
-TEST INFRASTRUCTURE ONLY -- see tests/hostemu/hip/hip_runtime.h."""
+TEST INFRASTRUCTURE ONLY -- see tests/hostemu/hip/hip_runtime.h.
+
+The environment the library needs, set BEFORE an Engine is created on it (the engine reads it in tw_create):
+
+  TW_TILE=1 TW_COOP_THREADS=1        one thread per workgroup: the threads of a workgroup run one after another here and barriers,
+                                     ballots and shuffles are no-ops, so no workgroup may have more than one.  The `emu_lib`
+                                     fixture of tests/conftest.py sets both, and TW_STAGE_MIN_TILES=0 (the small units of the tests
+                                     take the per-class window / selection stages too).
+  TW_EMU_LANES=1                     instead: a host thread per lane, the cross-lane operations as rendezvous.  With it the
+  (TW_TILE=128 TW_COOP_THREADS=256   workgroups have the sizes of the HIP build; a unit of a few hundred requests takes seconds to
+   TW_TILE_SUB=2)                    minutes, so the tests run it in child processes with the environment of their own.
+
+With neither (TW_TILE / TW_COOP_THREADS unset or above 1 and no TW_EMU_LANES=1) the shim refuses the device: Engine(...) raises
+EngineError and tw_create prints why.  (It used to run, and ended Python with a segmentation fault in pass 1.)"""
 import os
 import subprocess
 import sys

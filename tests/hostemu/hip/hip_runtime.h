@@ -49,8 +49,19 @@ struct emu_event { std::chrono::steady_clock::time_point t; };
 typedef emu_event* hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 
-inline const char* hipGetErrorString(hipError_t) { return "host emulation error"; }
-inline hipError_t hipSetDevice(int) { return hipSuccess; }
+// Without TW_EMU_LANES=1 the threads of a workgroup run one after another and every barrier, ballot and shuffle is a no-op: the
+// engine's kernels are only correct then with one thread per workgroup.  A library loaded with anything else in the environment used
+// to end the process with a segmentation fault in the first pass; the device is refused instead (tw_create fails with this text).
+inline const char* emu_env_refusal() {
+    const char* l = getenv("TW_EMU_LANES");
+    if (l && *l && *l != '0') return nullptr;
+    const char *t = getenv("TW_TILE"), *c = getenv("TW_COOP_THREADS");
+    if (t && *t && atoi(t) <= 1 && c && *c && atoi(c) <= 1) return nullptr;
+    return "host emulation: workgroups of more than one thread need TW_EMU_LANES=1 (a host thread per lane); without it the library "
+           "runs only with TW_TILE=1 TW_COOP_THREADS=1 in the environment (tests/hostemu/build_emu.py)";
+}
+inline const char* hipGetErrorString(hipError_t) { const char* m = emu_env_refusal(); return m ? m : "host emulation error"; }
+inline hipError_t hipSetDevice(int) { return emu_env_refusal() ? hipErrorEmu : hipSuccess; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }

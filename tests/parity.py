@@ -58,11 +58,19 @@ def check_units(lib_path, units, mixtures=None, device=0, allow_budget=False):
     window whose search ran out of its node budget on the engine (counted in budget_windows; tie-saturated inputs
     only) keeps the best selection found: with allow_budget the comparison of such a unit stops at the candidate
     lists of that pass (which do not depend on the selection) and the assignment must still be a valid one;
-    without it any such window is a failure."""
+    without it any such window is a failure.
+
+    After each pass the engine's decisions (Engine.decisions: per request the length of the list its selection chose from
+    -- the one on the remaining spans where it was enumerated again --, the chosen rank and the margin between two of
+    that list's scores) are held to traces.decisions_host on the oracle's pass: "lists on the remaining spans".  A list
+    that is stale is reported as that, not as the selection it leads to: where the selections differ the margins are
+    first compared at the engine's own ranks on the oracle's lists, and only if those agree is the difference the
+    selection's (explain_selection says what it costs)."""
     eng = Engine(device, lib_path=lib_path)
     eng.load(units)
     eng.run_pass1()
     r1 = eng.results(1)
+    d1 = eng.decisions(1)
     g_eng = eng.gauss_params()
     gaps_eng = eng.gaps()
     ora = []
@@ -72,6 +80,7 @@ def check_units(lib_path, units, mixtures=None, device=0, allow_budget=False):
     eng.set_mixtures([o[4][0] for o in ora], [o[4][1] for o in ora])
     eng.run_pass2()
     r2 = eng.results(2)
+    d2 = eng.decisions(2)
     eng.close()
     for k, u in enumerate(units):
         svc, end_flag, p1, p2, _ = ora[k]
@@ -86,17 +95,105 @@ def check_units(lib_path, units, mixtures=None, device=0, allow_budget=False):
             assert p1["budget_windows"] == 0 and p2["budget_windows"] == 0, tag + " the oracle's search did not complete either"
             assert np.array_equal(r1[k]["window_end"], end_flag), tag + " window ends"
             assert np.array_equal(np.transpose(r1[k]["topk_idx"], (2, 0, 1)), p1["topk2_idx"]), tag + " top-5 tuples"
+            for n, (d, p) in enumerate(((d1[k], p1), (d2[k], p2)), 1):
+                assert np.array_equal(d["list_n"], p["topk_n"]), tag + " pass %d lists on the remaining spans" % n
             for r in (r1[k], r2[k]):
                 assert_assignment_properties(u, r["parent"])
             assert r1[k]["cnt_unassigned"] >= p1["cnt_unassigned"] if not r1[k]["repaired_windows"] else True
             continue
-        assert_pass_equal(r1[k], p1, end_flag, tag + " pass 1")
+        assert_pass_and_lists(u, r1[k], d1[k], p1, end_flag, tag + " pass 1")
         for q, go in enumerate(T.gaps(svc, p1["parent"])):
             ge = gaps_eng[k][q]
             ge = ge[~np.isnan(ge)]
             assert (len(ge) == 0) if go is None else np.array_equal(ge, go), tag + " gap samples slot %d" % q
-        assert_pass_equal(r2[k], p2, end_flag, tag + " pass 2")
+        assert_pass_and_lists(u, r2[k], d2[k], p2, end_flag, tag + " pass 2")
     return r1, r2, ora
+
+
+def _same_doubles(a, b):
+    """Bit for bit, NaN matching NaN."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
+
+
+def assert_pass_and_lists(u, res, dec, ora, end_flag, tag):
+    """conftest.assert_pass_equal, and the lists the selection read (dec = the unit's entry of Engine.decisions) against the
+    oracle's lists on the remaining spans.  Everything assert_pass_equal checks before the selection keeps its place and
+    its message; then the lists on the remaining spans; then the selection and what follows it."""
+    from traceweaver_amd import traces
+
+    later = None
+    try:
+        assert_pass_equal(res, ora, end_flag, tag)
+    except AssertionError as e:
+        head = str(e).split("\n")[0]
+        if not any(head.startswith(tag + s) for s in (" selection", " parent arrays", " enumerated tuples", " not_best_count", " cnt_unassigned", " window count")):
+            raise
+        later = (head, e)
+    msg = tag + " lists on the remaining spans"
+    assert np.array_equal(dec["rank"], res["chosen"]), msg + " (the decisions' ranks are not the pass' selection)"
+    assert np.array_equal(dec["list_n"], ora["topk_n"]), msg
+    # the margins at the engine's own ranks, on the oracle's lists: they differ only if the engine's list does
+    own = dict(ora, chosen=np.where(dec["rank"] < ora["topk_n"], dec["rank"], -1))
+    assert _same_doubles(dec["margin"][own["chosen"] == dec["rank"]], traces.decisions_host(own)["margin"][own["chosen"] == dec["rank"]]), msg
+    if later is not None:
+        text = later[0]
+        if not np.array_equal(res["chosen"], ora["chosen"]):
+            text += "\n" + explain_selection(u, res, ora, end_flag)
+        raise AssertionError(text) from later[1]
+    want = traces.decisions_host(ora)
+    assert np.array_equal(dec["rank"], want["rank"]), msg
+    assert _same_doubles(dec["margin"], want["margin"]), msg
+
+
+def sel_weight(score):
+    """the selection's integer weight of a tuple, rint((10000 + score) * 2^32) floored at 0."""
+    return max(int(np.rint((10000.0 + float(score)) * 4294967296.0)), 0)
+
+
+def explain_selection(u, engine_pass, oracle_pass, end_flag):
+    """Where two selections of a pass differ, per window: the requests, the total integer weight of either assignment on the
+    oracle's lists on the remaining spans, and whether the engine's assignment uses an outgoing span twice.  engine_pass:
+    a unit's entry of Engine.results (chosen [n], parent [E, n]); oracle_pass: the oracle's pass dict."""
+    end_flag = np.asarray(end_flag)
+    ends = np.nonzero(end_flag)[0]
+    first = np.concatenate(([0], ends[:-1] + 1))
+    idx, sc, tn = oracle_pass["topk_idx"], oracle_pass["topk_score"], oracle_pass["topk_n"]
+    par = np.asarray(engine_pass["parent"])
+    lines = []
+    for w, (a, b) in enumerate(zip(first.tolist(), (ends + 1).tolist())):
+        diff = [i for i in range(a, b) if engine_pass["chosen"][i] != oracle_pass["chosen"][i]]
+        if not diff:
+            continue
+        tot_o = tot_e = unlisted = 0
+        for i in range(a, b):
+            c = int(oracle_pass["chosen"][i])
+            if c >= 0:
+                tot_o += sel_weight(sc[i, c])
+            if par[0, i] < 0:
+                continue
+            at = [k for k in range(int(tn[i])) if (idx[i, k] == par[:, i]).all()]
+            if at:
+                tot_e += sel_weight(sc[i, at[0]])
+            else:
+                unlisted += 1
+        twice = []
+        for e in range(u.E):
+            x = par[e, a:b]
+            x = x[x >= 0]
+            vals, cnt = np.unique(x, return_counts=True)
+            twice += [(e, int(v)) for v in vals[cnt > 1]]
+            before = par[e, :a]                      # spans earlier windows took are not this window's to take
+            twice += [(e, int(v)) for v in np.intersect1d(x, before[before >= 0])]
+        lines.append("window %d (requests %d..%d, %d): requests %s differ; engine %s, oracle %s; total weight on the oracle's lists on the "
+                     "remaining spans: engine %d%s, oracle %d (oracle - engine = %d, %.3f score units); the engine's assignment uses %s"
+                     % (w, a, b - 1, b - a, diff, [(i, par[:, i].tolist()) for i in diff],
+                        [(i, idx[i, int(oracle_pass["chosen"][i])].tolist() if oracle_pass["chosen"][i] >= 0 else None) for i in diff],
+                        tot_e, " (%d of its tuples are not in the oracle's list: weight 0)" % unlisted if unlisted else "", tot_o, tot_o - tot_e,
+                        (tot_o - tot_e) / 4294967296.0,
+                        "no outgoing span twice" if not twice else "outgoing spans twice (endpoint, span): %s" % twice))
+    return "\n".join(lines)
 
 
 def stress_units(cases):

@@ -127,11 +127,9 @@ def test_pair_units_emulated(emu_lib, monkeypatch, pair_units, pair):
 
 @pytest.mark.parametrize("pair", ["1", "0"])
 def test_pair_units_emulated_with_production_tables(emu_prod_lib, monkeypatch, pair_units, pair):
-    """The spans of 33 to 256 tuples by the tile kernel itself, a thread per workgroup.  Without unit 314: with the production
-    thresholds a thread per workgroup, its pass-2 selection differs from the oracle's on either route, with equal lists and scores --
-    and did before the pair path existed; the tiny-table build above and the GPU tier hold that unit to the oracle."""
+    """The spans of 33 to 256 tuples by the tile kernel itself, a thread per workgroup."""
     monkeypatch.setenv("TW_TILE_PAIR", pair)
-    parity.check_units(emu_prod_lib, [u for case, u in zip(CASES, pair_units) if case[0] != 314])
+    parity.check_units(emu_prod_lib, pair_units)
 
 
 @pytest.mark.parametrize("pair", ["1", "0"])

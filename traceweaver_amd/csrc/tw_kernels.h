@@ -3861,16 +3861,21 @@ __global__ void __launch_bounds__(kDpThreads) k_select_dp(Dev P, TileSet S) {
 // first window never changes.  Windows that do not share candidates (perfect cuts) never interact, chains of
 // size-capped windows settle front to back; all flagged windows of all units are re-solved concurrently by the same
 // wavefront kernels as the first solve.
-__device__ __forceinline__ void reset_class_lists(const Dev& P, int E, int t) {
-    if (t < 2) P.heavy_in_count[t * (kMaxEp + 1) + E] = 0;
-    if (t < 8) P.heavy_in_next[t * (kMaxEp + 1) + E] = 0;
-    if (t == 0) { P.heavy_big_count[E] = 0; P.redo_count[E] = 0; P.fb_count[E] = 0; }
+// (strided over the workgroup's threads: a workgroup of fewer than eight threads -- TW_TILE < 8, the one-thread emulation of the tests --
+// resets all of it too.  With `if (t < 8)` alone such a workgroup left the wide list's count and seven of the eight cursors standing: the
+// class' first repair round then enumerated the wide spans of the first solve again in mode 1, on words of P.gone that were not valid)
+__device__ __forceinline__ void reset_class_lists(const Dev& P, int E, int t, int nt) {
+    for (int q = t; q < 8; q += nt) {
+        if (q < 2) P.heavy_in_count[q * (kMaxEp + 1) + E] = 0;
+        P.heavy_in_next[q * (kMaxEp + 1) + E] = 0;
+        if (q == 0) { P.heavy_big_count[E] = 0; P.redo_count[E] = 0; P.fb_count[E] = 0; }
+    }
 }
 // reset_E > 0 (a class' own first round, launch_class_stage): the first workgroup also resets what a repair round resets of the
 // class' work lists -- the class' enumeration is complete, k_detect_gone, which lists into them, comes after this kernel
 __global__ void k_claim(Dev P, TileSet S, int reset_E) {
     if (*P.err != 0) return;  // an earlier kernel of this pass reported an error: its outputs are not usable
-    if (reset_E > 0 && blockIdx.x == 0) reset_class_lists(P, reset_E, threadIdx.x);
+    if (reset_E > 0 && blockIdx.x == 0) reset_class_lists(P, reset_E, threadIdx.x, blockDim.x);
     const TileDev Tl = P.tiles[set_tile(S)];
     const UnitDev& U = P.units[Tl.unit];
     const int i = Tl.first + threadIdx.x;

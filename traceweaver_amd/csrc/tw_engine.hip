@@ -44,6 +44,61 @@ int env_int(const char* name, int dflt) {
     return (v && *v) ? atoi(v) : dflt;
 }
 
+// Every TW_* variable of the engine.  read_knobs, called by tw_create, is the only reader of the environment: a knob has the
+// engine's lifetime, and a variable set after tw_create does not reach that engine.
+struct Knobs {
+    int tile;                 // TW_TILE: incoming spans (threads) per workgroup of the per-span kernels
+    int tile_threads;         // TW_TILE_THREADS: threads per incoming span of k_enumerate_tile (its items and tuples are spread over all of them)
+    int tile_single;          // TW_TILE_SINGLE: the one-endpoint class takes the lean path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int tile_single_threads;  // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
+    int tile_pair;            // TW_TILE_PAIR: the two-endpoint class takes the pair path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
+    int tile_pair_threads;    // TW_TILE_PAIR_THREADS: threads per incoming span on that path (1 or 2)
+    int tile_rank;            // TW_TILE_RANK: the general path of k_enumerate_tile ranks long spans among their compacted survivors (0 = the all-pairs loop: A/B runs, bisection)
+    int block_params;         // TW_BLOCK_PARAMS: pass-1 block parameters by a wavefront per group of blocks (0 = the thread-per-slot kernel: A/B runs, bisection)
+    int coop;                 // TW_COOP_THREADS: threads of the per-unit cooperative kernels
+    int set_hw_queues;        // TW_SET_HW_QUEUES: tw_create exports GPU_MAX_HW_QUEUES when it is still unset (see there)
+    int pipeline;             // TW_CLASS_PIPELINE=0: every class joins the engine's stream after its enumeration (measurements, tests)
+    int sig_hash_bits;        // TW_SIG_HASH_BITS: bits of the signature hash that tw_trace_signatures keeps (tests: collisions)
+    int debug_lists;          // TW_DEBUG_LISTS=1: the list counters of the first enumeration are copied to the host per class (tw_debug_worklists)
+    int stage_min_tiles;      // TW_STAGE_MIN_TILES: batches of fewer tiles per class on average join the classes after the enumeration (a stage is 17 small
+                              // launches per class: the 1 M-span Alibaba-shape slice, eight classes of 300 tiles, takes 7.8 ms per step staged and 6.4 joined)
+    int tile_sub;             // TW_TILE_SUB: workgroups per tile for classes of few tiles (1 = never)
+    int lean_pool;            // TW_LEAN_POOL: doubles of LDS for the pair tables of k_enumerate_lean
+    int split_twins, defer_min_e, lean_min_e, lean_grid, tile_max_deep;   // TW_SPLIT_TWINS .. TW_TILE_MAX_DEEP: handed to the kernels in Dev (tw_load_batch)
+    int64_t part_slots_max;   // TW_PART_SLOTS_MAX: most scratch slots of the split enumerations, whatever the batch (tw_load_batch)
+    int part_budget_deep;     // TW_PART_BUDGET_DEEP: extra work-list entries per span of the classes of five and more endpoints (part_extra)
+    int fit_sort;             // TW_FIT_SORT=1: the gap rows go the sort route (fit_prepare)
+};
+
+Knobs read_knobs() {
+    Knobs K;
+    K.tile = std::min(std::max(env_int("TW_TILE", kTile), 1), kTile);
+    K.tile_threads = std::min(std::max(env_int("TW_TILE_THREADS", 2), 1), 4);
+    K.tile_single = env_int("TW_TILE_SINGLE", 1);
+    K.tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
+    K.tile_pair = env_int("TW_TILE_PAIR", 1);
+    K.tile_pair_threads = std::min(std::max(env_int("TW_TILE_PAIR_THREADS", 2), 1), 2);
+    K.tile_rank = env_int("TW_TILE_RANK", 1) != 0 ? 1 : 0;
+    K.block_params = env_int("TW_BLOCK_PARAMS", 1);
+    K.coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
+    K.set_hw_queues = env_int("TW_SET_HW_QUEUES", 0);
+    K.pipeline = env_int("TW_CLASS_PIPELINE", 1);
+    K.sig_hash_bits = std::min(std::max(env_int("TW_SIG_HASH_BITS", 64), 1), 64);
+    K.debug_lists = env_int("TW_DEBUG_LISTS", 0);
+    K.stage_min_tiles = env_int("TW_STAGE_MIN_TILES", 1024);
+    K.tile_sub = std::max(env_int("TW_TILE_SUB", 8), 1);
+    K.lean_pool = std::min(std::max(env_int("TW_LEAN_POOL", 512), 1), 4096);
+    K.split_twins = env_int("TW_SPLIT_TWINS", 2);
+    K.defer_min_e = env_int("TW_DEFER_MIN_E", 5);
+    K.lean_min_e = env_int("TW_LEAN_MIN_E", 5);
+    K.lean_grid = std::max(env_int("TW_LEAN_GRID", TW_LEAN_GRID), 1);
+    K.tile_max_deep = std::min(std::max(env_int("TW_TILE_MAX_DEEP", kTileMax), 0), kTileMax);
+    K.part_slots_max = (int64_t)std::max(env_int("TW_PART_SLOTS_MAX", 16 << 20), 1024);
+    K.part_budget_deep = env_int("TW_PART_BUDGET_DEEP", 2);
+    K.fit_sort = env_int("TW_FIT_SORT", 0);
+    return K;
+}
+
 // MT19937 as numpy's RandomState runs it (the published reference algorithm of Matsumoto & Nishimura; seeding of an integer
 // seed = init_genrand, `random_sample` = (a >> 5, b >> 6) -> (a * 2^26 + b) / 2^53): `Mt19937(s).random_sample()` yields the
 // doubles of `np.random.RandomState(s).random_sample()`.  Used for the k-means++ draws of the mixture refit (tw_fit.h).
@@ -85,41 +140,14 @@ struct tw_engine {
     // the window / selection stage of a class follows its enumeration on the class' stream (run_pass): the three instantiations of
     // k_select_heavy on streams of their own beside it, forked from and joined to the class' stream
     hipStream_t sel_stream[3] = {};
-    // ... and a second set for the stages of the other classes that hold a large share of the batch's spans (their searches one after the
-    // other on the class' stream were the longest chain of a pass on the nodejs shape: 4.7 + 8.7 + 1.8 ms for the three one-endpoint services)
-    hipStream_t sel_stream2[3] = {};
-    int64_t select_fork_min = 0;         // TW_SELECT_FORK_MIN: incoming spans of a class from which its stage forks too (0 = only the deepest class)
     hipEvent_t prep_ev = nullptr;              // the per-pass fills the selection stage needs (main stream, beside the enumerations)
     hipEvent_t post_fork[kMaxEp + 1] = {}, post_join[kMaxEp + 1][3] = {}, post_done[kMaxEp + 1] = {};
-    hipEvent_t tile_ev[kMaxEp + 1] = {};       // class E's tile kernel done (launch_enumerate: gating of the classes launched after it)
-    // a class of many tiles is launched in stretches: the wavefront kernel of a stretch's listed spans on the class' second stream
-    // beside the tile kernel of the next stretch (launch_enumerate)
-    hipStream_t cls_stream2[kMaxEp + 1] = {};
-    hipEvent_t stretch_ev[kMaxEp + 1][kEnumStretches] = {}, stretch_done[kMaxEp + 1] = {};
-    int enum_stretches = 1, stretch_min_tiles = 2048;   // TW_ENUM_STRETCHES (1 = one launch: the default, see launch_enumerate), TW_STRETCH_MIN_TILES (tiles per stretch at least)
-    int heavy_grid = 4096, select_grid = 0;             // TW_HEAVY_GRID: most persistent wavefronts of k_enumerate_heavy per launch; TW_SELECT_GRID: of k_select_heavy (0 = by the layout's LDS, select_heavy_grid)
-    int debug_lists = 0;                                // TW_DEBUG_LISTS=1: the list counters of the first enumeration are copied to the host per class (tw_debug_worklists)
-    int32_t first_lists[3][kMaxEp + 1] = {};            // ... narrow, wide, long enumerations
-    hipEvent_t gate_ev = nullptr;              // ... the last one recorded in the current launch_enumerate_all
-    int tile_gate = 0;                         // TW_TILE_GATE (measured on the media shape: the tile kernels one after the other take 1.9 + 1.5 + 1.9 ms, beside one another 3.7 -- off)
-    int stage_min_tiles = 1024;                // TW_STAGE_MIN_TILES: batches of fewer tiles per class on average join the classes after the enumeration (a stage is 17 small
-                                               // launches per class: the 1 M-span Alibaba-shape slice, eight classes of 300 tiles, takes 7.8 ms per step staged and 6.4 joined)
+    Knobs K{};                                 // the TW_* variables as tw_create found them (read_knobs)
+    int32_t first_lists[3][kMaxEp + 1] = {};   // K.debug_lists: the list counters of the first enumeration per class -- narrow, wide, long enumerations
     int32_t *rank_in = nullptr, *rank_out = nullptr;   // scratch of sort_ends: rank of a span's end time less its index
     bool class_params = false;                 // pass 1 of a staged batch: sort_ends / k_block_params per class on the class' stream
-    int prio_min_e = 0, prio_high = 0;
-    bool prio_any = false;
-    int pipeline = 1;                          // TW_CLASS_PIPELINE=0: every class joins the engine's stream after its enumeration (measurements, tests)
     std::string err;
     int state = ST_EMPTY;
-    int tile = kTile;   // incoming spans (threads) per workgroup of the per-span kernels
-    int tile_threads = 2; // threads per incoming span of k_enumerate_tile (its items and tuples are spread over all of them)
-    int tile_single = 1;  // TW_TILE_SINGLE: the one-endpoint class takes the lean path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
-    int tile_rank = 1;    // TW_TILE_RANK: the general path of k_enumerate_tile ranks long spans among their compacted survivors (0 = the all-pairs loop: A/B runs, bisection)
-    int block_params = 1; // TW_BLOCK_PARAMS: pass-1 block parameters by a wavefront per group of blocks (0 = the thread-per-slot kernel: A/B runs, bisection)
-    int tile_single_threads = 1;   // TW_TILE_SINGLE_THREADS: threads per incoming span on that path (media shape: 19.3-19.4 ms per step with one, 19.5-19.6 with two)
-    int tile_pair = 1;    // TW_TILE_PAIR: the two-endpoint class takes the pair path of k_enumerate_tile (0 = the general path: A/B runs, bisection)
-    int tile_pair_threads = 2;   // TW_TILE_PAIR_THREADS: threads per incoming span on that path (1 or 2)
-    int coop = kCoop;   // threads of the per-unit cooperative kernels
     std::vector<UnitDev> units;
     std::vector<TileDev> tiles;
     std::vector<int64_t> gs_off_h;
@@ -152,11 +180,9 @@ struct tw_engine {
     int64_t fit_tape_cap = 0;
     bool fit_runs_pending = false;          // k_fit_runs is queued, its refusal flag not read yet (fit_prepare_launch / fit_prepare)
     bool fit_prepared = false;              // the gap rows of the resident pass-1 result are sorted and run-length compressed
-    int tile_sub_max = 8;
     int32_t hard_pass1[kMaxEp + 1] = {};    // per class: windows its stage listed for k_select_dp in pass 1 (-1 not known)
     int8_t wide_pass1[kMaxEp + 1] = {};     // per class: -1 not known, 0 / 1 = the first enumeration of pass 1 listed no / some span with wide windows
     int32_t split_pass1[kMaxEp + 1] = {};   // per class: spans the first enumeration of pass 1 cut into parts (-1 not known): sizes the merge launch of pass 2 (a guess that only costs time when wrong)
-    int lean_pool = 512;                    // doubles of LDS for the pair tables of k_enumerate_lean (TW_LEAN_POOL)
     bool pass1_done = false;                // tw_run_pass1 has run on the resident batch (tw_run_pass2 reads its cut-offs, windows, tuple counts)
     std::vector<int32_t> fit_max_n;         // per slot min(5, #unique), 0 = nothing to fit (host copy, tw_fit_rows)
     bool fit_max_n_valid = false;           // ... of the rows that are prepared now (cleared with fit_prepared)
@@ -213,7 +239,7 @@ struct tw_engine {
     SigDev G{};                             // tw_trace_signatures (tw_sig.h); sig_ready: the result of sig_q on the forest is resident, a further
     bool sig_ready = false, ref_set = false;        // call with the same query only copies; ref_set: the reference set, keyed by root row
     tw_sig_query sig_q{};
-    int32_t ref_mode = 0, sig_hash_bits = 64;
+    int32_t ref_mode = 0;
     int64_t sig_rows_cap = 0, sig_trees_cap = 0, sig_ent_cap = 0, sig_ref_cap = 0, sig_summary[6] = {0, 0, 0, 0, 0, 0};
     ProfDev F{};                            // tw_class_profiles (tw_prof.h); prof_ready: the profile of the resident signature result and the
     bool prof_ready = false;                // resident attribution is resident, a further call only copies
@@ -311,12 +337,12 @@ int copy_out(tw_engine* e, T* dst, const U* src, size_t count) {
 
 // launch shapes.  Flat kernels: a thread per item, workgroups of 256.  Persistent wavefronts that take `per_wave` items at a time:
 // workgroups of `waves` wavefronts, at most 8192 of them.  (TW_COOP_THREADS < 64, the emulation of the tests: that many threads.)
-unsigned flat_threads(const tw_engine* e) { return (unsigned)(e->coop >= 64 ? 256 : e->coop); }
+unsigned flat_threads(const tw_engine* e) { return (unsigned)(e->K.coop >= 64 ? 256 : e->K.coop); }
 unsigned flat_grid(int64_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
 struct WaveShape { dim3 grid, block; };
 WaveShape wave_shape(const tw_engine* e, int64_t n, int per_wave, int waves) {
     const int64_t want = (n / per_wave + 1 + waves - 1) / waves;
-    return WaveShape{dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(e->coop >= 64 ? 64u * (unsigned)waves : (unsigned)e->coop)};
+    return WaveShape{dim3((unsigned)std::min<int64_t>(want, 8192)), dim3(e->K.coop >= 64 ? 64u * (unsigned)waves : (unsigned)e->K.coop)};
 }
 
 // stage events: milliseconds between events a and b of the stage whose first event is `stage` (SE_*)
@@ -381,8 +407,7 @@ int need_forest(tw_engine* e, const char* fn) {
 
 int ensure_class_stream(tw_engine* e, int E) {
     if (e->cls_stream[E] != nullptr) return TW_OK;
-    if (e->prio_min_e > 0 && E >= e->prio_min_e && e->prio_any) HIPCHK(hipStreamCreateWithPriority(&e->cls_stream[E], hipStreamDefault, e->prio_high));
-    else HIPCHK(hipStreamCreate(&e->cls_stream[E]));
+    HIPCHK(hipStreamCreate(&e->cls_stream[E]));
     return TW_OK;
 }
 
@@ -438,9 +463,9 @@ const char* kernel_error_text(int code) {
 template <class Tr>
 int run_scan(tw_engine* e, const TileSet& S, hipStream_t st, typename Tr::T* agg) {
     const Dev& P = e->P;
-    hipLaunchKernelGGL((k_scan_local<Tr>), dim3(S.n), dim3(e->tile), 0, st, P, S, agg);
-    hipLaunchKernelGGL((k_scan_spine<Tr>), dim3(P.n_units), dim3(e->coop), 0, st, P, S, agg);
-    hipLaunchKernelGGL((k_scan_fix<Tr>), dim3(S.n), dim3(e->tile), 0, st, P, S, agg);
+    hipLaunchKernelGGL((k_scan_local<Tr>), dim3(S.n), dim3(e->K.tile), 0, st, P, S, agg);
+    hipLaunchKernelGGL((k_scan_spine<Tr>), dim3(P.n_units), dim3(e->K.coop), 0, st, P, S, agg);
+    hipLaunchKernelGGL((k_scan_fix<Tr>), dim3(S.n), dim3(e->K.tile), 0, st, P, S, agg);
     HIPCHK(hipGetLastError());
     return TW_OK;
 }
@@ -451,7 +476,7 @@ TileSet class_tiles(const tw_engine* e, int E) { return TileSet{e->tile_ids + e-
 // (no-skip batches: every endpoint list holds one span per incoming span, all lists sorted by (start, end))
 int sort_ends(tw_engine* e, const TileSet& S, hipStream_t st) {   // (the counters e->rank_in / rank_out zeroed by the caller)
     const Dev& P = e->P;
-    const dim3 tiles(S.n), tb(e->tile);
+    const dim3 tiles(S.n), tb(e->K.tile);
     hipLaunchKernelGGL(k_rank_ends, tiles, tb, 0, st, P, S, e->rank_in, e->rank_out);
     hipLaunchKernelGGL(k_place_ends, tiles, tb, 0, st, P, S, (const int32_t*)e->rank_in, (const int32_t*)e->rank_out);
     HIPCHK(hipGetLastError());
@@ -461,14 +486,14 @@ int sort_ends(tw_engine* e, const TileSet& S, hipStream_t st) {   // (the counte
 // ComputeEpPairDistParams3 behind sort_ends: the blocks of every unit (cls = 0) or of the units of one endpoint-count class
 void launch_block_params(tw_engine* e, int cls, hipStream_t st) {
     const Dev& P = e->P;
-    if (e->block_params == 0) {
+    if (e->K.block_params == 0) {
         const int64_t total = e->n_gp;
         hipLaunchKernelGGL(k_block_params, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, P, total, cls);
         return;
     }
     const int n = e->blk_cls_off[cls + 1] - e->blk_cls_off[cls];
     if (n <= 0) return;
-    const int threads = e->coop >= 64 ? 64 * std::min(e->coop / 64, kParamWaves) : e->coop, waves = std::max(threads / 64, 1);
+    const int threads = e->K.coop >= 64 ? 64 * std::min(e->K.coop / 64, kParamWaves) : e->K.coop, waves = std::max(threads / 64, 1);
     hipLaunchKernelGGL(k_block_params_wave, dim3((unsigned)((n + waves - 1) / waves)), dim3(threads), 0, st, P, (const BlockRef*)(e->blk_tab + e->blk_cls_off[cls]), n);
 }
 
@@ -481,17 +506,15 @@ void launch_block_params(tw_engine* e, int cls, hipStream_t st) {
 // Extra work-list entries of a class for the parts of its split enumerations.  Up to four endpoints few spans are split (an eighth of
 // the class + 64 was never short); in the deep call graphs most wavefront-enumerated spans are, and a budget that runs out leaves
 // whichever spans come last unsplit -- single wavefronts then hold the class' kernel for milliseconds (round 5: 3 of its 4 ms).
-// (Round 6, with the budget kept exactly -- bump_reserve in tw_kernels.h: the media shape at eight requests in flight asks for parts
-// for 2 400 of its 20 000 four-endpoint spans and an eighth of the class serves 520 of them; serving all of them -- TW_PART_BUDGET_SHALLOW
-// = 2 entries per span, like the deep classes -- is no faster: 10.5 vs 9.5 ms per step, k_merge_parts then replays 2 400 spans' logs.
-// One-endpoint classes never split: no budget.)
-int64_t part_extra(int cls, int64_t n_cls) {
+// One-endpoint classes never split: no budget.
+int64_t part_extra(const tw_engine* e, int cls, int64_t n_cls) {
     if (n_cls <= 0) return 0;
-    static const int deep = env_int("TW_PART_BUDGET_DEEP", 2), shallow = env_int("TW_PART_BUDGET_SHALLOW", 0);
     if (cls <= 1) return 64;
-    const int mult = cls >= 5 ? deep : shallow;
-    return (mult > 0 ? n_cls * mult : n_cls / 8) + 64;
+    const int deep = e->K.part_budget_deep;
+    return (cls >= 5 && deep > 0 ? n_cls * deep : n_cls / 8) + 64;
 }
+
+constexpr int pair_pool(int E) { return E > 4 ? 2048 : (E > 1 ? kPairPoolPerEp * E : 1); }   // doubles of pair-term tables per wavefront of k_enumerate_heavy<E>
 
 // `listed` (mode 1 only): the class' entries of heavy_in_count as the host read them with the round's change count -- a class, or an
 // instantiation, with nothing listed is not launched at all.
@@ -508,28 +531,23 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
     if (n_narrow == 0 && n_wide == 0) return;
     hipStream_t st = e->cls_stream[E];
     (void)hipStreamWaitEvent(st, e->cls_ev[0], 0);
-    // The tile kernel of a class that fills the GPU runs before those of the classes with fewer endpoints instead of beside them: its
-    // chain (wavefront kernels, merge, selection: few wavefronts, long tails) is the longest of the pass and overlaps with the tile
-    // kernels that follow, instead of starting when everything else has ended (TW_TILE_GATE: tiles from which a class gates, 0 = never)
-    if (mode == 0 && e->gate_ev != nullptr) (void)hipStreamWaitEvent(st, e->gate_ev, 0);
     const Dev& P = e->P;
-    const dim3 hb(std::min(e->coop, kHeavyThreads));
-    const int pool = E > 4 ? 2048 : (E > 1 ? kPairPoolPerEp * E : 1);       // doubles of pair-term tables per wavefront of k_enumerate_heavy
+    const dim3 hb(std::min(e->K.coop, kHeavyThreads));
+    constexpr int pool = pair_pool(E);
     const size_t pool_bytes = sizeof(double) * (size_t)pool;
     // (k_enumerate_lean: root / closing term tables + an LDS pool of pair tables for the common case, larger pair tables in global memory)
-    const size_t lean_bytes = sizeof(double) * (size_t)(2 * kMaxEp * kNarrow + e->lean_pool), lean_bytes_w = sizeof(double) * (size_t)(2 * kMaxEp * 64 * kCandWords + e->lean_pool);
+    const size_t lean_bytes = sizeof(double) * (size_t)(2 * kMaxEp * kNarrow + e->K.lean_pool), lean_bytes_w = sizeof(double) * (size_t)(2 * kMaxEp * 64 * kCandWords + e->K.lean_pool);
     const bool lean = E >= P.lean_min_e && !e->skip_mode;   // the deep call graphs: k_enumerate_lean; what it hands on to k_enumerate_heavy is launched by launch_enumerate_all
     const int cap = P.heavy_in_off[E + 1] - P.heavy_in_off[E];
     auto grid_for = [&](int known, int most) { return std::max(std::min(((known >= 0 ? known : cap) + kWorkChunk - 1) / kWorkChunk, most), 1); };   // persistent wavefronts pulling spans from the work list
     auto narrow = [&](int part, int g) {
-        if (lean) hipLaunchKernelGGL((k_enumerate_lean<kNarrow>), dim3(g), hb, lean_bytes, st, P, pass, mode, part, e->lean_pool, E, E);
+        if (lean) hipLaunchKernelGGL((k_enumerate_lean<kNarrow>), dim3(g), hb, lean_bytes, st, P, pass, mode, part, e->K.lean_pool, E, E);
         else hipLaunchKernelGGL((k_enumerate_heavy<E, kNarrow>), dim3(g), hb, pool_bytes, st, P, pass, mode, part, pool);
     };
     auto wide = [&](int part, int g) {
-        if (lean) hipLaunchKernelGGL((k_enumerate_lean<64 * kCandWords>), dim3(g), hb, lean_bytes_w, st, P, pass, mode, part, e->lean_pool, E, E);
+        if (lean) hipLaunchKernelGGL((k_enumerate_lean<64 * kCandWords>), dim3(g), hb, lean_bytes_w, st, P, pass, mode, part, e->K.lean_pool, E, E);
         else hipLaunchKernelGGL((k_enumerate_heavy<E, 64 * kCandWords>), dim3(g), hb, pool_bytes, st, P, pass, mode, part, pool);
     };
-    bool stretched = false;
     if (mode == 0 && pass == 1 && e->class_params) {   // the class' sorted end times and block parameters (run_pass)
         const TileSet S = class_tiles(e, E);
         (void)sort_ends(e, S, st);
@@ -538,57 +556,30 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
     if (mode == 0) {
         // cut-offs and work lists, the short enumerations: the tile kernel.  A class of few tiles: several workgroups per tile, until
         // the class fills the CUs twice over
-        const bool single = E == 1 && e->tile_single != 0;
-        const bool pair = E == 2 && e->tile_pair != 0;
-        const dim3 tile_block(e->tile >= 64 ? e->tile * (single ? e->tile_single_threads : (pair ? e->tile_pair_threads : e->tile_threads)) : e->tile);
+        const bool single = E == 1 && e->K.tile_single != 0;
+        const bool pair = E == 2 && e->K.tile_pair != 0;
+        const dim3 tile_block(e->K.tile >= 64 ? e->K.tile * (single ? e->K.tile_single_threads : (pair ? e->K.tile_pair_threads : e->K.tile_threads)) : e->K.tile);
         int sub = 1;
-        while (sub < e->tile_sub_max && nt * sub < 512 && (e->tile / (sub * 2)) * (sub * 2) == e->tile && e->tile / (sub * 2) >= 8) sub *= 2;
-        // A class of many tiles in stretches: what a stretch's tiles listed for the wavefront kernel is enumerated on the class' second
-        // stream beside the tile kernel of the next stretch (the wavefront kernel of the whole class behind the last tile ran 1.2-1.6 ms
-        // at 1.5 wavefronts per SIMD on the media shape, a quarter of the class' chain).  Not for the classes whose wavefront kernel
-        // appends list parts behind the listed entries (E >= defer_min_e) nor for k_enumerate_lean.
-        const int ns = (!lean && !e->skip_mode && !(E >= 3 && E >= P.defer_min_e) && e->cls_stream2[E] != nullptr)
-                           ? std::max(std::min(e->enum_stretches, nt / e->stretch_min_tiles), 1) : 1;
-        stretched = ns > 1;
-        for (int j = 0; j < ns; j++) {
-            const int t0 = (int)((int64_t)nt * j / ns), t1 = (int)((int64_t)nt * (j + 1) / ns);
-            const int32_t* ids = e->tile_ids + e->tile_cls_off[E] + t0;
-            const bool sub_tile = e->tile == kTile && e->tile / sub == kSubTileSpans;   // (the instantiation with tables for a sub-tile's 16 spans: a third of the LDS)
-            if constexpr (E == 1) {   // (the lean path: instantiated for one endpoint only)
-                if (single && sub_tile) hipLaunchKernelGGL((k_enumerate_tile<1, kSubTileSpans, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-                else if (single) hipLaunchKernelGGL((k_enumerate_tile<1, kTile, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            }
-            if constexpr (E == 2) {   // (the pair path: instantiated for two endpoints only)
-                if (pair && sub_tile) hipLaunchKernelGGL((k_enumerate_tile<2, kSubTileSpans, false, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-                else if (pair) hipLaunchKernelGGL((k_enumerate_tile<2, kTile, false, true>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            }
-            if (single || pair) {}
-            else if (sub_tile)
-                hipLaunchKernelGGL((k_enumerate_tile<E, kSubTileSpans>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            else
-                hipLaunchKernelGGL((k_enumerate_tile<E>), dim3((t1 - t0) * sub), tile_block, 0, st, P, pass, ids, t1 - t0, sub);
-            if (ns > 1) {
-                hipLaunchKernelGGL(k_enum_snapshot, dim3(1), dim3(1), 0, st, P, E, j + 1);
-                if (j + 1 < ns) {   // (the last stretch's spans: on the class' stream itself)
-                    hipStream_t s2 = e->cls_stream2[E];
-                    (void)hipEventRecord(e->stretch_ev[E][j], st);
-                    (void)hipStreamWaitEvent(s2, e->stretch_ev[E][j], 0);
-                    hipLaunchKernelGGL((k_enumerate_heavy<E, kNarrow>), dim3(grid_for(-1, e->heavy_grid)), hb, pool_bytes, s2, P, pass, mode, (j + 1) << 8, pool);
-                } else {
-                    hipLaunchKernelGGL((k_enumerate_heavy<E, kNarrow>), dim3(grid_for(-1, e->heavy_grid)), hb, pool_bytes, st, P, pass, mode, (j + 1) << 8, pool);
-                    (void)hipEventRecord(e->stretch_done[E], e->cls_stream2[E]);
-                    (void)hipStreamWaitEvent(st, e->stretch_done[E], 0);
-                }
-            }
-        }
-        if (e->tile_gate > 0 && nt >= e->tile_gate) { (void)hipEventRecord(e->tile_ev[E], st); e->gate_ev = e->tile_ev[E]; }
+        while (sub < e->K.tile_sub && nt * sub < 512 && (e->K.tile / (sub * 2)) * (sub * 2) == e->K.tile && e->K.tile / (sub * 2) >= 8) sub *= 2;
+        const bool sub_tile = e->K.tile == kTile && e->K.tile / sub == kSubTileSpans;   // (the instantiation with tables for a sub-tile's 16 spans: a third of the LDS)
+        auto tile = [&](auto spans, auto lean_single, auto lean_pair) {
+            hipLaunchKernelGGL((k_enumerate_tile<E, decltype(spans)::value, decltype(lean_single)::value, decltype(lean_pair)::value>), dim3(nt * sub), tile_block, 0, st,
+                               P, pass, (const int32_t*)(e->tile_ids + e->tile_cls_off[E]), nt, sub);
+        };
+        auto tile_path = [&](auto spans) {   // (the lean paths: instantiated for one and for two endpoints only)
+            if constexpr (E == 1) { if (single) return tile(spans, std::true_type{}, std::false_type{}); }
+            if constexpr (E == 2) { if (pair) return tile(spans, std::false_type{}, std::true_type{}); }
+            tile(spans, std::false_type{}, std::false_type{});
+        };
+        if (sub_tile) tile_path(std::integral_constant<int, kSubTileSpans>{});
+        else tile_path(std::integral_constant<int, kTile>{});
     }
     // the wavefront kernels of the class: the spans the tile kernel handed over (mode 1: the spans k_detect_gone listed), the long
     // enumerations first; the list parts of the spans those launches deferred (kListSplitFlag); the parts combined, the few spans whose
     // order of equal scores the parts left undecided enumerated whole.  Every launch of the chain has a work-list cursor of its own
     // (enum_cursor): nothing is reset in between.
-    if (n_narrow != 0 && !stretched) narrow(0, grid_for(n_narrow, e->heavy_grid));
-    if (n_wide != 0) wide(0, grid_for(n_wide, 1024));   // (stretched: the wide instantiation once, over the whole lists)
+    if (n_narrow != 0) narrow(0, grid_for(n_narrow, kHeavyGrid));
+    if (n_wide != 0) wide(0, grid_for(n_wide, 1024));
     if (mode == 0 && E >= 3 && E >= P.defer_min_e) { narrow(3, grid_for(-1, 4096)); if (n_wide != 0) wide(3, grid_for(-1, 1024)); }
     if (mode == 0 && E > 1) {
         // (34 KB of LDS a workgroup: a thousand of them ask for all there is -- and wait for it while the selection kernels of other
@@ -597,10 +588,10 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
         // its launch is sized by pass 1's count; the workgroups stride over the records, so a wrong guess only costs time)
         const int nsplit = (pass == 2 && mode == 0) ? e->split_pass1[E] : -1;
         const int merge_grid = nsplit < 0 ? (cap >= (1 << 20) ? 1024 : 256) : std::max(std::min(nsplit, 1024), 8);
-        hipLaunchKernelGGL(k_merge_parts, dim3(merge_grid), dim3(std::min(e->coop, 64)), 0, st, P, pass, E, E);
+        hipLaunchKernelGGL(k_merge_parts, dim3(merge_grid), dim3(std::min(e->K.coop, 64)), 0, st, P, pass, E, E);
         narrow(1, nsplit == 0 ? 8 : 256); if (n_wide != 0) wide(1, nsplit == 0 ? 8 : 64);
     }
-    if (e->debug_lists != 0 && mode == 0) {
+    if (e->K.debug_lists != 0 && mode == 0) {
         (void)hipMemcpyAsync(&e->first_lists[0][E], P.heavy_in_count + E, sizeof(int32_t), hipMemcpyDeviceToHost, st);
         (void)hipMemcpyAsync(&e->first_lists[1][E], P.heavy_in_count + kMaxEp + 1 + E, sizeof(int32_t), hipMemcpyDeviceToHost, st);
         (void)hipMemcpyAsync(&e->first_lists[2][E], P.heavy_big_count + E, sizeof(int32_t), hipMemcpyDeviceToHost, st);
@@ -616,8 +607,8 @@ void launch_fallback(tw_engine* e, int pass, int mode, const int32_t* fb) {
     if (fb[E] <= 0) return;
     hipStream_t st = e->cls_stream[E];
     (void)hipStreamWaitEvent(st, e->cls_ev[0], 0);
-    const dim3 hb(std::min(e->coop, kHeavyThreads));
-    const int pool = E > 4 ? 2048 : (E > 1 ? kPairPoolPerEp * E : 1);
+    const dim3 hb(std::min(e->K.coop, kHeavyThreads));
+    constexpr int pool = pair_pool(E);
     const int grid = std::max(std::min((fb[E] + kWorkChunk - 1) / kWorkChunk, 1024), 1);
     hipLaunchKernelGGL((k_enumerate_heavy<E, kNarrow>), dim3(grid), hb, sizeof(double) * (size_t)pool, st, e->P, pass, mode, 4, pool);
     hipLaunchKernelGGL((k_enumerate_heavy<E, 64 * kCandWords>), dim3(grid), hb, sizeof(double) * (size_t)pool, st, e->P, pass, mode, 4, pool);
@@ -630,11 +621,11 @@ void launch_fallback(tw_engine* e, int pass, int mode, const int32_t* fb) {
 // tiles on the engine's stream beside the enumerations.  The rest in five launches, k_cut_scan .. k_index_fix in tw_kernels.h)
 int launch_windows(tw_engine* e, const TileSet& S, hipStream_t st) {
     const Dev& P = e->P;
-    const dim3 tiles(S.n), tb(e->tile);
+    const dim3 tiles(S.n), tb(e->K.tile);
     hipLaunchKernelGGL(k_cut_scan, tiles, tb, 0, st, P, S, e->agg_i32);
-    hipLaunchKernelGGL((k_scan_spine<ScanSegStart>), dim3(P.n_units), dim3(e->coop), 0, st, P, S, e->agg_i32);
+    hipLaunchKernelGGL((k_scan_spine<ScanSegStart>), dim3(P.n_units), dim3(e->K.coop), 0, st, P, S, e->agg_i32);
     hipLaunchKernelGGL(k_flags_scan, tiles, tb, 0, st, P, S, (const int32_t*)e->agg_i32, e->agg_i32b);
-    hipLaunchKernelGGL((k_scan_spine<ScanWinId>), dim3(P.n_units), dim3(e->coop), 0, st, P, S, e->agg_i32b);
+    hipLaunchKernelGGL((k_scan_spine<ScanWinId>), dim3(P.n_units), dim3(e->K.coop), 0, st, P, S, e->agg_i32b);
     hipLaunchKernelGGL(k_index_fix, tiles, tb, 0, st, P, S, (const int32_t*)e->agg_i32b);
     HIPCHK(hipGetLastError());
     return TW_OK;
@@ -652,10 +643,9 @@ int launch_windows(tw_engine* e, const TileSet& S, hipStream_t st) {
 // Persistent workgroups of one wavefront each, as many as the CUs hold at a time by the layout's LDS (the window's data + the small tables
 // of the level solver): 2 800 / 4 300 / 6 100 for the three layouts of a two-endpoint class.  (One figure for all three, 4 096, left the
 // small layouts short of wavefronts and gave the large one a second round: nodejs shape at 14.4 M spans 40.9 -> 39.2 ms with 6 144, 41.4
-// with 8 192.)  TW_SELECT_GRID > 0 is that one figure again.
+// with 8 192.)
 template <class LDS>
 unsigned select_heavy_grid(const tw_engine* e, dim3 most) {
-    if (e->select_grid > 0) return std::min<unsigned>(most.x, (unsigned)e->select_grid);
     const size_t lds = sizeof(LDS) + sizeof(SelectDpT<LDS::kW, kDpCapSmall, kDpSlotsSmall>) + 512;
     const unsigned resident = 256u * (unsigned)std::max<size_t>((160u * 1024u) / lds, 1);
     return std::max(std::min(most.x, std::min(resident, 8192u)), 1u);
@@ -675,16 +665,16 @@ void launch_select_heavy3(tw_engine* e, const TileSet& S, dim3 most, dim3 wave, 
     else launch_select_heavy3<kMaxEp>(e, S, most, wave, s0, s1, s2);
 }
 
-void launch_select_listed(tw_engine* e, const TileSet& S, hipStream_t st, int64_t n_spans, bool fork = true, bool second = false) {
+void launch_select_listed(tw_engine* e, const TileSet& S, hipStream_t st, int64_t n_spans, bool fork = true) {
     const Dev& P = e->P;
-    const dim3 wave(std::min(e->coop, 64));
+    const dim3 wave(std::min(e->K.coop, 64));
     const dim3 grid((unsigned)std::min<int64_t>(n_spans / 2 + 1, 1 << 20));   // (what the set could need at most; launch_select_heavy3 sizes each layout's launch)
     if (!fork) {
         hipLaunchKernelGGL(k_select_tiny, dim3((unsigned)std::min<int64_t>(n_spans / 2 + 1, 8192)), wave, 0, st, P, S);
         launch_select_heavy3(e, S, grid, wave, st, st, st);
         return;
     }
-    hipStream_t* ss = second ? e->sel_stream2 : e->sel_stream;
+    hipStream_t* ss = e->sel_stream;
     (void)hipEventRecord(e->post_fork[S.slot], st);
     for (int j = 0; j < 3; j++) (void)hipStreamWaitEvent(ss[j], e->post_fork[S.slot], 0);
     launch_select_heavy3(e, S, grid, wave, ss[0], ss[1], ss[2]);
@@ -697,7 +687,7 @@ void launch_select_listed(tw_engine* e, const TileSet& S, hipStream_t st, int64_
 // (`few`: the set listed no such window in pass 1 -- pass 2 rarely differs, and 512 workgroups of 70 KB of LDS take 0.1-0.2 ms to come and
 // go with nothing to do; the workgroups are persistent, a small grid is only slower when the guess is wrong)
 void launch_select_hard(tw_engine* e, const TileSet& S, hipStream_t st, bool few = false) {
-    hipLaunchKernelGGL(k_select_dp, dim3(few ? 32 : (kDpCap <= 384 ? 512 : 256)), dim3(std::min(e->coop, kDpThreads)), 0, st, e->P, S);   // (one / two workgroups per CU by their LDS)
+    hipLaunchKernelGGL(k_select_dp, dim3(few ? 32 : (kDpCap <= 384 ? 512 : 256)), dim3(std::min(e->K.coop, kDpThreads)), 0, st, e->P, S);   // (one / two workgroups per CU by their LDS)
 }
 
 // What follows a class' first enumeration, on the class' stream: its windows (pass 1), the first selection of its windows, the first
@@ -710,14 +700,13 @@ int launch_class_stage(tw_engine* e, int pass, int E) {
     hipStream_t st = e->cls_stream[E];
     (void)hipStreamWaitEvent(st, e->prep_ev, 0);
     if (pass == 1) { int rc = launch_windows(e, S, st); if (rc != TW_OK) return rc; }
-    hipLaunchKernelGGL(k_select_fast, dim3(S.n), dim3(e->tile), 0, st, e->P, S);
+    hipLaunchKernelGGL(k_select_fast, dim3(S.n), dim3(e->K.tile), 0, st, e->P, S);
     int deepest = 0;
     for (int c = 1; c <= kMaxEp; c++) if (e->tile_cls_off[c + 1] > e->tile_cls_off[c]) deepest = c;
     const int64_t n_cls = (int64_t)e->P.heavy_in_off[E + 1] - e->P.heavy_in_off[E];
-    const bool second = E != deepest && e->select_fork_min > 0 && n_cls >= e->select_fork_min && e->sel_stream2[0] != nullptr;
-    launch_select_listed(e, S, st, n_cls, E == deepest || second, second);
+    launch_select_listed(e, S, st, n_cls, E == deepest);
     launch_select_hard(e, S, st, pass == 2 && e->hard_pass1[E] == 0);
-    const dim3 tiles(S.n), tb(e->tile);
+    const dim3 tiles(S.n), tb(e->K.tile);
     hipLaunchKernelGGL(k_claim, tiles, tb, 0, st, e->P, S, E);
     hipLaunchKernelGGL(k_detect_gone, tiles, tb, 0, st, e->P, S, 0, pass == 1 ? 2 : 1);
     (void)hipEventRecord(e->post_done[E], st);
@@ -730,7 +719,6 @@ template <class Prep>
 int launch_enumerate_all(tw_engine* e, int pass, int mode, const int32_t* listed, bool staged, Prep prep) {
     // (the work-list cursors were reset with the counter block of the pass / the repair round)
     (void)hipEventRecord(e->cls_ev[0], e->stream);
-    e->gate_ev = nullptr;
     // the classes with the most endpoints first: their enumerations are the longest and end the group (each class runs on a
     // stream of its own; what is launched first is dispatched first)
     launch_enumerate<8>(e, pass, mode, listed); launch_enumerate<7>(e, pass, mode, listed); launch_enumerate<6>(e, pass, mode, listed); launch_enumerate<5>(e, pass, mode, listed);
@@ -741,13 +729,10 @@ int launch_enumerate_all(tw_engine* e, int pass, int mode, const int32_t* listed
     bool any_lean = false;
     for (int E = 1; E <= kMaxEp; E++) any_lean |= has(E) && is_lean(E);
     // the classes that are complete with their chain go on at once -- those expected to end first first (the selection streams serve
-    // the classes in this order): the fewest endpoints, or, when the tile kernels ran one after the other, the most
-    const bool deep_first = e->gate_ev != nullptr;
+    // the classes in this order): the fewest endpoints
     if (staged)
-        for (int k = 1; k <= kMaxEp; k++) {
-            const int E = deep_first ? kMaxEp + 1 - k : k;
+        for (int E = 1; E <= kMaxEp; E++)
             if (has(E) && !is_lean(E)) { int rc = launch_class_stage(e, pass, E); if (rc != TW_OK) return rc; }
-        }
     if (any_lean) {
         // what k_enumerate_lean handed on: the host reads the counts when the lean classes' chains have ended
         int32_t fb[kMaxEp + 1] = {};
@@ -830,7 +815,7 @@ int sort_rows(tw_engine* e, const Key* keys, Key* out, unsigned size, const uint
 // borrow two per-span words that the pass writes only later: the window ids and the owner words)
 int run_pass(tw_engine* e, int pass) {
     const Dev& P = e->P;
-    const dim3 tiles(P.n_tiles), tb(e->tile);
+    const dim3 tiles(P.n_tiles), tb(e->K.tile);
     const auto host_t0 = std::chrono::steady_clock::now();
     HIPCHK(hipEventRecord(e->ev[EV_BEGIN], e->stream));
     HIPCHK(hipMemsetAsync(e->ctr, 0, sizeof(int32_t) * (size_t)e->ctr_pass_ints, e->stream));   // error flag, statistics, every work-list counter
@@ -842,7 +827,7 @@ int run_pass(tw_engine* e, int pass) {
     // enumerations of other classes are still running.  TW_CLASS_PIPELINE=0 / skip mode / small batches: the classes join after the enumeration.
     int n_cls = 0;
     for (int E = 1; E <= kMaxEp; E++) n_cls += e->tile_cls_off[E + 1] > e->tile_cls_off[E] ? 1 : 0;
-    const bool staged = !e->skip_mode && e->pipeline != 0 && P.n_tiles >= (int64_t)e->stage_min_tiles * std::max(n_cls, 1);
+    const bool staged = !e->skip_mode && e->K.pipeline != 0 && P.n_tiles >= (int64_t)e->K.stage_min_tiles * std::max(n_cls, 1);
     // pass 1, ComputeEpPairDistParams3: sorted end times and block parameters -- staged: per class, at the head of the class' chain
     // (launch_enumerate: the class with the longest chain does not wait for the parameters of the others)
     e->class_params = false;
@@ -889,7 +874,7 @@ int run_pass(tw_engine* e, int pass) {
         HIPCHK(hipMemsetAsync(P.owner, 0x7f, sizeof(int32_t) * std::max<int64_t>(P.n_out_total, 1), e->stream));
         HIPCHK(hipMemsetAsync(e->skip_fetch, 0, sizeof(long long) * (size_t)std::max<int64_t>(e->skip_fetch_n, 1), e->stream));
         HIPCHK(hipMemsetAsync(P.w_dirty, 0, (size_t)P.n_in_total, e->stream));
-        hipLaunchKernelGGL(k_skip_walk, dim3(P.n_units), dim3(std::min(e->coop, 64)), 0, e->stream, P, (const SkipUnitDev*)e->skip_units);
+        hipLaunchKernelGGL(k_skip_walk, dim3(P.n_units), dim3(std::min(e->K.coop, 64)), 0, e->stream, P, (const SkipUnitDev*)e->skip_units);
         HIPCHK(hipEventRecord(e->ev[EV_SEL], e->stream));
         HIPCHK(hipEventRecord(e->ev[EV_REPAIR], e->stream));
         hipLaunchKernelGGL(k_finalize, tiles, tb, 0, e->stream, P, all_tiles_host(e));
@@ -1046,9 +1031,9 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
     HIPCHK(hipMemsetAsync(L.kmax, 0, sizeof(int32_t) * P.n_units, e->stream));
     HIPCHK(hipMemsetAsync(L.err, 0, sizeof(int32_t), e->stream));
     HIPCHK(hipMemsetAsync(L.owner_req, 0xff, sizeof(int32_t) * n_out, e->stream));
-    hipLaunchKernelGGL(k_load_scale_in, dim3(P.n_tiles), dim3(e->tile), 0, e->stream, L);
-    hipLaunchKernelGGL(k_load_scale_out, dim3(P.n_tiles), dim3(e->tile), 0, e->stream, L);
-    hipLaunchKernelGGL(k_load_to_int, dim3(P.n_tiles), dim3(e->tile), 0, e->stream, L);
+    hipLaunchKernelGGL(k_load_scale_in, dim3(P.n_tiles), dim3(e->K.tile), 0, e->stream, L);
+    hipLaunchKernelGGL(k_load_scale_out, dim3(P.n_tiles), dim3(e->K.tile), 0, e->stream, L);
+    hipLaunchKernelGGL(k_load_to_int, dim3(P.n_tiles), dim3(e->K.tile), 0, e->stream, L);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> kmax_h((size_t)P.n_units);
     int32_t err_h = 0;
@@ -1084,7 +1069,7 @@ extern "C" int tw_scale_load(tw_engine* e, const int32_t* unit_factor, const int
         if (host != nullptr) HIPCHK(hipMemcpyAsync(host, perm, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
-    hipLaunchKernelGGL(k_load_retruth, dim3(P.n_tiles), dim3(e->tile), 0, e->stream, L, (const int32_t*)pos_in, (const int32_t*)pos_out, e->truth,
+    hipLaunchKernelGGL(k_load_retruth, dim3(P.n_tiles), dim3(e->K.tile), 0, e->stream, L, (const int32_t*)pos_in, (const int32_t*)pos_out, e->truth,
                        has_trace ? e->in_trace : nullptr);
     HIPCHK(hipGetLastError());
     for (int u = 0; u < P.n_units; u++) {
@@ -1108,15 +1093,7 @@ int tw_create(int device_id, tw_engine** out) {
     *out = nullptr;
     tw_engine* e = new tw_engine();
     e->device = device_id;
-    e->tile = std::min(std::max(env_int("TW_TILE", kTile), 1), kTile);
-    e->tile_threads = std::min(std::max(env_int("TW_TILE_THREADS", 2), 1), 4);
-    e->tile_single = env_int("TW_TILE_SINGLE", 1);
-    e->block_params = env_int("TW_BLOCK_PARAMS", 1);
-    e->tile_rank = env_int("TW_TILE_RANK", 1) != 0 ? 1 : 0;
-    e->tile_single_threads = std::min(std::max(env_int("TW_TILE_SINGLE_THREADS", 1), 1), 4);
-    e->tile_pair = env_int("TW_TILE_PAIR", 1);
-    e->tile_pair_threads = std::min(std::max(env_int("TW_TILE_PAIR_THREADS", 2), 1), 2);
-    e->coop = std::min(std::max(env_int("TW_COOP_THREADS", kCoop), 1), kCoop);
+    e->K = read_knobs();
     // The engine runs its endpoint-count classes and window classes on streams of their own (up to 8 + 3 beside its own).  The
     // runtime multiplexes a process' streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default: classes that share a queue run one
     // after the other (Alibaba-shape slice, eight classes: 9.5 / 11.2 ms per pass with 4 or 8 queues, 6.3 / 7.0 ms with 12 or 16;
@@ -1124,47 +1101,21 @@ int tw_create(int device_id, tw_engine** out) {
     // (torch, RCCL, other HIP libraries in it): the library does not touch it.  The applications of this repository export it
     // before anything initialises HIP (bench.py, python -m traceweaver_amd.executor); other hosts do the same, or set
     // TW_SET_HW_QUEUES=1 to let this call export it when it is still unset (effective if the engine is the process' first user of HIP).
-    if (env_int("TW_SET_HW_QUEUES", 0) != 0) setenv("GPU_MAX_HW_QUEUES", "12", 0);
+    if (e->K.set_hw_queues != 0) setenv("GPU_MAX_HW_QUEUES", "12", 0);
     hipError_t s = hipSetDevice(device_id);
     if (s == hipSuccess) s = hipStreamCreate(&e->stream);
     for (int i = 0; i < EV_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->ev[i]);
     for (int i = 0; i < SE_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->stage_ev[i]);
-    // (Priorities for the class streams were measured: every class stream created with one -- the classes of four and more
-    // endpoints highest -- takes the media shape's enumeration from 4.6 to 4.4 ms per launch set and the nodejs shape's from 0.9
-    // to 1.2 ms: streams created with a priority, any, are mapped to the hardware queues differently and that shape's two classes
-    // partly serialise.  Only the long classes prioritised: no change.  Plain streams.)
-    // Round 6, with the classes' window / selection stages on their streams: what a deep class' tile kernel gains by going first is no
-    // longer lost to a join -- its wavefront kernels and its stage then run beside the other classes' tile kernels.  TW_PRIO_MIN_E:
-    // classes from this many endpoints on get the high priority (0 = plain streams everywhere).
-    const int prio_min_e = env_int("TW_PRIO_MIN_E", 0);
-    int prio_least = 0, prio_greatest = 0;
-    if (s == hipSuccess) s = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     // (the class streams are created when a batch first holds the class, tw_load_batch: the streams of a process share its hardware
     // queues, and a queue shared by two busy streams runs their kernels one after the other -- an engine that only ever sees three
     // classes owns seven streams, not twelve)
-    e->prio_min_e = prio_min_e; e->prio_high = prio_greatest; e->prio_any = prio_greatest != prio_least;
     for (int i = 0; i <= kMaxEp + 1 && s == hipSuccess; i++) s = hipEventCreateWithFlags(&e->cls_ev[i], hipEventDisableTiming);
     if (s == hipSuccess) s = hipEventCreateWithFlags(&e->prep_ev, hipEventDisableTiming);
     for (int i = 0; i <= kMaxEp && s == hipSuccess; i++) {
         s = hipEventCreateWithFlags(&e->post_fork[i], hipEventDisableTiming);
-        if (s == hipSuccess) s = hipEventCreateWithFlags(&e->tile_ev[i], hipEventDisableTiming);
         if (s == hipSuccess) s = hipEventCreateWithFlags(&e->post_done[i], hipEventDisableTiming);
-        if (s == hipSuccess) s = hipEventCreateWithFlags(&e->stretch_done[i], hipEventDisableTiming);
-        for (int j = 0; j < kEnumStretches && s == hipSuccess; j++) s = hipEventCreateWithFlags(&e->stretch_ev[i][j], hipEventDisableTiming);
         for (int j = 0; j < 3 && s == hipSuccess; j++) s = hipEventCreateWithFlags(&e->post_join[i][j], hipEventDisableTiming);
     }
-    e->pipeline = env_int("TW_CLASS_PIPELINE", 1);
-    e->sig_hash_bits = std::min(std::max(env_int("TW_SIG_HASH_BITS", 64), 1), 64);
-    e->tile_gate = env_int("TW_TILE_GATE", 0);
-    e->enum_stretches = std::min(std::max(env_int("TW_ENUM_STRETCHES", 1), 1), kEnumStretches);
-    e->heavy_grid = std::max(env_int("TW_HEAVY_GRID", 4096), 64);
-    e->select_grid = std::max(env_int("TW_SELECT_GRID", 0), 0);
-    e->debug_lists = env_int("TW_DEBUG_LISTS", 0);
-    e->select_fork_min = (int64_t)env_int("TW_SELECT_FORK_MIN", 0);
-    e->stretch_min_tiles = std::max(env_int("TW_STRETCH_MIN_TILES", 2048), 1);
-    e->stage_min_tiles = env_int("TW_STAGE_MIN_TILES", 1024);
-    e->tile_sub_max = std::max(env_int("TW_TILE_SUB", 8), 1);   // workgroups per tile for classes of few tiles (1 = never)
-    e->lean_pool = std::min(std::max(env_int("TW_LEAN_POOL", 512), 1), 4096);
     if (s != hipSuccess) {
         fprintf(stderr, "tw_create: %s\n", hipGetErrorString(s));
         delete e;
@@ -1186,19 +1137,12 @@ void tw_destroy(tw_engine* e) {
         if (e->cls_ev[i]) (void)hipEventDestroy(e->cls_ev[i]);
     for (int i = 1; i <= kMaxEp; i++)
         if (e->cls_stream[i]) (void)hipStreamDestroy(e->cls_stream[i]);
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 3; i++)
         if (e->sel_stream[i]) (void)hipStreamDestroy(e->sel_stream[i]);
-        if (e->sel_stream2[i]) (void)hipStreamDestroy(e->sel_stream2[i]);
-    }
     if (e->prep_ev) (void)hipEventDestroy(e->prep_ev);
     for (int i = 0; i <= kMaxEp; i++) {
         if (e->post_fork[i]) (void)hipEventDestroy(e->post_fork[i]);
-        if (e->tile_ev[i]) (void)hipEventDestroy(e->tile_ev[i]);
         if (e->post_done[i]) (void)hipEventDestroy(e->post_done[i]);
-        if (e->stretch_done[i]) (void)hipEventDestroy(e->stretch_done[i]);
-        for (int j = 0; j < kEnumStretches; j++)
-            if (e->stretch_ev[i][j]) (void)hipEventDestroy(e->stretch_ev[i][j]);
-        if (e->cls_stream2[i]) (void)hipStreamDestroy(e->cls_stream2[i]);
         for (int j = 0; j < 3; j++)
             if (e->post_join[i][j]) (void)hipEventDestroy(e->post_join[i][j]);
     }
@@ -1249,8 +1193,8 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
         U.gp_off = gp;
         U.slot_off = (int32_t)slots;
         U.tile_off = (int32_t)e->tiles.size();
-        U.ntile = (int32_t)((n + e->tile - 1) / e->tile);
-        for (int t = 0; t < U.ntile; t++) e->tiles.push_back(TileDev{u, t * e->tile});
+        U.ntile = (int32_t)((n + e->K.tile - 1) / e->K.tile);
+        for (int t = 0; t < U.ntile; t++) e->tiles.push_back(TileDev{u, t * e->K.tile});
         seg_in[(size_t)u] = (uint32_t)U.in_off;
         const uint8_t* dag = b->dag + dagi;
         for (int k = 0; k <= E; k++) U.ep_off[k] = b->ep_off[epi + k];
@@ -1327,19 +1271,9 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     for (int cls = 1; cls <= kMaxEp; cls++)
         if (e->tile_cls_off[cls + 1] > e->tile_cls_off[cls]) {
             int rs = ensure_class_stream(e, cls); if (rs != TW_OK) return rs;
-            if (e->enum_stretches > 1 && e->tile_cls_off[cls + 1] - e->tile_cls_off[cls] >= 2 * e->stretch_min_tiles && e->cls_stream2[cls] == nullptr)
-                HIPCHK(hipStreamCreate(&e->cls_stream2[cls]));
         }
     for (int j = 0; j < 3; j++)
         if (e->sel_stream[j] == nullptr) HIPCHK(hipStreamCreate(&e->sel_stream[j]));
-    {   // (the second set only for a batch that has such a class: every stream takes a share of the hardware queues)
-        bool want = false;
-        int deepest = 0;
-        for (int cls = 1; cls <= kMaxEp; cls++) if (e->tile_cls_off[cls + 1] > e->tile_cls_off[cls]) deepest = cls;
-        for (int cls = 1; cls < deepest; cls++) want |= e->select_fork_min > 0 && heavy_off_h[cls + 1] - heavy_off_h[cls] >= e->select_fork_min;
-        for (int j = 0; j < 3 && want; j++)
-            if (e->sel_stream2[j] == nullptr) HIPCHK(hipStreamCreate(&e->sel_stream2[j]));
-    }
     const int64_t n_in_total = b->unit_in_off[b->n_units], n_out_total = b->ep_off[epi];
     if (n_in_total >= (1ll << 31) || n_out_total >= (1ll << 31)) return fail(e, TW_ERR_ARG, "batch exceeds 2^31 spans");
     if (gaps >= (1ll << 31)) return fail(e, TW_ERR_ARG, "batch too large: sum of nslot*n_in must stay below 2^31");
@@ -1378,17 +1312,17 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     P = Dev{};
     P.n_units = b->n_units;
     P.n_tiles = (int32_t)e->tiles.size();
-    P.tile_spans = e->tile;
+    P.tile_spans = e->K.tile;
     P.n_in_total = n_in_total;
     P.n_out_total = n_out_total;
     P.batch_size = b->batch_size;
     P.batch_mis = b->batch_size_mis;
-    P.split_twins = env_int("TW_SPLIT_TWINS", 2);
-    P.defer_min_e = env_int("TW_DEFER_MIN_E", 5);
-    P.lean_min_e = env_int("TW_LEAN_MIN_E", 5);
-    P.lean_grid = std::max(env_int("TW_LEAN_GRID", TW_LEAN_GRID), 1);
-    P.tile_max_deep = std::min(std::max(env_int("TW_TILE_MAX_DEEP", kTileMax), 0), kTileMax);
-    P.tile_rank = e->tile_rank;
+    P.split_twins = e->K.split_twins;
+    P.defer_min_e = e->K.defer_min_e;
+    P.lean_min_e = e->K.lean_min_e;
+    P.lean_grid = e->K.lean_grid;
+    P.tile_max_deep = e->K.tile_max_deep;
+    P.tile_rank = e->K.tile_rank;
     int rc;
     e->arena_req.clear();
     e->arena_open = true;
@@ -1421,12 +1355,12 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     {   // long enumerations: a list entry per span plus the extra entries of the split ones (an eighth of the class + 64), two
         // scratch slots per extra entry
         int64_t big_total = 0, slots = 0, want = 0;
-        for (int cls = 0; cls <= kMaxEp; cls++) want += 2 * part_extra(cls, heavy_off_h[cls + 1] - heavy_off_h[cls]);
+        for (int cls = 0; cls <= kMaxEp; cls++) want += 2 * part_extra(e, cls, heavy_off_h[cls + 1] - heavy_off_h[cls]);
         // (a scratch slot is 4.4 KB, most of it the log of a part in log mode: at most TW_PART_SLOTS_MAX slots, 16 M = 70 GB, whatever the batch)
-        static const int64_t slots_max = (int64_t)std::max(env_int("TW_PART_SLOTS_MAX", 16 << 20), 1024);
+        const int64_t slots_max = e->K.part_slots_max;
         for (int cls = 0; cls <= kMaxEp; cls++) {
             const int64_t n_cls = heavy_off_h[cls + 1] - heavy_off_h[cls];
-            int64_t extra = part_extra(cls, n_cls);
+            int64_t extra = part_extra(e, cls, n_cls);
             if (want > slots_max && extra > 64) extra = std::max<int64_t>((int64_t)((double)extra * (double)slots_max / (double)want), std::min<int64_t>(n_cls / 8 + 64, extra));
             P.heavy_big_off[cls] = (int32_t)big_total; P.part_off[cls] = (int32_t)slots;
             big_total += n_cls + extra; slots += 2 * extra;
@@ -1448,7 +1382,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     }
     for (int cls = 0; cls <= kMaxEp + 1; cls++) P.heavy_in_off[cls] = heavy_off_h[cls];
     DEV_ALLOC(P.prof, 32); DEV_ALLOC(e->key_acc, 2);
-    const int64_t sel_cap = (int64_t)P.n_tiles * e->tile + 1;   // every segment of the selection lists has room for all windows of its tiles
+    const int64_t sel_cap = (int64_t)P.n_tiles * e->K.tile + 1;   // every segment of the selection lists has room for all windows of its tiles
     {   // the counter block (every array on a 128-byte line of its own: their atomics come from different kernels)
         int64_t at = 0;
         auto take = [&](int64_t ints) { const int64_t o = at; at += (ints + 31) / 32 * 32; return o; };
@@ -1457,7 +1391,6 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
         e->ctr_round_ints = at;
         const int64_t o_pu = take(kMaxEp + 1), o_sc = take(kMaxEp + 1), o_dc = take(kMaxEp + 1), o_du = take(1), o_err = take(1), o_nd = take(P.n_units), o_us = take((int64_t)P.n_units * 16);
         const int64_t o_dr = take(kMaxEp + 1), o_ft = take(kMaxEp + 1), o_aw = take(kMaxEp + 1);
-        const int64_t o_es = take((kMaxEp + 1) * (kEnumStretches + 1) * 4), o_en = take((kMaxEp + 1) * kEnumStretches * 2);
         const int64_t o_fn = take(kFrontierSlots), o_fb = take(P.frontier_big_slots), o_pb = take(kPairSlots);   // flags of the tuple-list pools (given back by the kernels themselves)
         e->ctr_pass_ints = at;
         auto place = [=](void* q) {
@@ -1468,7 +1401,6 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
             D.defer_count = c + o_dc; D.defer_used = c + o_du;
             D.part_used = c + o_pu; D.split_count = c + o_sc; D.err = c + o_err; D.unit_ndirty = c + o_nd;
             D.redo_count = c + o_rd; D.fb_count = c + o_fc; D.defer_refused = c + o_dr; D.fb_total = c + o_ft; D.pair_busy = c + o_pb; D.any_wide = c + o_aw;
-            D.enum_snap = c + o_es; D.enum_stretch_next = c + o_en;
             D.unit_stats = (int64_t*)(c + o_us);
         };
         if (e->arena_open) e->arena_req.emplace_back(place, ((size_t)at * sizeof(int32_t) + 255) / 256 * 256);   // (placed by arena_commit, like the rest)
@@ -1651,8 +1583,6 @@ FitDev fit_dev(tw_engine* e) {
     F.gs_off = e->P.gs_off; F.slot_unit = e->slot_unit; F.slot_scored = e->slot_scored; F.models = e->fit_models; F.mix_n = e->mix_n_dev; F.mix_p = e->mix_p_dev;
     F.uval = e->fit_uval; F.ustart = e->fit_ustart; F.row_n = e->fit_row_n; F.row_uniq = e->fit_row_uniq;
     F.tape = e->fit_tape; F.tape_off = e->fit_tape_off; F.tape100 = e->fit_tape100; F.err = e->P.err; F.centres = e->fit_centres;
-    static const int by_row = env_int("TW_FIT_BY_ROW", 0);
-    F.by_row = by_row;
     return F;
 }
 
@@ -1663,13 +1593,13 @@ FitDev fit_dev(tw_engine* e) {
 // uniforms of the k-means++ draws -- and fit_prepare waits for it, reads whether a row was refused and runs the sort route then)
 int fit_prepare_launch(tw_engine* e) {
     e->fit_runs_pending = false;
-    if (e->fit_prepared || env_int("TW_FIT_SORT", 0) != 0) return TW_OK;
+    if (e->fit_prepared || e->K.fit_sort != 0) return TW_OK;
     int32_t* flag = (int32_t*)e->key_acc;
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int32_t), e->stream));
 #ifdef TW_HOST_EMULATION
-    const int runs_threads = e->coop;
+    const int runs_threads = e->K.coop;
 #else
-    const int runs_threads = e->coop >= 64 ? kRunsThreads : e->coop;
+    const int runs_threads = e->K.coop >= 64 ? kRunsThreads : e->K.coop;
 #endif
     hipLaunchKernelGGL(k_fit_runs, dim3((unsigned)e->n_slots), dim3(runs_threads), 0, e->stream, fit_dev(e), flag);
     HIPCHK(hipGetLastError());
@@ -1678,7 +1608,7 @@ int fit_prepare_launch(tw_engine* e) {
 }
 int fit_prepare(tw_engine* e) {
     if (e->fit_prepared) return TW_OK;
-    if (env_int("TW_FIT_SORT", 0) == 0) {
+    if (e->K.fit_sort == 0) {
         if (!e->fit_runs_pending) { int rl = fit_prepare_launch(e); if (rl != TW_OK) return rl; }
         e->fit_runs_pending = false;
         int32_t* flag = (int32_t*)e->key_acc;
@@ -1711,9 +1641,9 @@ int fit_prepare(tw_engine* e) {
     }
     FitDev F = fit_dev(e);
 #ifdef TW_HOST_EMULATION   // (the lane-threaded emulation of the tests runs a host thread per lane: the cooperative size there)
-    const int compress_threads = e->coop;
+    const int compress_threads = e->K.coop;
 #else
-    const int compress_threads = e->coop >= 64 ? kCompressThreads : e->coop;
+    const int compress_threads = e->K.coop >= 64 ? kCompressThreads : e->K.coop;
 #endif
     hipLaunchKernelGGL(k_fit_compress, dim3((unsigned)e->n_slots), dim3(compress_threads), 0, e->stream, F);
     HIPCHK(hipGetLastError());
@@ -1735,28 +1665,10 @@ int fit_run(tw_engine* e) {
     HIPCHK(hipMemcpyAsync(e->fit_tape100, tape100.data(), sizeof(double) * tape100.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemsetAsync(e->P.err, 0, sizeof(int32_t), e->stream));
     FitDev F = fit_dev(e);
-    const int threads = e->coop >= 64 ? kFitThreads : e->coop;
-    // Model selection: the fits of one component count depend on nothing but their own k-means start -- a stream per count (the
-    // class streams, idle between the passes), seed then EM, the largest count (the longest fits) first: the EM sweeps of one count
-    // (f64 arithmetic) run beside the k-means++ walks of another (waiting on loads).  TW_FIT_STREAMS=0: two launches over all counts.
-    static const int fit_streams = env_int("TW_FIT_STREAMS", 0);
-    if (fit_streams != 0 && kMaxComp <= kMaxEp) {
-        (void)hipEventRecord(e->cls_ev[0], e->stream);
-        for (int k = kMaxComp; k >= 1; k--) {
-            { int rs = ensure_class_stream(e, k); if (rs != TW_OK) return rs; }
-            FitDev Fk = F;
-            Fk.k_only = k;
-            hipStream_t st = e->cls_stream[k];
-            (void)hipStreamWaitEvent(st, e->cls_ev[0], 0);
-            if (k >= 2) hipLaunchKernelGGL(k_fit_seed<false>, dim3((unsigned)e->n_slots), dim3(threads), 0, st, Fk);
-            hipLaunchKernelGGL(k_fit_em<false>, dim3((unsigned)e->n_slots), dim3(threads), 0, st, Fk);
-            (void)hipEventRecord(e->cls_ev[k], st);
-            (void)hipStreamWaitEvent(e->stream, e->cls_ev[k], 0);
-        }
-    } else {
-        hipLaunchKernelGGL(k_fit_seed<false>, dim3((unsigned)(e->n_slots * (kMaxComp - 1))), dim3(threads), 0, e->stream, F);
-        hipLaunchKernelGGL(k_fit_em<false>, dim3((unsigned)(e->n_slots * kMaxComp)), dim3(threads), 0, e->stream, F);
-    }
+    const int threads = e->K.coop >= 64 ? kFitThreads : e->K.coop;
+    // Model selection: two launches over all counts, the largest count (the longest fits) first (fit_row)
+    hipLaunchKernelGGL(k_fit_seed<false>, dim3((unsigned)(e->n_slots * (kMaxComp - 1))), dim3(threads), 0, e->stream, F);
+    hipLaunchKernelGGL(k_fit_em<false>, dim3((unsigned)(e->n_slots * kMaxComp)), dim3(threads), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_select, dim3((unsigned)((e->n_slots + 63) / 64)), dim3(64), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_seed<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_em<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, e->stream, F);
@@ -2261,7 +2173,7 @@ int tw_evaluate(tw_engine* e, int64_t* per_unit, uint8_t* trace_flags, int64_t* 
     const int64_t nc = (int64_t)P.n_units * 4 + 2;
     HIPCHK(hipMemsetAsync(e->eval_counts, 0, sizeof(unsigned long long) * nc, e->stream));
     if (e->n_traces > 0) HIPCHK(hipMemsetAsync(e->trace_bad, 0, (size_t)(2 * e->n_traces), e->stream));
-    hipLaunchKernelGGL(k_evaluate, dim3(P.n_tiles), dim3(e->tile), 0, e->stream, P, (const int32_t*)e->truth,
+    hipLaunchKernelGGL(k_evaluate, dim3(P.n_tiles), dim3(e->K.tile), 0, e->stream, P, (const int32_t*)e->truth,
                        (const int32_t*)(e->n_traces > 0 ? e->in_trace : nullptr), e->eval_counts, e->trace_bad,
                        e->n_traces > 0 ? e->trace_bad + e->n_traces : nullptr);
     if (e->n_traces > 0 && e2e != nullptr)
@@ -2369,7 +2281,7 @@ int stitch_forest(tw_engine* e, const int32_t* src, int32_t* root_out, int32_t* 
     hipLaunchKernelGGL(k_stitch_init, rows, tb, 0, e->stream, S);
     int max_e = 1;
     for (const UnitDev& U : e->units) max_e = std::max(max_e, (int)U.E);
-    hipLaunchKernelGGL(k_stitch_links, dim3((unsigned)P.n_tiles, (unsigned)max_e), dim3((unsigned)e->tile), 0, e->stream, P, S, src);
+    hipLaunchKernelGGL(k_stitch_links, dim3((unsigned)P.n_tiles, (unsigned)max_e), dim3((unsigned)e->K.tile), 0, e->stream, P, S, src);
     HIPCHK(hipGetLastError());
     if (final) HIPCHK(hipEventRecord(e->stage_ev[SE_STITCH + 1], e->stream));
     unsigned long long *a = S.state_a, *b = S.state_b;
@@ -2584,7 +2496,7 @@ int conf_decisions(tw_engine* e) {
         }
     }
     HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 0], e->stream));
-    hipLaunchKernelGGL(k_conf_requests, dim3((unsigned)P.n_tiles), dim3((unsigned)e->tile), 0, e->stream, P, C);
+    hipLaunchKernelGGL(k_conf_requests, dim3((unsigned)P.n_tiles), dim3((unsigned)e->K.tile), 0, e->stream, P, C);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->stage_ev[SE_CONF + 1], e->stream));
     return TW_OK;
@@ -2884,7 +2796,7 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
             e->sig_ref_cap = n_rows;
             drop_ref(e);   // (new arrays: the set in the old ones is out of reach)
         }
-        D.mode = q->mode; D.hash_bits = e->sig_hash_bits; D.need_flags = q->need_flags; D.skip_flags = q->skip_flags;
+        D.mode = q->mode; D.hash_bits = e->K.sig_hash_bits; D.need_flags = q->need_flags; D.skip_flags = q->skip_flags;
         D.row_group = e->A.row_group;
         const unsigned threads = flat_threads(e);
         const dim3 tb(threads), trees(flat_grid(nt, threads)), rows(flat_grid(n_rows, threads));
@@ -3087,7 +2999,6 @@ int tw_measure_hbm_copy(tw_engine* e, int64_t bytes, int32_t iters, double* gbps
         if (s == hipSuccess) s = hipEventElapsedTime(&ms, e->ev[EV_BEGIN], e->ev[EV_END]);
         if (s == hipSuccess) {
             const double r = 2.0 * (double)(n16 * 16) * iters / ((double)ms * 1e-3) / 1e9;
-            if (env_int("TW_COPY_TRACE", 0)) fprintf(stderr, "tw_measure_hbm_copy: variant %d, %u workgroups: %.0f GB/s\n", variant, grid, r);
             if (r > *gbps) *gbps = r;
         }
     }
@@ -3141,7 +3052,7 @@ int tw_run_baseline(tw_engine* e, int kind, int32_t* parent_out) {
     if (kind == TW_BASELINE_VPATH && e->truth == nullptr) return fail(e, TW_ERR_STATE, "vPath follows a returning call to its request (vpath.py:42-46,81-84): tw_set_truth first");
     HIPCHK(hipSetDevice(e->device));
     const Dev& P = e->P;
-    const dim3 tiles(P.n_tiles), tb(e->tile);
+    const dim3 tiles(P.n_tiles), tb(e->K.tile);
     BaseScratch S;
     BaseDev B{};
     B.truth = e->truth;
@@ -3177,7 +3088,7 @@ int tw_wap5_delays(tw_engine* e, int64_t* delay_sum, int32_t* delay_cnt, int64_t
     if (rc != TW_OK) return rc;
     HIPCHK(hipSetDevice(e->device));
     const Dev& P = e->P;
-    const dim3 tiles(P.n_tiles), tb(e->tile);
+    const dim3 tiles(P.n_tiles), tb(e->K.tile);
     BaseScratch S;
     BaseDev B{};
     B.parent = (int32_t*)S.raw(e->n_ie, sizeof(int32_t), 0); B.count = (int32_t*)S.raw(e->n_ie, sizeof(int32_t), 0);
@@ -3202,7 +3113,7 @@ int tw_wap5_parents(tw_engine* e, const double* mean, int32_t* parent_out, int32
     if (rc != TW_OK) return rc;
     HIPCHK(hipSetDevice(e->device));
     const Dev& P = e->P;
-    const dim3 tiles(P.n_tiles), tb(e->tile);
+    const dim3 tiles(P.n_tiles), tb(e->K.tile);
     BaseScratch S;
     BaseDev B{};
     B.parent = (int32_t*)S.raw(e->n_ie, sizeof(int32_t), 0xff); B.count = (int32_t*)S.raw(e->n_ie, sizeof(int32_t), 0);
@@ -3242,7 +3153,7 @@ int tw_debug_worklists(tw_engine* e, int32_t* out) {
     out[0] = 0;
     for (int k = 0; k < 4 * kSelSeg; k++) out[0] += sel_all[k * kCtrStride];
     for (int k = 0; k <= kMaxEp; k++) out[1 + k] = both[k] + both[kMaxEp + 1 + k];
-    if (e->debug_lists != 0)   // (the first enumeration's lists, as its chain left them: narrow + wide + long enumerations)
+    if (e->K.debug_lists != 0)   // (the first enumeration's lists, as its chain left them: narrow + wide + long enumerations)
         for (int k = 1; k <= kMaxEp; k++) out[1 + k] = e->first_lists[0][k] + e->first_lists[1][k] + e->first_lists[2][k];
     int32_t split[kMaxEp + 1];   // [0] spans listed again after the merge, [E >= 2] split spans of the class
     HIPCHK(hipMemcpy(split, e->P.split_count, sizeof(split), hipMemcpyDeviceToHost));

@@ -63,6 +63,7 @@ __device__ __forceinline__ void group_sync() {  // workgroup barrier of kernels 
     if (blockDim.x <= 64) wave_sync(); else __syncthreads();
 }
 constexpr int kWorkChunk = 4;  // work-list entries a wavefront claims per atomic
+constexpr int kHeavyGrid = 4096;   // most persistent wavefronts of k_enumerate_heavy per launch
 
 __device__ __forceinline__ int lower_bound_i64(const int64_t* a, int n, int64_t t) {  // first a[x] >= t
     int lo = 0, hi = n;
@@ -835,23 +836,11 @@ __device__ __forceinline__ int32_t* enum_cursor(const Dev& P, int part, bool wid
     return P.heavy_in_next + ((kind * 2 + (wide ? 1 : 0)) * (kMaxEp + 1) + E);
 }
 
-// What the tile kernel of class E has listed when the launch before this one has ended: the end of stretch `j - 1` of the class' lists
-// (stretch 0 starts at 0: the snapshots are zeroed with the counter block of the pass)
-__global__ void k_enum_snapshot(Dev P, int E, int j) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int32_t* snap = P.enum_snap + (E * (kEnumStretches + 1) + j) * 4;
-    snap[0] = P.heavy_big_count[E]; snap[1] = P.heavy_in_count[E]; snap[2] = P.heavy_in_count[kMaxEp + 1 + E];
-}
-
 template <int E, int W>
-__global__ void __launch_bounds__(kHeavyThreads) TW_HEAVY_ATTR k_enumerate_heavy(Dev P, int pass, int mode, int part_arg, int pool) {
+__global__ void __launch_bounds__(kHeavyThreads) TW_HEAVY_ATTR k_enumerate_heavy(Dev P, int pass, int mode, int part, int pool) {
     // part: 0 = the class' lists, the long enumerations first (one launch serves both); 1 = only the long ones (the split spans
     // that k_merge_parts lists again); 2 = only the others.  `pool` = doubles of dynamic LDS for the pair-term tables.
-    // part_arg = part | (stretch + 1) << 8: a launch of part 0 that serves one stretch of the class' lists -- the entries the tile
-    // kernel appended between two snapshots of the list counters (k_enum_snapshot; launch_enumerate runs such launches beside the
-    // tile kernel of the class' following tiles instead of behind the last one)
     if (*P.err != 0) return;  // an earlier kernel of this pass reported an error: its outputs are not usable
-    const int part = part_arg & 255, stretch = (part_arg >> 8) - 1;
     static_assert(W == kNarrow || W == 64 * kCandWords, "one instantiation per half of the work list");
     constexpr bool kWide = W != kNarrow;
     constexpr int kList = kWide ? kMaxEp + 1 + E : E;
@@ -872,14 +861,10 @@ __global__ void __launch_bounds__(kHeavyThreads) TW_HEAVY_ATTR k_enumerate_heavy
     const int t = threadIdx.x, nt = blockDim.x;
     // part 3: the list parts of the deferred spans (see kListSplitFlag), appended behind the class' listed entries by the launch before
     // part 4: what k_enumerate_lean left to this kernel (P.fb_*: entries in the format of the list of long enumerations)
-    const int32_t* snap = stretch >= 0 ? P.enum_snap + (E * (kEnumStretches + 1) + stretch) * 4 : nullptr;   // [0] long enumerations, [1] narrow, [2] wide entries listed so far
-    const int big_lo = stretch >= 0 ? snap[0] : 0, in_lo = stretch >= 0 ? snap[kWide ? 2 : 1] : 0;
-    const int defer_base = part == 3 ? P.heavy_big_count[E] : big_lo;
-    const int n_big = stretch >= 0 ? snap[4] - big_lo
-                                   : (part == 2 ? 0 : (part == 3 ? P.defer_count[E] : (part == 1 ? P.redo_count[E] : (part == 4 ? P.fb_count[E] : P.heavy_big_count[E]))));   // (both instantiations walk the list of long enumerations; each takes its own)
-    const int count = n_big + (stretch >= 0 ? snap[4 + (kWide ? 2 : 1)] - in_lo : ((part == 0 || part == 2) ? P.heavy_in_count[kList] : 0));
-    int32_t* next_counter = stretch >= 0 ? P.enum_stretch_next + (E * kEnumStretches + stretch) * 2 + (kWide ? 1 : 0)
-                                         : enum_cursor(P, part, kWide, E);   // (a cursor per kind of launch: nothing to reset between the launches of a class)
+    const int defer_base = part == 3 ? P.heavy_big_count[E] : 0;
+    const int n_big = part == 2 ? 0 : (part == 3 ? P.defer_count[E] : (part == 1 ? P.redo_count[E] : (part == 4 ? P.fb_count[E] : P.heavy_big_count[E])));   // (both instantiations walk the list of long enumerations; each takes its own)
+    const int count = n_big + ((part == 0 || part == 2) ? P.heavy_in_count[kList] : 0);
+    int32_t* next_counter = enum_cursor(P, part, kWide, E);   // (a cursor per kind of launch: nothing to reset between the launches of a class)
     const int32_t *big_unit = part == 4 ? P.fb_unit : P.heavy_big_unit, *big_idx = part == 4 ? P.fb_idx : P.heavy_big_idx;
     const int32_t *big_part = part == 4 ? P.fb_part : P.heavy_big_part, *big_slot_of = part == 4 ? P.fb_slot : P.heavy_big_slot;
     const int nstatic = (int)gridDim.x * kWorkChunk;
@@ -909,7 +894,7 @@ __global__ void __launch_bounds__(kHeavyThreads) TW_HEAVY_ATTR k_enumerate_heavy
         // wave-uniform by construction; telling the compiler so turns every access to the unit descriptor below
         // into a scalar load (SGPRs, constant cache) instead of 64 lanes loading the same address
         const bool from_big = item < n_big;
-        const int pos = from_big ? P.heavy_big_off[E] + defer_base + item : (kWide ? P.heavy_in_off[E + 1] - 1 - (in_lo + item - n_big) : P.heavy_in_off[E] + in_lo + (item - n_big));
+        const int pos = from_big ? P.heavy_big_off[E] + defer_base + item : (kWide ? P.heavy_in_off[E + 1] - 1 - (item - n_big) : P.heavy_in_off[E] + (item - n_big));
         const int unit = __builtin_amdgcn_readfirstlane((from_big ? big_unit : P.heavy_in_unit)[pos]);
         const int i_raw = __builtin_amdgcn_readfirstlane((from_big ? big_idx : P.heavy_in_idx)[pos]);
         const int i = i_raw & ~kIdxReplayFlag;

@@ -253,7 +253,8 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * (tw_get_decisions alone writes ms[19]).
  * The last tw_latency_distributions (HIP events): ms[22] cohorts + the two sweeps over the rows (counts, items; incl. the host's
  * read of the item count), ms[23] sort, offsets and values, ms[24] quantiles and histogram (22 and 23: of the call that built
- * the items).  ms[25..30]: tw_trace_signatures and tw_class_profiles (see there).  ms[31]: the kernel of the last tw_order_bound. */
+ * the items).  ms[25..30]: tw_trace_signatures and tw_class_profiles (see there).  ms[31]: the kernel of the last tw_order_bound.
+ * ms[32] (a count): class stages of the last pass that were queued behind the stage gate (TW_STAGE_GATE), 0 = the pass was not gated. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------

@@ -68,6 +68,7 @@ struct Knobs {
     int64_t part_slots_max;   // TW_PART_SLOTS_MAX: most scratch slots of the split enumerations, whatever the batch (tw_load_batch)
     int part_budget_deep;     // TW_PART_BUDGET_DEEP: extra work-list entries per span of the classes of five and more endpoints (part_extra)
     int fit_sort;             // TW_FIT_SORT=1: the gap rows go the sort route (fit_prepare)
+    int stage_gate;           // TW_STAGE_GATE: the stages of the shorter classes wait for the critical class' tile kernel (launch_class_stage; 0 = they do not: A/B runs, bisection)
 };
 
 Knobs read_knobs() {
@@ -96,6 +97,7 @@ Knobs read_knobs() {
     K.part_slots_max = (int64_t)std::max(env_int("TW_PART_SLOTS_MAX", 16 << 20), 1024);
     K.part_budget_deep = env_int("TW_PART_BUDGET_DEEP", 2);
     K.fit_sort = env_int("TW_FIT_SORT", 0);
+    K.stage_gate = env_int("TW_STAGE_GATE", 1);
     return K;
 }
 
@@ -140,6 +142,10 @@ struct tw_engine {
     // the window / selection stage of a class follows its enumeration on the class' stream (run_pass): the three instantiations of
     // k_select_heavy on streams of their own beside it, forked from and joined to the class' stream
     hipStream_t sel_stream[3] = {};
+    // the stage gate (launch_enumerate_all, launch_class_stage): the critical class of the pass being queued (0 = none), the event
+    // behind its k_enumerate_tile, and how many stages of the last pass were queued behind that event (tw_get_timing slot 32)
+    int gate_cls = 0, gate_waits = 0;
+    hipEvent_t tile_done = nullptr;
     hipEvent_t prep_ev = nullptr;              // the per-pass fills the selection stage needs (main stream, beside the enumerations)
     hipEvent_t post_fork[kMaxEp + 1] = {}, post_join[kMaxEp + 1][3] = {}, post_done[kMaxEp + 1] = {};
     Knobs K{};                                 // the TW_* variables as tw_create found them (read_knobs)
@@ -573,6 +579,7 @@ void launch_enumerate(tw_engine* e, int pass, int mode, const int32_t* listed) {
         };
         if (sub_tile) tile_path(std::integral_constant<int, kSubTileSpans>{});
         else tile_path(std::integral_constant<int, kTile>{});
+        if (E == e->gate_cls) (void)hipEventRecord(e->tile_done, st);   // (who waits for it: launch_class_stage of the other classes, queued after every class' chain)
     }
     // the wavefront kernels of the class: the spans the tile kernel handed over (mode 1: the spans k_detect_gone listed), the long
     // enumerations first; the list parts of the spans those launches deferred (kListSplitFlag); the parts combined, the few spans whose
@@ -694,15 +701,21 @@ void launch_select_hard(tw_engine* e, const TileSet& S, hipStream_t st, bool few
 // round of the span consumption (claim, detect) and -- in anticipation of that round finding nothing to repair, the usual case --
 // the parents and gap samples of its units (run_pass runs both again over all tiles when a repair round changed something).  Units
 // of different classes are independent (traceweaver_v3.py:1182-1193 runs per service): nothing here waits for another class.
-int launch_class_stage(tw_engine* e, int pass, int E) {
+// The stage gate.  e->gate_cls (0 = no gate) is the class whose chain is the pass and whose tile kernel takes the general path of
+// k_enumerate_tile (launch_enumerate_all).  That kernel fills every CU's LDS, four workgroups of 39 KB, and is bound by instruction
+// issue: what runs beside it makes the pass longer, while behind it the machine runs that class' wavefront kernels and a stage of few
+// wavefronts with room to spare.  The other classes therefore hold the persistent, LDS-sized part of their stage -- the listed and the
+// hard windows, claim, detect -- until that tile kernel has ended; windows and k_select_fast, plain throughput kernels, run at once.
+// (The wait is on an event of the critical class' stream that was recorded when the chains were queued: before this wait in
+// submission order, so streams that share a hardware queue cannot wait on one another.)
+int launch_class_stage(tw_engine* e, int pass, int E, int deepest) {
     const TileSet S = class_tiles(e, E);
     if (S.n == 0) return TW_OK;
     hipStream_t st = e->cls_stream[E];
     (void)hipStreamWaitEvent(st, e->prep_ev, 0);
     if (pass == 1) { int rc = launch_windows(e, S, st); if (rc != TW_OK) return rc; }
     hipLaunchKernelGGL(k_select_fast, dim3(S.n), dim3(e->K.tile), 0, st, e->P, S);
-    int deepest = 0;
-    for (int c = 1; c <= kMaxEp; c++) if (e->tile_cls_off[c + 1] > e->tile_cls_off[c]) deepest = c;
+    if (e->gate_cls > 0 && E != e->gate_cls) { (void)hipStreamWaitEvent(st, e->tile_done, 0); e->gate_waits++; }
     const int64_t n_cls = (int64_t)e->P.heavy_in_off[E + 1] - e->P.heavy_in_off[E];
     launch_select_listed(e, S, st, n_cls, E == deepest);
     launch_select_hard(e, S, st, pass == 2 && e->hard_pass1[E] == 0);
@@ -719,20 +732,31 @@ template <class Prep>
 int launch_enumerate_all(tw_engine* e, int pass, int mode, const int32_t* listed, bool staged, Prep prep) {
     // (the work-list cursors were reset with the counter block of the pass / the repair round)
     (void)hipEventRecord(e->cls_ev[0], e->stream);
+    auto has = [&](int E) { return e->tile_cls_off[E + 1] > e->tile_cls_off[E]; };
+    auto is_lean = [&](int E) { return E >= e->P.lean_min_e && !e->skip_mode; };
+    int deepest = 0;
+    for (int E = 1; E <= kMaxEp; E++) if (has(E)) deepest = E;
+    // The stage gate's critical class: the deepest class of a staged batch (media shape: four endpoints), where the general path of the
+    // tile kernel serves it.  Not where k_enumerate_lean does (Alibaba shape: the pass is as long as the deep classes' chains, whenever
+    // the shallower tile kernels end), and not where the tile kernel takes one of its lean paths (nodejs shape: the pair path; the
+    // single-endpoint services' stages are the longer part of the pass there and the gate serialises them -- profiles/HISTORY.md, round
+    // 12).  Measured on those three shapes only: a deepest class of three endpoints, or of one or two with TW_TILE_SINGLE / TW_TILE_PAIR
+    // = 0, is gated by the same reasoning, without a measurement of its own.
+    e->gate_cls = 0;
+    if (staged && e->K.stage_gate != 0 && !is_lean(deepest) && !(deepest == 1 && e->K.tile_single != 0) && !(deepest == 2 && e->K.tile_pair != 0)) e->gate_cls = deepest;
+    if (mode == 0) e->gate_waits = 0;
     // the classes with the most endpoints first: their enumerations are the longest and end the group (each class runs on a
     // stream of its own; what is launched first is dispatched first)
     launch_enumerate<8>(e, pass, mode, listed); launch_enumerate<7>(e, pass, mode, listed); launch_enumerate<6>(e, pass, mode, listed); launch_enumerate<5>(e, pass, mode, listed);
     launch_enumerate<4>(e, pass, mode, listed); launch_enumerate<3>(e, pass, mode, listed); launch_enumerate<2>(e, pass, mode, listed); launch_enumerate<1>(e, pass, mode, listed);
     { int rc = prep(); if (rc != TW_OK) return rc; }   // (fills on the engine's stream, beside the enumerations)
-    auto has = [&](int E) { return e->tile_cls_off[E + 1] > e->tile_cls_off[E]; };
-    auto is_lean = [&](int E) { return E >= e->P.lean_min_e && !e->skip_mode; };
     bool any_lean = false;
     for (int E = 1; E <= kMaxEp; E++) any_lean |= has(E) && is_lean(E);
     // the classes that are complete with their chain go on at once -- those expected to end first first (the selection streams serve
     // the classes in this order): the fewest endpoints
     if (staged)
         for (int E = 1; E <= kMaxEp; E++)
-            if (has(E) && !is_lean(E)) { int rc = launch_class_stage(e, pass, E); if (rc != TW_OK) return rc; }
+            if (has(E) && !is_lean(E)) { int rc = launch_class_stage(e, pass, E, deepest); if (rc != TW_OK) return rc; }
     if (any_lean) {
         // what k_enumerate_lean handed on: the host reads the counts when the lean classes' chains have ended
         int32_t fb[kMaxEp + 1] = {};
@@ -748,7 +772,7 @@ int launch_enumerate_all(tw_engine* e, int pass, int mode, const int32_t* listed
         launch_fallback<4>(e, pass, mode, fb); launch_fallback<3>(e, pass, mode, fb); launch_fallback<2>(e, pass, mode, fb); launch_fallback<1>(e, pass, mode, fb);
         if (staged)
             for (int E = 1; E <= kMaxEp; E++)
-                if (has(E) && is_lean(E)) { int rc = launch_class_stage(e, pass, E); if (rc != TW_OK) return rc; }
+                if (has(E) && is_lean(E)) { int rc = launch_class_stage(e, pass, E, deepest); if (rc != TW_OK) return rc; }   // (a batch with lean classes has no gate)
     }
     for (int E = 1; E <= kMaxEp; E++)
         if (has(E)) (void)hipStreamWaitEvent(e->stream, e->cls_ev[E], 0);
@@ -1111,6 +1135,7 @@ int tw_create(int device_id, tw_engine** out) {
     // classes owns seven streams, not twelve)
     for (int i = 0; i <= kMaxEp + 1 && s == hipSuccess; i++) s = hipEventCreateWithFlags(&e->cls_ev[i], hipEventDisableTiming);
     if (s == hipSuccess) s = hipEventCreateWithFlags(&e->prep_ev, hipEventDisableTiming);
+    if (s == hipSuccess) s = hipEventCreateWithFlags(&e->tile_done, hipEventDisableTiming);
     for (int i = 0; i <= kMaxEp && s == hipSuccess; i++) {
         s = hipEventCreateWithFlags(&e->post_fork[i], hipEventDisableTiming);
         if (s == hipSuccess) s = hipEventCreateWithFlags(&e->post_done[i], hipEventDisableTiming);
@@ -1140,6 +1165,7 @@ void tw_destroy(tw_engine* e) {
     for (int i = 0; i < 3; i++)
         if (e->sel_stream[i]) (void)hipStreamDestroy(e->sel_stream[i]);
     if (e->prep_ev) (void)hipEventDestroy(e->prep_ev);
+    if (e->tile_done) (void)hipEventDestroy(e->tile_done);
     for (int i = 0; i <= kMaxEp; i++) {
         if (e->post_fork[i]) (void)hipEventDestroy(e->post_fork[i]);
         if (e->post_done[i]) (void)hipEventDestroy(e->post_done[i]);
@@ -1855,6 +1881,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 3 && 25 + i < n; i++) ms[25 + i] = e->sg_ms[i];   // the last tw_trace_signatures that ran kernels
     for (int i = 0; i < 3 && 28 + i < n; i++) ms[28 + i] = e->pf_ms[i];   // the last tw_class_profiles that ran kernels
     if (n > 31) ms[31] = e->ob_ms;                                        // the last tw_order_bound
+    if (n > 32) ms[32] = (double)e->gate_waits;                           // class stages of the last pass that were queued behind the stage gate
     return TW_OK;
 }
 

@@ -808,3 +808,10 @@ class Engine(object):
         ms = np.zeros(10, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 10))
         return dict(zip(("pass", "enumerate", "select", "windows", "repair", "params", "fit", "rounds", "host_enum_submit", "host_pass"), ms.tolist()))
+
+    def gated_stages(self):
+        """Class stages of the last pass that were queued behind the stage gate (tw_get_timing slot 32): 0 = the pass was not gated --
+        TW_STAGE_GATE=0, a batch that is not staged, or a deepest class that the general path of the tile kernel does not serve."""
+        ms = np.zeros(33, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 33))
+        return int(ms[32])

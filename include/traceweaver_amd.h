@@ -254,7 +254,8 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * The last tw_latency_distributions (HIP events): ms[22] cohorts + the two sweeps over the rows (counts, items; incl. the host's
  * read of the item count), ms[23] sort, offsets and values, ms[24] quantiles and histogram (22 and 23: of the call that built
  * the items).  ms[25..30]: tw_trace_signatures and tw_class_profiles (see there).  ms[31]: the kernel of the last tw_order_bound.
- * ms[32] (a count): class stages of the last pass that were queued behind the stage gate (TW_STAGE_GATE), 0 = the pass was not gated. */
+ * ms[32] (a count): class stages of the last pass that were queued behind the stage gate (TW_STAGE_GATE), 0 = the pass was not gated.
+ * The last tw_compare_cohorts (HIP events): ms[33] ranks, pool and observed statistics, ms[34] the permutation walk (0 without one). */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -577,6 +578,64 @@ typedef struct {
 } tw_distributions;
 int tw_set_row_cohorts(tw_engine *e, int32_t n_cohorts, const int32_t *row_cohort);
 int tw_latency_distributions(tw_engine *e, const tw_dist_query *q, const tw_distributions *out, int64_t *summary4);
+
+/* ---- two cohorts compared: KS, rank sum, quantile shifts, permutation test (csrc/tw_cmp.h) --------------------------
+ *
+ * Replaces: the reading of the two latency lists the delay-culprit query writes (src/query_engine/delay_culprit.py:80-97),
+ * for the case the cohorts exist for: requests served by version a against those served by version b of one service.  It
+ * answers "is b slower than a, where, and could that be noise" on the device, from what tw_latency_distributions works on:
+ * the last attribution, the cohort labels as they are and the sorted items (built here if they are not resident).  The call
+ * drops nothing and keeps no result: tw_latency_distributions answers after it what it answered before.
+ *
+ * Definitions (integers throughout; latencies are assumed below 2^62 in magnitude):
+ *   rows       pairs [n_pairs][2] = (a, b), a != b, both in [0, n_cohorts), 1 <= n_pairs <= 64.  Row pair * (3 G + 1) + r, r =
+ *              m * G + g the (metric, group) position inside a cohort (the trace latency last), compares A = the sorted values
+ *              of segment (a, r) with B = those of (b, r); n_a, n_b their sizes, N = n_a + n_b, M the N pooled values ascending
+ *              (only values matter: M is fully determined).
+ *   observed   Where either side is empty: ks_gap = u2 = 0, ks_at = INT64_MIN, every shift 0, every perm_* -1.  Else
+ *              ks_gap, ks_at   over the distinct x of M, g(x) = #{A <= x} n_b - #{B <= x} n_a; ks_gap = g at the smallest x
+ *                              where |g| is greatest (signed: positive = A's CDF lies above B's there), ks_at that x.  The
+ *                              two-sample KS statistic is |ks_gap| / (n_a n_b).
+ *              u2              2 #{(i, j): A_i < B_j} + #{(i, j): A_i = B_j}: twice the Mann-Whitney U of B over A;
+ *                              u2 / (2 n_a n_b) is the probability that a value of B exceeds one of A (ties count half).
+ *              quantile_shift  [n_q], n_q <= 8: Q_B(p_j) - Q_A(p_j), Q(p) the value at index min(n - 1, (int64)(p * (double)n))
+ *                              (the index of tw_latency_distributions: one binary64 product, -ffp-contract=off).
+ *   permuted   n_perm <= 65536 permutations p of every row with both sides non-empty and (max_pool = 0 or N <= max_pool).
+ *              Permutation p hands n_a of the N pooled values to A' by selection sampling along M: with c = items given so
+ *              far, item k goes to A' iff (h_k * (N - k)) >> 64 < n_a - c (a 128-bit product), h_k = mix(key + GOLD * (k + 1)),
+ *              key = mix(mix(seed + GOLD * (row + 1)) + GOLD * (p + 1)), GOLD = 0x9E3779B97F4A7C15, mix = the finaliser of
+ *              splitmix64 (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31), all
+ *              mod 2^64.  Its statistics are the ones above on (A', B'): the gap at the end of every run of equal values, u2
+ *              per run as rb * (2 * cA_before_run + ra).  perm_ge_ks = #{p: |gap_p| >= |ks_gap|}, perm_ge_u = #{p: |u2_p - n_a
+ *              n_b| >= |u2 - n_a n_b|}, perm_ge_q [n_q] = #{p: |shift_p,j| >= |quantile_shift_j|} (magnitudes as unsigned 64
+ *              bit).  A p-value is (1 + ge) / (1 + n_perm), left to the caller.  Rows not permuted hold -1 in all three; with
+ *              n_perm = 0 the three arrays are not written.  The draws of different rows are independent.
+ *   outputs    caller-allocated, any may be NULL; [n_rows = n_pairs * (3 G + 1)], quantile_shift and perm_ge_q [n_rows][n_q].
+ *   summary4   rows with both sides non-empty, rows permuted, pooled items permuted (the sum of N over those rows), n_perm
+ *
+ * TW_ERR_STATE before a tw_attribute_traces on the current forest.  TW_ERR_ARG: n_pairs outside [1, 64], a label outside
+ * [0, n_cohorts) (so every pair while there is one cohort), a = b, n_q outside [0, 8], a prob that is NaN or outside [0, 1],
+ * n_perm outside [0, 65536], max_pool < 0.  TW_ERR_UNSUPPORTED: some n_a n_b >= 2^61 or N >= 2^32 (and n_seg > 2^24, as above).
+ * All refused on the host.  The atomics are integer adds, maxima and minima of which only the result is read: results do not
+ * depend on scheduling.  Limits: one engine's batch; cohort against cohort (predicted against true are two resident states:
+ * traces.compare_distributions on the host); the walk of one permutation is sequential in N, so the largest row bounds the
+ * call and max_pool is the handle on that.  Timing: tw_get_timing slots 33, 34 (observed statistics; permutation walk). */
+#define TW_CMP_MAX_Q 8
+typedef struct {
+    int32_t n_pairs;
+    const int32_t *pairs;
+    int32_t n_q;
+    const double *probs;
+    int32_t n_perm;
+    uint64_t seed;
+    int64_t max_pool;
+} tw_cmp_query;
+typedef struct {
+    int64_t *n_a, *n_b, *ks_gap, *ks_at, *u2;
+    int64_t *quantile_shift;
+    int64_t *perm_ge_ks, *perm_ge_u, *perm_ge_q;
+} tw_cohort_comparison;
+int tw_compare_cohorts(tw_engine *e, const tw_cmp_query *q, const tw_cohort_comparison *out, int64_t *summary4);
 
 /* ---- traces grouped by call-graph signature (csrc/tw_sig.h) -------------------------------------------------------
  *

@@ -97,6 +97,16 @@ class Distributions(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("tree_cohort", "seg_count", "seg_sum", "seg_off", "values", "quantile", "hist")]
 
 
+class CmpQuery(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_int32), ("pairs", ctypes.c_void_p), ("n_q", ctypes.c_int32), ("probs", ctypes.c_void_p),
+                ("n_perm", ctypes.c_int32), ("seed", ctypes.c_uint64), ("max_pool", ctypes.c_int64)]
+
+
+class CohortComparison(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "n_a", "n_b", "ks_gap", "ks_at", "u2", "quantile_shift", "perm_ge_ks", "perm_ge_u", "perm_ge_q")]
+
+
 class SigQuery(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int32), ("need_flags", ctypes.c_uint32), ("skip_flags", ctypes.c_uint32),
                 ("keep_reference", ctypes.c_int32), ("compare", ctypes.c_int32)]
@@ -118,12 +128,14 @@ TW_TREE_CONFIDENT = 8
 TW_CONF_MAX_EDGES = 15
 TW_DIST_MAX_Q = 32
 TW_DIST_MAX_EDGES = 63
+TW_CMP_MAX_Q = 8
+TW_CMP_MAX_PAIRS = 64
 
 EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_pass1", "tw_get_gaps", "tw_set_gaps",
            "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
            "tw_assign_service", "tw_find_order", "tw_order_bound", "tw_order_stage", "tw_order_load", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
-           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_trace_signatures", "tw_class_profiles",
+           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
            "tw_corpus_string", "tw_corpus_loop_origin", "tw_corpus_trace_names", "tw_corpus_span_table", "tw_corpus_build_units"]
 
@@ -187,6 +199,7 @@ def load(path=None):
     lib.tw_score_traces.argtypes = [vp, ctypes.POINTER(ConfQuery), ctypes.POINTER(Confidence), vp]
     lib.tw_set_row_cohorts.argtypes = [vp, ctypes.c_int32, vp]
     lib.tw_latency_distributions.argtypes = [vp, ctypes.POINTER(DistQuery), ctypes.POINTER(Distributions), vp]
+    lib.tw_compare_cohorts.argtypes = [vp, ctypes.POINTER(CmpQuery), ctypes.POINTER(CohortComparison), vp]
     lib.tw_trace_signatures.argtypes = [vp, ctypes.POINTER(SigQuery), ctypes.POINTER(Signatures), vp]
     lib.tw_class_profiles.argtypes = [vp, ctypes.POINTER(ClassProfile), vp]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]

@@ -26,6 +26,7 @@
 #include "tw_attr.h"
 #include "tw_conf.h"
 #include "tw_dist.h"
+#include "tw_cmp.h"
 #include "tw_sig.h"
 #include "tw_prof.h"
 #include "tw_order.h"
@@ -37,7 +38,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_COUNT = 26 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_COUNT = 29 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -242,6 +243,8 @@ struct tw_engine {
     bool cohorts_set = false, dist_ready = false;   // last attribution and the current labels are resident, a further call only gathers
     int64_t cohort_rows_cap = 0, dist_trees_cap = 0, dist_seg_cap = 0, dist_out_cap = 0 /* segments */, dist_items = 0;
     DistKeyDev dist_key{};
+    CmpDev M{};                             // tw_compare_cohorts (tw_cmp.h): scratch of a call (the pool, the per-row results); nothing of it
+    int64_t cmp_rows_cap = 0, cmp_items_cap = 0;    // outlives the call but the buffers
     SigDev G{};                             // tw_trace_signatures (tw_sig.h); sig_ready: the result of sig_q on the forest is resident, a further
     bool sig_ready = false, ref_set = false;        // call with the same query only copies; ref_set: the reference set, keyed by root row
     tw_sig_query sig_q{};
@@ -258,6 +261,7 @@ struct tw_engine {
     double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
+    double cm_ms[2] = {0, 0};               // ranks, pool and observed statistics; the permutation walk
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
     // tw_order_stage / tw_order_load (tw_order.h): the span table of a batch in partition-key order, staged once, and the buffers a
     // candidate's permuted copy is gathered into before tw_load_batch takes it device to device.  Owned by the engine, not by a
@@ -399,6 +403,7 @@ void drop_buffers(tw_engine* e) {
     e->D = DistDev{}; e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;   // cohort labels, items
     e->G = SigDev{}; e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;   // signatures, reference set
     e->F = ProfDev{}; e->prof_ent_cap = 0; e->prof_cls_cap = 0; e->prof_rows_cap = 0;                  // class profile
+    e->M = CmpDev{}; e->cmp_rows_cap = 0; e->cmp_items_cap = 0;                                        // scratch of the cohort comparison
 }
 
 bool pass_resident(const tw_engine* e, int pass) {
@@ -1882,6 +1887,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 3 && 28 + i < n; i++) ms[28 + i] = e->pf_ms[i];   // the last tw_class_profiles that ran kernels
     if (n > 31) ms[31] = e->ob_ms;                                        // the last tw_order_bound
     if (n > 32) ms[32] = (double)e->gate_waits;                           // class stages of the last pass that were queued behind the stage gate
+    for (int i = 0; i < 2 && 33 + i < n; i++) ms[33 + i] = e->cm_ms[i];   // the last tw_compare_cohorts
     return TW_OK;
 }
 
@@ -2784,6 +2790,112 @@ int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_dist
     if (summary != nullptr) {
         summary[0] = n_items; summary[1] = (int64_t)counters[5]; summary[2] = (int64_t)counters[3]; summary[3] = (int64_t)counters[4];
     }
+    return TW_OK;
+}
+
+/* ---- two cohorts compared: KS, rank sum, quantile shifts, permutation test (tw_cmp.h) -------------------------------- */
+int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comparison* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (!e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_compare_cohorts needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
+                                     "whatever drops the forest drop the attribution)");
+    if (q->n_pairs < 1 || q->n_pairs > kCmpMaxPairs || q->pairs == nullptr) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_pairs outside [1, 64]");
+    const int32_t n_cohorts = e->cohorts_set ? e->D.n_cohorts : 1;
+    for (int i = 0; i < q->n_pairs; i++) {
+        const int32_t a = q->pairs[2 * i], b = q->pairs[2 * i + 1];
+        if (a < 0 || a >= n_cohorts || b < 0 || b >= n_cohorts) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a pair names a cohort outside [0, n_cohorts)");
+        if (a == b) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a pair compares a cohort with itself");
+    }
+    if (q->n_q < 0 || q->n_q > kCmpMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_q outside [0, 8]");
+    for (int j = 0; j < q->n_q; j++)
+        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a prob outside [0, 1]");
+    if (q->n_perm < 0 || q->n_perm > kCmpMaxPerm) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_perm outside [0, 65536]");
+    if (q->max_pool < 0) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: max_pool below 0");
+    const int64_t per = 3 * (int64_t)e->A.n_groups + 1, n_seg = (int64_t)n_cohorts * per;
+    if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->dist_ready) TWCHK(dist_build(e));
+    const DistDev& D = e->D;
+    // the sizes of the rows: limits, pool offsets and the summary on the host
+    std::vector<unsigned long long> count((size_t)n_seg);
+    HIPCHK(hipMemcpyAsync(count.data(), D.seg_count, sizeof(unsigned long long) * (size_t)n_seg, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t n_rows = (int64_t)q->n_pairs * per;
+    std::vector<int64_t> row_off((size_t)n_rows + 1, 0);
+    int64_t both = 0, permuted = 0, permuted_items = 0;
+    for (int64_t row = 0; row < n_rows; row++) {
+        const int64_t pi = row / per, r = row - pi * per;
+        const unsigned long long na = count[(size_t)(q->pairs[2 * pi] * per + r)], nb = count[(size_t)(q->pairs[2 * pi + 1] * per + r)];
+        int64_t n = 0;
+        if (na > 0 && nb > 0) {
+            if (na + nb >= (1ull << 32)) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: a row pools 2^32 values or more");
+            if (na * nb >= (1ull << 61)) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: n_a * n_b of a row is 2^61 or more");
+            n = (int64_t)(na + nb);
+            both++;
+            if (q->n_perm > 0 && (q->max_pool == 0 || n <= q->max_pool)) { permuted++; permuted_items += n; }
+        }
+        row_off[(size_t)row + 1] = row_off[(size_t)row] + n;
+    }
+    const int64_t n_items = row_off[(size_t)n_rows];
+    CmpDev& M = e->M;
+    if (M.pairs == nullptr) { int32_t* pairs_d; DEV_ALLOC(pairs_d, 2 * kCmpMaxPairs); M.pairs = pairs_d; }   // (all of them freed with the batch)
+    if (M.row_off == nullptr || n_rows > e->cmp_rows_cap) {
+        int64_t* off_d;
+        DEV_ALLOC(off_d, n_rows + 1);
+        M.row_off = off_d;
+        DEV_ALLOC(M.ks_abs, n_rows); DEV_ALLOC(M.ks_pos, n_rows); DEV_ALLOC(M.u2_acc, n_rows);
+        DEV_ALLOC(M.n_a, n_rows); DEV_ALLOC(M.n_b, n_rows); DEV_ALLOC(M.ks_gap, n_rows); DEV_ALLOC(M.ks_at, n_rows); DEV_ALLOC(M.u2, n_rows);
+        DEV_ALLOC(M.ge_ks, n_rows); DEV_ALLOC(M.ge_u, n_rows);
+        DEV_ALLOC(M.shift, n_rows * kCmpMaxQ); DEV_ALLOC(M.ge_q, n_rows * kCmpMaxQ);
+        e->cmp_rows_cap = n_rows;
+    }
+    if (M.pool == nullptr || n_items > e->cmp_items_cap) {
+        DEV_ALLOC(M.pool, n_items); DEV_ALLOC(M.gabs, n_items);
+        e->cmp_items_cap = std::max<int64_t>(n_items, 1);
+    }
+    M.n_pairs = q->n_pairs; M.n_q = q->n_q; M.n_perm = q->n_perm;
+    M.per = per; M.n_rows = n_rows; M.n_items = n_items;
+    M.max_pool = q->max_pool; M.seed = q->seed;
+    for (int j = 0; j < kCmpMaxQ; j++) M.probs[j] = j < q->n_q ? q->probs[j] : 0.0;
+    HIPCHK(hipMemcpyAsync(const_cast<int32_t*>(M.pairs), q->pairs, sizeof(int32_t) * 2 * (size_t)q->n_pairs, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(M.row_off), row_off.data(), sizeof(int64_t) * ((size_t)n_rows + 1), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(M.ks_abs, 0, sizeof(unsigned long long) * (size_t)n_rows, e->stream));
+    HIPCHK(hipMemsetAsync(M.u2_acc, 0, sizeof(unsigned long long) * (size_t)n_rows, e->stream));
+    HIPCHK(hipMemsetAsync(M.ks_pos, 0xFF, sizeof(unsigned long long) * (size_t)n_rows, e->stream));
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads);
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 0], e->stream));
+    if (n_items > 0) {
+        const dim3 items((unsigned)std::min<int64_t>(flat_grid(n_items, threads), 1 << 20));
+        hipLaunchKernelGGL(k_cmp_rank, items, tb, 0, e->stream, D, M);
+        hipLaunchKernelGGL(k_cmp_at, items, tb, 0, e->stream, M);
+    }
+    hipLaunchKernelGGL(k_cmp_final, dim3(flat_grid(n_rows, threads)), tb, 0, e->stream, D, M);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 1], e->stream));
+    if (permuted > 0) {
+        const WaveShape per_block = wave_shape(e, n_rows * ((q->n_perm + 63) / 64), 1, kCmpWaves);
+        hipLaunchKernelGGL(k_cmp_perm, per_block.grid, per_block.block, 0, e->stream, M);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 2], e->stream));
+    if (out != nullptr) {
+        const size_t nr = (size_t)n_rows, nrq = nr * (size_t)q->n_q;
+        TWCHK(copy_out(e, out->n_a, M.n_a, nr));
+        TWCHK(copy_out(e, out->n_b, M.n_b, nr));
+        TWCHK(copy_out(e, out->ks_gap, M.ks_gap, nr));
+        TWCHK(copy_out(e, out->ks_at, M.ks_at, nr));
+        TWCHK(copy_out(e, out->u2, M.u2, nr));
+        if (nrq > 0) TWCHK(copy_out(e, out->quantile_shift, M.shift, nrq));
+        if (q->n_perm > 0) {
+            TWCHK(copy_out(e, out->perm_ge_ks, M.ge_ks, nr));
+            TWCHK(copy_out(e, out->perm_ge_u, M.ge_u, nr));
+            if (nrq > 0) TWCHK(copy_out(e, out->perm_ge_q, M.ge_q, nrq));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, SE_CMP, i, i + 1, &e->cm_ms[i]));
+    if (summary != nullptr) { summary[0] = both; summary[1] = permuted; summary[2] = permuted_items; summary[3] = q->n_perm; }
     return TW_OK;
 }
 

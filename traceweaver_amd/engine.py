@@ -570,6 +570,36 @@ class Engine(object):
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 25))
         return dict(zip(("items", "sort", "quantiles"), ms[22:25].tolist()))
 
+    def compare_cohorts(self, pairs=((0, 1),), probs=(0.5, 0.95, 0.99), permutations=0, seed=0, max_pool=0):
+        """Pairs of cohorts (a, b) compared segment by segment on the device (tw_compare_cohorts), on what distributions() works
+        on: per (pair, metric, group) the sizes, the two-sample KS gap and where it lies, twice the Mann-Whitney U of b over a,
+        the quantile shifts Q_b - Q_a at `probs` (at most 8) and, with `permutations` > 0 (at most 65536), how many permutations
+        of the pooled values are at least as extreme in each of them (`seed` selects the draws; rows of more than `max_pool`
+        pooled values, when it is > 0, are not permuted).  Returns traces.CohortComparison."""
+        from .traces import CohortComparison
+
+        G = int(getattr(self, "_n_groups", 0))
+        pa = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        n_rows = min(len(pa), _ffi.TW_CMP_MAX_PAIRS) * (3 * G + 1)
+        nq, n_perm = min(len(pr), _ffi.TW_CMP_MAX_Q), int(permutations)
+        q = _ffi.CmpQuery(len(pa), _vp(pa) if len(pa) else ctypes.c_void_p(0), len(pr), _vp(pr) if len(pr) else ctypes.c_void_p(0),
+                          n_perm, int(seed) & ((1 << 64) - 1), int(max_pool))
+        one = [np.zeros(n_rows, dtype=np.int64) for _ in range(5)]
+        shift = np.zeros((n_rows, nq), dtype=np.int64)
+        ge_ks, ge_u = np.full(n_rows, -1, dtype=np.int64), np.full(n_rows, -1, dtype=np.int64)   # (not written with permutations=0)
+        ge_q = np.full((n_rows, nq), -1, dtype=np.int64)
+        summary = np.zeros(4, dtype=np.int64)
+        out = _ffi.CohortComparison(*([_vp(x) for x in one] + [_vp(shift) if shift.size else None, _vp(ge_ks), _vp(ge_u), _vp(ge_q) if ge_q.size else None]))
+        self._check(self._lib.tw_compare_cohorts(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        return CohortComparison(one[0], one[1], one[2], one[3], one[4], shift, ge_ks, ge_u, ge_q, summary, pa, pr, G, n_perm)
+
+    def compare_timing(self):
+        """The last compare_cohorts() on the device (HIP events, ms): ranks, pool and observed statistics; the permutation walk."""
+        ms = np.zeros(35, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 35))
+        return dict(zip(("observed", "permutations"), ms[33:35].tolist()))
+
     def signatures(self, mode="levels", need_flags=1, skip_flags=0, keep_reference=False, compare=False):
         """The trees of the last stitch() grouped by call-graph signature (tw_trace_signatures): per eligible tree (flags hold
         need_flags, none of skip_flags; default: whole traces, those with an unassigned call included) the run-length encoded,

@@ -109,6 +109,14 @@ def parse_args(argv=None):
     ap.add_argument("--cohort_service", type=q, default=None,
                     help="--latency_out: split the traces into cohorts by the operation of this service's span in them (the smallest "
                          "operation index where a trace holds several); traces without a span of the service are left out")
+    ap.add_argument("--compare_out", type=q, default=None,
+                    help="compare the cohorts of --cohort_service pair by pair on the device (tw_compare_cohorts: per service and metric the "
+                         "two-sample KS gap, the Mann-Whitney U, the shifts of --quantiles (at most 8) and, with --permutations, a permutation "
+                         "test of each), write the result to this .npz and print the culprit's span latency per pair.  Needs --latency_out "
+                         "and --cohort_service.  Default: off, nothing changes")
+    ap.add_argument("--compare_pairs", type=q, default="0,1", help="--compare_out: the pairs of cohorts a,b, separated by semicolons (0,1;0,2)")
+    ap.add_argument("--permutations", type=int, default=0, help="--compare_out: permutations per compared segment, at most 65536 (0: no test)")
+    ap.add_argument("--compare_seed", type=int, default=0, help="--compare_out: the seed of the permutations")
     ap.add_argument("--signatures_out", type=q, default=None,
                     help="group the traces by call-graph signature on the device (per level the services seen there, the reference's "
                          "AssignCGSignature / FindUniqueCGs): the signatures of the true traces are kept as the reference set, those of "
@@ -161,6 +169,15 @@ def quantiles_of(args):
     return probs if 0 < len(probs) <= 32 and all(0.0 <= p <= 1.0 for p in probs) else None
 
 
+def pairs_of(args):
+    """--compare_pairs as a list of (a, b), None if it is malformed (the cohorts' range is checked once their number is known)."""
+    try:
+        pairs = [tuple(int(x) for x in part.split(",")) for part in args.compare_pairs.split(";") if part.strip() != ""]
+    except ValueError:
+        return None
+    return pairs if 0 < len(pairs) <= 64 and all(len(p) == 2 and p[0] != p[1] and min(p) >= 0 for p in pairs) else None
+
+
 def unsupported(args):
     problems = []
     bad = [i for i in requested(args) if i != 10 and i not in BASELINES]
@@ -185,6 +202,16 @@ def unsupported(args):
         problems.append("--quantiles %s (up to 32 comma-separated numbers in [0, 1])" % args.quantiles)
     if args.cohort_service and not args.latency_out:
         problems.append("--cohort_service without --latency_out")
+    if args.compare_out and not (args.latency_out and args.cohort_service):
+        problems.append("--compare_out without --latency_out and --cohort_service (it compares the cohorts of that service)")
+    if args.compare_out and pairs_of(args) is None:
+        problems.append("--compare_pairs %s (up to 64 pairs a,b of different cohorts, separated by semicolons)" % args.compare_pairs)
+    if args.compare_out and not 0 <= args.permutations <= 65536:
+        problems.append("--permutations outside [0, 65536]")
+    if args.compare_out and args.compare_seed < 0:
+        problems.append("--compare_seed below 0")
+    if args.compare_out and len(quantiles_of(args) or ()) > 8:
+        problems.append("--compare_out with more than 8 --quantiles")
     if args.signatures_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--signatures_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.profiles_out and (10 not in requested(args) or args.cache_rate > 0):
@@ -408,6 +435,19 @@ def quantile_line(d, g, head):
     return "%s: %s" % (head, "; ".join(parts) if parts else "no spans")
 
 
+def comparison_line(c, i, g, name):
+    """Pair i of a comparison for the span latency of group g."""
+    r = c.row(i, 0, g)
+    a, b = c.pairs[i].tolist()
+    if c.n_a[r] == 0 or c.n_b[r] == 0:
+        return "Cohort %d against %d, %s span latency: no spans in one of them (%d, %d)" % (a, b, name, c.n_a[r], c.n_b[r])
+    tested = c.perm_ge_ks[r] >= 0
+    shifts = ", ".join("p%g %+d us%s" % (100 * p, c.quantile_shift[r][j], " (p = %.4f)" % c.p_value(j)[r] if tested else "") for j, p in enumerate(c.probs.tolist()))
+    return "Cohort %d against %d, %s span latency over %d and %d spans: %s; KS %.4f at %d us%s; superiority %.4f%s" % (
+        a, b, name, c.n_a[r], c.n_b[r], shifts, c.ks()[r], c.ks_at[r], " (p = %.4f)" % c.p_value("ks")[r] if tested else "",
+        c.superiority()[r], " (p = %.4f)" % c.p_value("u")[r] if tested else "")
+
+
 def attribute_out(args, eng, st, corpus, table):
     """--attribute_out / --latency_out: the delay-culprit query on the forest just stitched, groups by service, and the
     distributions behind its answer."""
@@ -429,6 +469,15 @@ def attribute_out(args, eng, st, corpus, table):
         print("Latency distributions: %d values in %d segments over %d traces (%d without a cohort)" % (d.n_items, d.summary[1], d.summary[2], d.summary[3]))
         if args.verbose and a.culprit >= 0:
             print(quantile_line(d, a.culprit, "Culprit span latency"))
+    if args.compare_out:
+        pairs = pairs_of(args)
+        if max(max(p) for p in pairs) >= len(cohort_names):
+            raise SystemExit("--compare_pairs %s: %s has %d cohorts (%s)" % (args.compare_pairs, args.cohort_service, len(cohort_names), ", ".join(str(x) for x in cohort_names)))
+        c = eng.compare_cohorts(pairs, quantiles_of(args), args.permutations, args.compare_seed)
+        traces.write_comparison_npz(args.compare_out, c, names)
+        print("Cohort comparison: %d pairs, %d segments with spans in both, %d permutations of %d" % (len(pairs), c.summary[0], c.summary[3], c.summary[1]))
+        for i in range(len(pairs) if a.culprit >= 0 else 0):
+            print(comparison_line(c, i, a.culprit, names[a.culprit]))
     if args.verbose:
         eng.stitch(truth=True)
         b = eng.attribute(**query)

@@ -572,7 +572,9 @@ def distributions_host(stitched, attribution, row_start, row_end, row_group, n_g
 def compare_distributions(a, b):
     """Two results with the same segment layout side by side, per segment: quantile_diff [n_seg, n_q] = b's quantile less a's (0
     where either segment is empty), both [n_seg] = neither is empty, and cdf_gap [n_seg] = the largest |F_a(x) - F_b(x)| over the
-    union of both value sets, F(x) = the share of values <= x (nan where either is empty).  On the host, in numpy."""
+    union of both value sets, F(x) = the share of values <= x (nan where either is empty).  On the host, in numpy: it compares any
+    two results, predicted against true among them, which are two different resident states.  Cohort against cohort of one result
+    is compared on the device, with a permutation test: Engine.compare_cohorts (tw_compare_cohorts)."""
     if (a.n_cohorts, a.n_groups) != (b.n_cohorts, b.n_groups) or not np.array_equal(a.probs, b.probs):
         raise ValueError("the two results differ in their segments or probs")
     both = (np.asarray(a.seg_count) > 0) & (np.asarray(b.seg_count) > 0)
@@ -594,6 +596,183 @@ def write_distributions_npz(path, distributions, names):
         np.savez_compressed(
             f, n_cohorts=np.int64(d.n_cohorts), n_groups=np.int64(d.n_groups), metrics=np.array(METRICS), group_names=np.array([str(x) for x in names]),
             probs=d.probs, edges=d.edges, **{k: getattr(d, k) for k in LatencyDistributions.FIELDS})
+
+
+class CohortComparison(object):
+    """Pairs of cohorts compared segment by segment (include/traceweaver_amd.h has the definitions): row = pair * (3 G + 1) + m * G +
+    g compares A = segment (a, m, g) with B = segment (b, m, g) of pairs[pair] = (a, b).  n_a, n_b [n_rows]; ks_gap = #{A <= x} n_b
+    - #{B <= x} n_a at ks_at, the smallest x where its magnitude is greatest; u2 = 2 #{A_i < B_j} + #{A_i = B_j}; quantile_shift
+    [n_rows, len(probs)] = Q_B - Q_A; perm_ge_ks, perm_ge_u, perm_ge_q: of n_perm permutations of the pooled values those at least
+    as extreme as the observed statistic, -1 where the row was not permuted (a side empty, more than max_pool values, n_perm = 0);
+    summary = rows with both sides non-empty, rows permuted, pooled items permuted, n_perm."""
+
+    FIELDS = ("n_a", "n_b", "ks_gap", "ks_at", "u2", "quantile_shift", "perm_ge_ks", "perm_ge_u", "perm_ge_q", "summary")
+
+    def __init__(self, n_a, n_b, ks_gap, ks_at, u2, quantile_shift, perm_ge_ks, perm_ge_u, perm_ge_q, summary, pairs, probs, n_groups, n_perm):
+        self.n_a, self.n_b, self.ks_gap, self.ks_at, self.u2, self.quantile_shift = n_a, n_b, ks_gap, ks_at, u2, quantile_shift
+        self.perm_ge_ks, self.perm_ge_u, self.perm_ge_q = perm_ge_ks, perm_ge_u, perm_ge_q
+        self.summary = np.asarray(summary, dtype=np.int64)
+        self.pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        self.probs = np.asarray(probs, dtype=np.float64)
+        self.n_groups, self.n_perm = int(n_groups), int(n_perm)
+
+    n_rows = property(lambda self: len(self.pairs) * (3 * self.n_groups + 1))
+
+    def row(self, pair_index, metric, group=None):
+        m = METRICS.index(metric) if isinstance(metric, str) else int(metric)
+        if not (0 <= pair_index < len(self.pairs) and 0 <= m < 4 and (m == 3 or 0 <= group < self.n_groups)):
+            raise IndexError((pair_index, metric, group))
+        return pair_index * (3 * self.n_groups + 1) + m * self.n_groups + (0 if m == 3 else int(group))
+
+    def _both(self):
+        return (np.asarray(self.n_a) > 0) & (np.asarray(self.n_b) > 0)
+
+    def _over_pairs(self, x):
+        both = self._both()
+        prod = np.where(both, np.asarray(self.n_a, dtype=np.float64) * np.asarray(self.n_b, dtype=np.float64), 1.0)
+        return np.where(both, np.asarray(x, dtype=np.float64) / prod, np.nan)
+
+    def ks(self):
+        """The two-sample KS statistic |ks_gap| / (n_a n_b) per row, nan where a side is empty."""
+        return self._over_pairs(np.abs(np.asarray(self.ks_gap, dtype=np.float64)))
+
+    def superiority(self):
+        """u2 / (2 n_a n_b) per row: the probability that a value of B exceeds one of A, ties counted half; nan where a side is empty."""
+        return self._over_pairs(np.asarray(self.u2, dtype=np.float64) / 2.0)
+
+    def p_value(self, which):
+        """(1 + ge) / (1 + n_perm) per row for "ks", "u" or the index of a prob; nan where the row was not permuted."""
+        ge = self.perm_ge_ks if which == "ks" else self.perm_ge_u if which == "u" else np.asarray(self.perm_ge_q)[:, int(which)]
+        ge = np.asarray(ge, dtype=np.float64)
+        return np.where(ge >= 0, (1.0 + ge) / (1.0 + self.n_perm), np.nan)
+
+    def table(self, names=None):
+        """One dict per row with both sides non-empty: pair, metric, group (None for the trace latency), the sizes, ks, ks_at,
+        superiority, the shifts as shift_p<percent> and, where permuted, p_ks, p_u and p_shift_p<percent>."""
+        rows, per = [], 3 * self.n_groups + 1
+        ks, sup = self.ks(), self.superiority()
+        pv = {"ks": self.p_value("ks"), "u": self.p_value("u")}
+        pq = [self.p_value(j) for j in range(len(self.probs))]
+        for i in np.flatnonzero(self._both()).tolist():
+            pi, rest = divmod(i, per)
+            m, g = (3, None) if rest == 3 * self.n_groups else divmod(rest, self.n_groups)
+            d = dict([("pair", tuple(self.pairs[pi].tolist())), ("metric", METRICS[m]), ("group", g if names is None or g is None else names[g]),
+                      ("n_a", int(self.n_a[i])), ("n_b", int(self.n_b[i])), ("ks", float(ks[i])), ("ks_at", int(self.ks_at[i])),
+                      ("superiority", float(sup[i]))] +
+                     [("shift_p%g" % (100 * p), int(self.quantile_shift[i][j])) for j, p in enumerate(self.probs.tolist())])
+            if self.perm_ge_ks[i] >= 0:
+                d.update([("p_ks", float(pv["ks"][i])), ("p_u", float(pv["u"][i]))] +
+                         [("p_shift_p%g" % (100 * p), float(pq[j][i])) for j, p in enumerate(self.probs.tolist())])
+            rows.append(d)
+        return rows
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+_M64 = (1 << 64) - 1
+_GOLD = 0x9E3779B97F4A7C15
+
+
+def _mix64(x):
+    """splitmix64's finaliser."""
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def permutation_labels_host(N, n_a, seed, row, p):
+    """Permutation p of row `row`: a list of N labels, 0 = the pooled value at that position goes to A', 1 = to B'; exactly n_a
+    zeros.  Selection sampling along the pooled values: item k goes to A' iff (h_k * (N - k)) >> 64 < n_a - (given so far)."""
+    key = _mix64((_mix64((seed + _GOLD * (row + 1)) & _M64) + _GOLD * (p + 1)) & _M64)
+    labels, c = [], 0
+    for k in range(N):
+        h = _mix64((key + _GOLD * (k + 1)) & _M64)
+        if (h * (N - k)) >> 64 < n_a - c:
+            labels.append(0)
+            c += 1
+        else:
+            labels.append(1)
+    return labels
+
+
+def two_sample_host(A, B, probs):
+    """ks_gap, ks_at, u2 and the quantile shifts of two non-empty ascending lists of integers, from the definitions."""
+    import bisect
+
+    na, nb = len(A), len(B)
+    gap, at = 0, None
+    for x in sorted(set(A) | set(B)):
+        g = bisect.bisect_right(A, x) * nb - bisect.bisect_right(B, x) * na
+        if at is None or abs(g) > abs(gap):
+            gap, at = g, x
+    u2 = 0
+    for v in A:
+        hi = bisect.bisect_right(B, v)
+        u2 += 2 * (nb - hi) + (hi - bisect.bisect_left(B, v))
+    shifts = [B[min(nb - 1, int(p * float(nb)))] - A[min(na - 1, int(p * float(na)))] for p in probs]
+    return gap, at, u2, shifts
+
+
+def compare_cohorts_host(distributions, pairs=((0, 1),), probs=(0.5, 0.95, 0.99), permutations=0, seed=0, max_pool=0):
+    """What tw_compare_cohorts computes, restated from the definitions in plain Python integers, from a LatencyDistributions (with
+    its values) alone, for the tests."""
+    d = distributions
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    probs = [float(p) for p in np.asarray(probs, dtype=np.float64).ravel().tolist()]
+    per, nq, n_perm = 3 * d.n_groups + 1, len(probs), int(permutations)
+    n_rows = len(pairs) * per
+    out = {k: np.zeros(n_rows, dtype=np.int64) for k in ("n_a", "n_b", "ks_gap", "u2")}
+    out["ks_at"] = np.full(n_rows, EMPTY, dtype=np.int64)
+    out["quantile_shift"] = np.zeros((n_rows, nq), dtype=np.int64)
+    out["perm_ge_ks"], out["perm_ge_u"] = np.full(n_rows, -1, dtype=np.int64), np.full(n_rows, -1, dtype=np.int64)
+    out["perm_ge_q"] = np.full((n_rows, nq), -1, dtype=np.int64)
+    both = permuted = items = 0
+    for row in range(n_rows):
+        pi, r = divmod(row, per)
+        sa, sb = int(pairs[pi][0]) * per + r, int(pairs[pi][1]) * per + r
+        A = d.values[int(d.seg_off[sa]):int(d.seg_off[sa + 1])].tolist()
+        B = d.values[int(d.seg_off[sb]):int(d.seg_off[sb + 1])].tolist()
+        na, nb = len(A), len(B)
+        out["n_a"][row], out["n_b"][row] = na, nb
+        if na == 0 or nb == 0:
+            continue
+        both += 1
+        gap, at, u2, shifts = two_sample_host(A, B, probs)
+        out["ks_gap"][row], out["ks_at"][row], out["u2"][row] = gap, at, u2
+        out["quantile_shift"][row] = shifts
+        N = na + nb
+        if n_perm == 0 or (max_pool > 0 and N > max_pool):
+            continue
+        permuted += 1
+        items += N
+        M = sorted(A + B)
+        ge_ks = ge_u = 0
+        ge_q = [0] * nq
+        for p in range(n_perm):
+            labels = permutation_labels_host(N, na, int(seed), row, p)
+            A2 = [v for v, l in zip(M, labels) if l == 0]
+            B2 = [v for v, l in zip(M, labels) if l == 1]
+            g2, _, u, s2 = two_sample_host(A2, B2, probs)
+            ge_ks += abs(g2) >= abs(gap)
+            ge_u += abs(u - na * nb) >= abs(u2 - na * nb)
+            for j in range(nq):
+                ge_q[j] += abs(s2[j]) >= abs(shifts[j])
+        out["perm_ge_ks"][row], out["perm_ge_u"][row] = ge_ks, ge_u
+        out["perm_ge_q"][row] = ge_q
+    return CohortComparison(summary=[both, permuted, items, n_perm], pairs=pairs, probs=probs, n_groups=d.n_groups, n_perm=n_perm, **out)
+
+
+def write_comparison_npz(path, comparison, names):
+    """The comparison as one .npz next to the one write_distributions_npz stores: the arrays of CohortComparison, the layout (pairs,
+    n_groups, metrics, group names) and the query (probs, n_perm)."""
+    c = comparison
+    with open(path, "wb") as f:
+        np.savez_compressed(
+            f, pairs=c.pairs, n_groups=np.int64(c.n_groups), metrics=np.array(METRICS), group_names=np.array([str(x) for x in names]),
+            probs=c.probs, n_perm=np.int64(c.n_perm), **{k: getattr(c, k) for k in CohortComparison.FIELDS})
 
 
 SIGNATURE_MODES = ("levels", "edges")

@@ -255,7 +255,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * read of the item count), ms[23] sort, offsets and values, ms[24] quantiles and histogram (22 and 23: of the call that built
  * the items).  ms[25..30]: tw_trace_signatures and tw_class_profiles (see there).  ms[31]: the kernel of the last tw_order_bound.
  * ms[32] (a count): class stages of the last pass that were queued behind the stage gate (TW_STAGE_GATE), 0 = the pass was not gated.
- * The last tw_compare_cohorts (HIP events): ms[33] ranks, pool and observed statistics, ms[34] the permutation walk (0 without one). */
+ * The last tw_compare_cohorts (HIP events): ms[33] ranks, pool and observed statistics, ms[34] the permutation walk (0 without one).
+ * ms[35], ms[36] (counts): rows of the last refit whose final fit ran beside the model selection and was adopted (the row selected
+ * the largest admissible count, min(5, #distinct)) / rows that were fitted after the selection; both 0 under TW_FIT_SPEC=0. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------

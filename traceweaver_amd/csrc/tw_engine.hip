@@ -70,6 +70,7 @@ struct Knobs {
     int part_budget_deep;     // TW_PART_BUDGET_DEEP: extra work-list entries per span of the classes of five and more endpoints (part_extra)
     int fit_sort;             // TW_FIT_SORT=1: the gap rows go the sort route (fit_prepare)
     int stage_gate;           // TW_STAGE_GATE: the stages of the shorter classes wait for the critical class' tile kernel (launch_class_stage; 0 = they do not: A/B runs, bisection)
+    int fit_spec;             // TW_FIT_SPEC: the final fit of the likeliest count runs beside the model selection (fit_run; 0 = after it, five launches on one stream: A/B runs, bisection)
 };
 
 Knobs read_knobs() {
@@ -99,6 +100,7 @@ Knobs read_knobs() {
     K.part_budget_deep = env_int("TW_PART_BUDGET_DEEP", 2);
     K.fit_sort = env_int("TW_FIT_SORT", 0);
     K.stage_gate = env_int("TW_STAGE_GATE", 1);
+    K.fit_spec = env_int("TW_FIT_SPEC", 1) != 0 ? 1 : 0;
     return K;
 }
 
@@ -182,6 +184,12 @@ struct tw_engine {
     double* fit_uval = nullptr;
     int32_t *fit_ustart = nullptr, *fit_row_n = nullptr, *fit_row_uniq = nullptr;
     double* fit_centres = nullptr;
+    // the speculative final fit (fit_run, tw_fit.h): forked from and joined to the engine's stream; its results; hits and misses of
+    // the last refit (tw_get_timing slots 35, 36)
+    hipEvent_t fit_fork = nullptr, fit_join = nullptr;
+    double *fit_spec_centres = nullptr, *fit_spec_p = nullptr;
+    int32_t *fit_spec_failed = nullptr, *fit_spec_ctr = nullptr;
+    int32_t fit_spec_count[2] = {0, 0};
     double *fit_tape = nullptr, *fit_tape100 = nullptr;   // uniforms of the k-means++ seedings: model-selection fits / the refit (MT19937(100))
     int64_t* fit_tape_off = nullptr;
     int64_t fit_tape_cap = 0;
@@ -1133,6 +1141,8 @@ int tw_create(int device_id, tw_engine** out) {
     if (e->K.set_hw_queues != 0) setenv("GPU_MAX_HW_QUEUES", "12", 0);
     hipError_t s = hipSetDevice(device_id);
     if (s == hipSuccess) s = hipStreamCreate(&e->stream);
+    if (s == hipSuccess) s = hipEventCreateWithFlags(&e->fit_fork, hipEventDisableTiming);
+    if (s == hipSuccess) s = hipEventCreateWithFlags(&e->fit_join, hipEventDisableTiming);
     for (int i = 0; i < EV_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->ev[i]);
     for (int i = 0; i < SE_COUNT && s == hipSuccess; i++) s = hipEventCreate(&e->stage_ev[i]);
     // (the class streams are created when a batch first holds the class, tw_load_batch: the streams of a process share its hardware
@@ -1171,6 +1181,8 @@ void tw_destroy(tw_engine* e) {
         if (e->sel_stream[i]) (void)hipStreamDestroy(e->sel_stream[i]);
     if (e->prep_ev) (void)hipEventDestroy(e->prep_ev);
     if (e->tile_done) (void)hipEventDestroy(e->tile_done);
+    if (e->fit_fork) (void)hipEventDestroy(e->fit_fork);
+    if (e->fit_join) (void)hipEventDestroy(e->fit_join);
     for (int i = 0; i <= kMaxEp; i++) {
         if (e->post_fork[i]) (void)hipEventDestroy(e->post_fork[i]);
         if (e->post_done[i]) (void)hipEventDestroy(e->post_done[i]);
@@ -1449,6 +1461,8 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     DEV_ALLOC(e->fit_tape, slots * kFitRowTape); DEV_ALLOC(e->fit_tape_off, slots); DEV_ALLOC(e->fit_tape100, kMaxComp * 13);
     e->fit_tape_cap = slots * kFitRowTape;
     DEV_ALLOC(e->fit_centres, slots * kMaxComp * (kMaxComp + 1));
+    DEV_ALLOC(e->fit_spec_centres, slots * (kMaxComp + 1)); DEV_ALLOC(e->fit_spec_p, slots * kMaxComp * 3);
+    DEV_ALLOC(e->fit_spec_failed, slots); DEV_ALLOC(e->fit_spec_ctr, 2);
     DEV_ALLOC(e->slot_unit, slots); DEV_ALLOC(e->slot_scored, slots);
     DEV_ALLOC(e->seg_gap, (int64_t)seg_gap_h.size()); DEV_ALLOC(e->seg_gap_end, (int64_t)seg_gap_end_h.size()); DEV_ALLOC(e->seg_gap_dst, (int64_t)seg_gap_dst_h.size());
     e->comp_cap = std::max(std::max(n_in_total, n_out_total), e->n_gap_scored);
@@ -1614,6 +1628,7 @@ FitDev fit_dev(tw_engine* e) {
     F.gs_off = e->P.gs_off; F.slot_unit = e->slot_unit; F.slot_scored = e->slot_scored; F.models = e->fit_models; F.mix_n = e->mix_n_dev; F.mix_p = e->mix_p_dev;
     F.uval = e->fit_uval; F.ustart = e->fit_ustart; F.row_n = e->fit_row_n; F.row_uniq = e->fit_row_uniq;
     F.tape = e->fit_tape; F.tape_off = e->fit_tape_off; F.tape100 = e->fit_tape100; F.err = e->P.err; F.centres = e->fit_centres;
+    F.full_mode = FIT_FINAL; F.spec_centres = e->fit_spec_centres; F.spec_p = e->fit_spec_p; F.spec_failed = e->fit_spec_failed; F.spec_ctr = e->fit_spec_ctr;
     return F;
 }
 
@@ -1697,10 +1712,42 @@ int fit_run(tw_engine* e) {
     HIPCHK(hipMemsetAsync(e->P.err, 0, sizeof(int32_t), e->stream));
     FitDev F = fit_dev(e);
     const int threads = e->K.coop >= 64 ? kFitThreads : e->K.coop;
+    // The second stream of the refit is the stream of the batch's first class, idle between the passes: every batch has one
+    // (tw_load_batch), and its work is joined to the engine's stream below.  A stream of the refit's own, created in tw_create, took
+    // the hardware queue that the class streams created after it would have had (the runtime deals a process' streams onto four
+    // queues by default): the deepest class then shared the engine's queue and each pass of the headline was 1 ms longer
+    // (profiles/HISTORY.md, round 13).  Borrowed, the streams' queues are those of an engine without the speculative fit; the
+    // headline gains the same 1.1 ms with 4 and with 12 hardware queues.  (side_cls = 0 cannot occur for a loaded batch: every unit
+    // has at least one endpoint, so some class has tiles and tw_load_batch created its stream; such a refit would run unforked.)
+    int side_cls = 0;
+    for (int E = kMaxEp; E >= 1; E--)
+        if (e->tile_cls_off[E + 1] > e->tile_cls_off[E]) side_cls = E;
+    const hipStream_t side = e->cls_stream[side_cls];
+    const bool spec = e->K.fit_spec != 0 && side_cls > 0;
+    e->fit_spec_count[0] = e->fit_spec_count[1] = 0;
+    if (spec) {
+        // The final fit GaussianMixture(n_selected, random_state=100) depends on the model selection only through the count; the
+        // row, its runs and the tape are fixed by now.  The likeliest count (fit_spec_k) is fitted on the second stream beside
+        // the selection, into buffers of its own: the two nearly empty launches behind k_fit_select (one workgroup per row on
+        // 256 CUs, as long as the longest fit) leave the chain and their workgroups fill the tails of the two busy ones.  (Queued
+        // first: the long rows' fits of the largest count are the longest workgroups of the refit.)
+        HIPCHK(hipMemsetAsync(e->fit_spec_ctr, 0, 2 * sizeof(int32_t), e->stream));
+        HIPCHK(hipEventRecord(e->fit_fork, e->stream));   // (behind the tapes, the prepared rows and the reset of err)
+        HIPCHK(hipStreamWaitEvent(side, e->fit_fork, 0));
+        FitDev S = F;
+        S.full_mode = FIT_SPEC;
+        hipLaunchKernelGGL(k_fit_seed<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, side, S);
+        hipLaunchKernelGGL(k_fit_em<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, side, S);
+        HIPCHK(hipEventRecord(e->fit_join, side));
+    }
     // Model selection: two launches over all counts, the largest count (the longest fits) first (fit_row)
     hipLaunchKernelGGL(k_fit_seed<false>, dim3((unsigned)(e->n_slots * (kMaxComp - 1))), dim3(threads), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_em<false>, dim3((unsigned)(e->n_slots * kMaxComp)), dim3(threads), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_select, dim3((unsigned)((e->n_slots + 63) / 64)), dim3(64), 0, e->stream, F);
+    if (spec) {   // rows that selected the count fitted ahead adopt its result (k_fit_em), the others are fitted now
+        HIPCHK(hipStreamWaitEvent(e->stream, e->fit_join, 0));
+        F.full_mode = FIT_ADOPT;
+    }
     hipLaunchKernelGGL(k_fit_seed<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, e->stream, F);
     hipLaunchKernelGGL(k_fit_em<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, e->stream, F);
     const int64_t total = e->n_slots * kMaxComp;
@@ -1709,6 +1756,7 @@ int fit_run(tw_engine* e) {
     HIPCHK(hipGetLastError());
     int32_t kerr = 0;
     HIPCHK(hipMemcpyAsync(&kerr, e->P.err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (spec) HIPCHK(hipMemcpyAsync(e->fit_spec_count, e->fit_spec_ctr, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float f = 0.f;
     HIPCHK(hipEventElapsedTime(&f, e->ev[EV_BEGIN], e->ev[EV_END]));
@@ -1888,6 +1936,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 31) ms[31] = e->ob_ms;                                        // the last tw_order_bound
     if (n > 32) ms[32] = (double)e->gate_waits;                           // class stages of the last pass that were queued behind the stage gate
     for (int i = 0; i < 2 && 33 + i < n; i++) ms[33 + i] = e->cm_ms[i];   // the last tw_compare_cohorts
+    for (int i = 0; i < 2 && 35 + i < n; i++) ms[35 + i] = (double)e->fit_spec_count[i];   // the last refit: rows that adopted the fit made ahead / that were fitted after the selection
     return TW_OK;
 }
 

@@ -78,7 +78,18 @@ struct FitDev {
     const double* tape100;  // [kMaxComp][13] draws of the refit with n components: MT19937(100)
     int32_t* err;
     double* centres;        // [n_slots][kMaxComp][1 + kMaxComp] k-means start of every fit: mean of the samples, final centres (centred)
+    // The speculative final fit (fit_run): the refit of the selected count depends on the model selection only through the count, so
+    // the likeliest count -- fit_spec_k -- is fitted beside the selection, into buffers of its own, and adopted by the rows that
+    // select it.  full_mode says which (row, count) pairs a launch of the kFull kernels serves and where its results go.
+    int32_t full_mode;      // FIT_FINAL | FIT_SPEC | FIT_ADOPT
+    double* spec_centres;   // [n_slots][1 + kMaxComp] k-means start of the speculative fit
+    double* spec_p;         // [n_slots][kMaxComp][3] its result, laid out like mix_p ...
+    int32_t* spec_failed;   // [n_slots] ... or 1: it ended in a covariance <= 0 (an error only if the row selects that count)
+    int32_t* spec_ctr;      // [2] rows of the last refit that adopted their speculative fit / that were fitted after the selection
 };
+enum { FIT_FINAL = 0,   // k = mix_n[q], results in centres / mix_p (the refit without speculation)
+       FIT_SPEC = 1,    // k = fit_spec_k(q), results in spec_centres / spec_p / spec_failed; runs beside the model selection
+       FIT_ADOPT = 2 }; // k = mix_n[q]; a row that selected fit_spec_k(q) takes the speculative result, the others are fitted as under FIT_FINAL
 
 // deterministic block reduction of `cnt` doubles per thread: lanes of a wavefront by shuffles (fixed
 // butterfly order), wavefronts by thread 0 in wavefront order.  Result broadcast to every thread.
@@ -306,14 +317,30 @@ struct FitRow {
     int64_t q, row;
     int k, n_all, n, uniq;
     bool live;
+    bool adopt;   // FIT_ADOPT: the row selected the count that was fitted ahead
 };
+// The count fitted ahead of the selection: the largest admissible one, min(kMaxComp, #distinct) -- what BIC picks whenever a row
+// has many samples (every row of 10^5 samples probed, half of the rows of 10^3) -- from what k_fit_runs / k_fit_compress leave.
+__device__ __forceinline__ int fit_spec_k(const FitDev& F, int64_t q) {
+    if (!F.slot_scored[q] || F.row_n[q] <= 0) return 0;
+    const int u = F.row_uniq[q];
+    return u < kMaxComp ? u : kMaxComp;
+}
 // Which (row, component count) a workgroup serves.  Model selection: the fits with the most components first (they run
-// longest), `skip1` leaves k = 1 out (k-means of one cluster is no work); refit: k = the selected count.
+// longest), `skip1` leaves k = 1 out (k-means of one cluster is no work); refit: k = the selected count, or the speculative
+// one (F.full_mode; a FIT_SPEC launch runs beside k_fit_select and does not read mix_n).
 template <bool kFull>
 __device__ __forceinline__ FitRow fit_row(const FitDev& F, bool skip1) {
     FitRow R;
     R.q = kFull ? (int64_t)blockIdx.x : (int64_t)(blockIdx.x % F.n_slots);
-    R.k = kFull ? F.mix_n[R.q] : kMaxComp - (int)(blockIdx.x / F.n_slots);
+    R.adopt = false;
+    if (kFull) {
+        const int sk = F.full_mode != FIT_FINAL ? fit_spec_k(F, R.q) : 0;
+        R.k = F.full_mode == FIT_SPEC ? sk : F.mix_n[R.q];
+        R.adopt = F.full_mode == FIT_ADOPT && R.k == sk;
+    } else {
+        R.k = kMaxComp - (int)(blockIdx.x / F.n_slots);
+    }
     const UnitDev& U = F.units[F.slot_unit[R.q]];
     R.n_all = U.n_in;
     R.row = F.gs_off[F.slot_unit[R.q]] + (R.q - U.slot_off) * (int64_t)R.n_all;
@@ -339,7 +366,7 @@ __global__ void __launch_bounds__(kFitThreads) TW_FIT_SEED_ATTR k_fit_seed(FitDe
     __shared__ double run_x[kRunCache];
     __shared__ int32_t run_c[kRunCache];
     const FitRow R = fit_row<kFull>(F, true);
-    if (!R.live) return;
+    if (!R.live || R.adopt) return;
     const int k = R.k, n = R.n, uniq = R.uniq, n_all = R.n_all;
     const int64_t q = R.q;
     const int t = threadIdx.x, nt = blockDim.x;
@@ -606,7 +633,7 @@ __global__ void __launch_bounds__(kFitThreads) TW_FIT_SEED_ATTR k_fit_seed(FitDe
     }
     // the labels KMeans returns: those of the last assignment (strict convergence) or a fresh one under the final centres
     if (t == 0) {
-        double* out = F.centres + (q * kMaxComp + (k - 1)) * (kMaxComp + 1);
+        double* out = (kFull && F.full_mode == FIT_SPEC) ? F.spec_centres + q * (kMaxComp + 1) : F.centres + (q * kMaxComp + (k - 1)) * (kMaxComp + 1);
         out[0] = mean;
 #pragma unroll
         for (int j = 0; j < kMaxComp; j++) out[1 + j] = strict ? cp[j] : cc[j];
@@ -630,11 +657,21 @@ __global__ void __launch_bounds__(kFitThreads) k_fit_em(FitDev F) {
         if (!kFull && t == 0 && k >= 1 && k <= kMaxComp) model[0] = dinf();
         return;
     }
+    const bool spec = kFull && F.full_mode == FIT_SPEC;
+    if (kFull && R.adopt) {   // the fit of this count ran beside the selection: take its result -- what this workgroup would have computed and done
+        if (t == 0) {
+            atomicAdd(F.spec_ctr, 1);
+            if (F.spec_failed[q]) atomicCAS(F.err, 0, (int)TW_ERR_FIT);
+            else for (int j = 0; j < kMaxComp * 3; j++) F.mix_p[q * kMaxComp * 3 + j] = F.spec_p[q * kMaxComp * 3 + j];
+        }
+        return;
+    }
+    if (kFull && F.full_mode == FIT_ADOPT && t == 0) atomicAdd(F.spec_ctr + 1, 1);
     const int nt = blockDim.x;
     const double* xv = F.uval + R.row;      // distinct values, ascending
     const int32_t* xa = F.ustart + R.row;   // first index of each value in the sorted row
     const double dn = (double)n;
-    const double* seed = F.centres + (q * kMaxComp + (k - 1)) * (kMaxComp + 1);
+    const double* seed = spec ? F.spec_centres + q * (kMaxComp + 1) : F.centres + (q * kMaxComp + (k - 1)) * (kMaxComp + 1);
     const double mean = k > 1 ? seed[0] : 0.0;
     for (int r = t; r < uniq && r < kRunCache; r += nt) { run_x[r] = xv[r]; run_c[r] = (r + 1 < uniq ? xa[r + 1] : n) - xa[r]; }
     __syncthreads();
@@ -811,12 +848,14 @@ __global__ void __launch_bounds__(kFitThreads) k_fit_em(FitDev F) {
     }
     if (t != 0) return;
     if (kFull) {
-        if (failed) { atomicCAS(F.err, 0, (int)TW_ERR_FIT); return; }
+        if (spec) F.spec_failed[q] = failed ? 1 : 0;
+        if (failed) { if (!spec) atomicCAS(F.err, 0, (int)TW_ERR_FIT); return; }
+        double* out = (spec ? F.spec_p : F.mix_p) + q * kMaxComp * 3;
 #pragma unroll
         for (int j = 0; j < kMaxComp; j++) {
-            F.mix_p[(q * kMaxComp + j) * 3 + 0] = j < k ? pw[j] : 0.0;
-            F.mix_p[(q * kMaxComp + j) * 3 + 1] = j < k ? pm[j] : 0.0;
-            F.mix_p[(q * kMaxComp + j) * 3 + 2] = j < k ? 1.0 / sqrt(pv[j]) : 0.0;
+            out[j * 3 + 0] = j < k ? pw[j] : 0.0;
+            out[j * 3 + 1] = j < k ? pm[j] : 0.0;
+            out[j * 3 + 2] = j < k ? 1.0 / sqrt(pv[j]) : 0.0;
         }
     } else {
         model[0] = failed ? dinf() : -2.0 * lower * dn + (double)(3 * k - 1) * log(dn);   // GaussianMixture.bic

@@ -845,3 +845,11 @@ class Engine(object):
         ms = np.zeros(33, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 33))
         return int(ms[32])
+
+    def fit_spec(self):
+        """(hits, misses) of the last refit (tw_get_timing slots 35, 36): rows whose final fit ran beside the model selection and was
+        adopted -- the row selected the largest admissible count, min(5, #distinct) -- and rows that were fitted after the selection.
+        (0, 0) = TW_FIT_SPEC=0, or no refit yet."""
+        ms = np.zeros(37, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 37))
+        return int(ms[35]), int(ms[36])

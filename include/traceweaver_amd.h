@@ -199,6 +199,16 @@ int tw_set_fit_seed(tw_engine *e, uint32_t seed);
 int tw_fit_rows(tw_engine *e, int32_t *max_n);
 int tw_fit_mixtures_tape(tw_engine *e, const double *tape, int64_t tape_len, const int64_t *slot_off);
 
+/* The order tables of the last refit (TW_FIT_ORDER, default 1): its launches hand their fits out longest first -- by distinct
+ * values x components of the (row, count) a workgroup serves -- through permutations of their grids, built on the host from the
+ * rows' distinct-value counts.  order_seed [4 n_slots] and order_em [5 n_slots]: workgroup b of the model selection's seeding /
+ * EM launch serves block order[b] = (5 - count) * n_slots + slot; order_row [n_slots]: the rows of the final fits' launches.
+ * Live blocks first, by key descending, then count descending, then slot ascending; blocks without a fit last, in index order.
+ * Which workgroup makes a fit does not enter the fit: the mixtures are the same bits under TW_FIT_ORDER=0.  *present = 0 (and
+ * nothing written): that refit ran in grid order, or the resident mixtures were set with tw_set_mixtures and come from no refit.
+ * For tests and measurements. */
+int tw_get_fit_order(tw_engine *e, int32_t *order_seed, int32_t *order_em, int32_t *order_row, int32_t *present);
+
 /* The mixture tables currently resident (layout of tw_set_mixtures). */
 int tw_get_mixtures(tw_engine *e, int32_t *mix_n, double *mix_p);
 
@@ -257,7 +267,8 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * ms[32] (a count): class stages of the last pass that were queued behind the stage gate (TW_STAGE_GATE), 0 = the pass was not gated.
  * The last tw_compare_cohorts (HIP events): ms[33] ranks, pool and observed statistics, ms[34] the permutation walk (0 without one).
  * ms[35], ms[36] (counts): rows of the last refit whose final fit ran beside the model selection and was adopted (the row selected
- * the largest admissible count, min(5, #distinct)) / rows that were fitted after the selection; both 0 under TW_FIT_SPEC=0. */
+ * the largest admissible count, min(5, #distinct)) / rows that were fitted after the selection; both 0 under TW_FIT_SPEC=0.
+ * ms[37]: host wall clock the last refit spent building and queueing its order tables (tw_get_fit_order; 0 under TW_FIT_ORDER=0). */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------

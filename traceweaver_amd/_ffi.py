@@ -132,7 +132,7 @@ TW_CMP_MAX_Q = 8
 TW_CMP_MAX_PAIRS = 64
 
 EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_pass1", "tw_get_gaps", "tw_set_gaps",
-           "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
+           "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_fit_order", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
            "tw_assign_service", "tw_find_order", "tw_order_bound", "tw_order_stage", "tw_order_load", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
            "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles",
@@ -176,6 +176,7 @@ def load(path=None):
     lib.tw_set_fit_seed.argtypes = [vp, ctypes.c_uint32]
     lib.tw_fit_rows.argtypes = [vp, vp]
     lib.tw_fit_mixtures_tape.argtypes = [vp, vp, ctypes.c_int64, vp]
+    lib.tw_get_fit_order.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32)]
     lib.tw_get_mixtures.argtypes = [vp, vp, vp]
     lib.tw_get_results.argtypes = [vp, ctypes.c_int, ctypes.POINTER(Results)]
     lib.tw_get_gauss_params.argtypes = [vp, vp]

@@ -10,6 +10,7 @@
 #include <functional>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -71,6 +72,7 @@ struct Knobs {
     int fit_sort;             // TW_FIT_SORT=1: the gap rows go the sort route (fit_prepare)
     int stage_gate;           // TW_STAGE_GATE: the stages of the shorter classes wait for the critical class' tile kernel (launch_class_stage; 0 = they do not: A/B runs, bisection)
     int fit_spec;             // TW_FIT_SPEC: the final fit of the likeliest count runs beside the model selection (fit_run; 0 = after it, five launches on one stream: A/B runs, bisection)
+    int fit_order;            // TW_FIT_ORDER: the refit's launches hand their fits out longest first, by order tables built on the host (fit_order; 0 = in grid order: A/B runs, bisection)
 };
 
 Knobs read_knobs() {
@@ -101,6 +103,7 @@ Knobs read_knobs() {
     K.fit_sort = env_int("TW_FIT_SORT", 0);
     K.stage_gate = env_int("TW_STAGE_GATE", 1);
     K.fit_spec = env_int("TW_FIT_SPEC", 1) != 0 ? 1 : 0;
+    K.fit_order = env_int("TW_FIT_ORDER", 1) != 0 ? 1 : 0;
     return K;
 }
 
@@ -199,8 +202,13 @@ struct tw_engine {
     int8_t wide_pass1[kMaxEp + 1] = {};     // per class: -1 not known, 0 / 1 = the first enumeration of pass 1 listed no / some span with wide windows
     int32_t split_pass1[kMaxEp + 1] = {};   // per class: spans the first enumeration of pass 1 cut into parts (-1 not known): sizes the merge launch of pass 2 (a guess that only costs time when wrong)
     bool pass1_done = false;                // tw_run_pass1 has run on the resident batch (tw_run_pass2 reads its cut-offs, windows, tuple counts)
-    std::vector<int32_t> fit_max_n;         // per slot min(5, #unique), 0 = nothing to fit (host copy, tw_fit_rows)
-    bool fit_max_n_valid = false;           // ... of the rows that are prepared now (cleared with fit_prepared)
+    std::vector<int32_t> fit_rows_h;        // host copy of fit_row_n, fit_row_uniq and the refusal flag of k_fit_runs, one block on the device too (fit_prepare): tw_fit_rows and the order tables read it
+    bool fit_rows_h_valid = false;          // ... of the rows that are prepared now (cleared with fit_prepared)
+    // The order tables of the last refit (fit_order; TW_FIT_ORDER): permutations of the grids of k_fit_seed<false> [4 n_slots] and
+    // k_fit_em<false> [5 n_slots] and of the rows [n_slots] for the four kFull launches, behind one another; empty = grid order
+    std::vector<int32_t> fit_order_h;
+    int32_t* fit_order_dev = nullptr;
+    double fit_order_host_ms = 0.0;         // host wall clock of building them (tw_get_timing slot 37)
     Mt19937 fit_rng;                        // stream of tw_fit_mixtures (tw_set_fit_seed; restarted by every tw_load_batch)
     uint32_t fit_seed = 0;
     int32_t* slot_unit = nullptr;
@@ -1207,7 +1215,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     if (b->batch_size <= 0 || b->batch_size_mis <= 0) return fail(e, TW_ERR_ARG, "batch sizes must be positive");
     free_all(e);
     e->fit_rng = Mt19937(e->fit_seed);   // a batch's refit does not depend on what the engine solved before
-    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
+    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_rows_h_valid = false;
     e->units.assign((size_t)b->n_units, UnitDev{});
     e->tiles.clear();
     e->gs_off_h.assign((size_t)b->n_units, 0);
@@ -1457,12 +1465,14 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     DEV_ALLOC(e->agg_pair, P.n_tiles); DEV_ALLOC(e->agg_i32, P.n_tiles); DEV_ALLOC(e->agg_i32b, P.n_tiles);
     DEV_ALLOC(e->seg_in, (int64_t)seg_in.size()); DEV_ALLOC(e->seg_out, (int64_t)seg_out.size());
     DEV_ALLOC(e->gaps_sorted, gaps); DEV_ALLOC(e->fit_models, slots * kMaxComp * kModelStride);
-    DEV_ALLOC(e->fit_uval, gaps); DEV_ALLOC(e->fit_ustart, gaps); DEV_ALLOC(e->fit_row_n, slots); DEV_ALLOC(e->fit_row_uniq, slots);
+    DEV_ALLOC(e->fit_uval, gaps); DEV_ALLOC(e->fit_ustart, gaps); DEV_ALLOC(e->fit_row_n, 2 * slots + 1);   // samples, distinct values (fit_row_uniq, set behind arena_commit) and the refusal flag of k_fit_runs: one copy to the host, fit_prepare
     DEV_ALLOC(e->fit_tape, slots * kFitRowTape); DEV_ALLOC(e->fit_tape_off, slots); DEV_ALLOC(e->fit_tape100, kMaxComp * 13);
     e->fit_tape_cap = slots * kFitRowTape;
     DEV_ALLOC(e->fit_centres, slots * kMaxComp * (kMaxComp + 1));
     DEV_ALLOC(e->fit_spec_centres, slots * (kMaxComp + 1)); DEV_ALLOC(e->fit_spec_p, slots * kMaxComp * 3);
     DEV_ALLOC(e->fit_spec_failed, slots); DEV_ALLOC(e->fit_spec_ctr, 2);
+    DEV_ALLOC(e->fit_order_dev, slots * (2 * kMaxComp));
+    e->fit_order_h.clear();
     DEV_ALLOC(e->slot_unit, slots); DEV_ALLOC(e->slot_scored, slots);
     DEV_ALLOC(e->seg_gap, (int64_t)seg_gap_h.size()); DEV_ALLOC(e->seg_gap_end, (int64_t)seg_gap_end_h.size()); DEV_ALLOC(e->seg_gap_dst, (int64_t)seg_gap_dst_h.size());
     e->comp_cap = std::max(std::max(n_in_total, n_out_total), e->n_gap_scored);
@@ -1498,6 +1508,7 @@ int tw_load_batch(tw_engine* e, const tw_batch* b, int spans_on_device) {
     }
     rc = arena_commit(e);
     if (rc != TW_OK) return rc;
+    e->fit_row_uniq = e->fit_row_n + slots;   // (one block; the arena has placed it only now)
     if (e->skip_mode) {
         for (int u = 0; u < b->n_units; u++) {
             SkipUnitDev K{};
@@ -1555,7 +1566,7 @@ int tw_run_pass1(tw_engine* e) {
     HIPCHK(hipSetDevice(e->device));
     drop_forest(e);   // (the parent arrays a stitched forest was made from are overwritten)
     const int rc = run_pass(e, 1);
-    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
+    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_rows_h_valid = false;
     if (rc == TW_OK) { e->state = ST_PASS1; e->pass1_done = true; }
     return rc;
 }
@@ -1577,7 +1588,7 @@ int tw_set_gaps(tw_engine* e, const double* gaps) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->P.gaps, gaps, sizeof(double) * e->n_gaps, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
+    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_rows_h_valid = false;
     e->state = ST_PASS1;
     return TW_OK;
 }
@@ -1598,7 +1609,7 @@ int tw_set_gaps_device(tw_engine* e, const double* dev_gaps) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->P.gaps, dev_gaps, sizeof(double) * e->n_gaps, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_max_n_valid = false;
+    e->fit_prepared = false; e->fit_runs_pending = false; e->fit_rows_h_valid = false;
     e->state = ST_PASS1;
     return TW_OK;
 }
@@ -1616,6 +1627,7 @@ int tw_set_mixtures(tw_engine* e, const int32_t* mix_n, const double* mix_p) {
     hipLaunchKernelGGL(k_mix_consts, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->mix_p_dev, (const int32_t*)e->mix_n_dev, (const int32_t*)e->slot_unit, e->P.units, e->mix_c_dev, total);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
+    e->fit_order_h.clear();   // (these mixtures come from no refit: tw_get_fit_order reports none)
     e->state = ST_MIX;
     return TW_OK;
 }
@@ -1640,7 +1652,7 @@ FitDev fit_dev(tw_engine* e) {
 int fit_prepare_launch(tw_engine* e) {
     e->fit_runs_pending = false;
     if (e->fit_prepared || e->K.fit_sort != 0) return TW_OK;
-    int32_t* flag = (int32_t*)e->key_acc;
+    int32_t* flag = e->fit_row_n + 2 * e->n_slots;
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int32_t), e->stream));
 #ifdef TW_HOST_EMULATION
     const int runs_threads = e->K.coop;
@@ -1652,18 +1664,23 @@ int fit_prepare_launch(tw_engine* e) {
     e->fit_runs_pending = true;
     return TW_OK;
 }
+// The rows' sample and distinct-value counts for the host (tw_fit_rows, fit_order), with the refusal flag of k_fit_runs behind them
+// (the three are one block): one copy queued behind the kernel that leaves them, where the hash route copied the flag alone.
+int fit_rows_to_host(tw_engine* e) {
+    e->fit_rows_h.resize((size_t)(2 * e->n_slots + 1));
+    HIPCHK(hipMemcpyAsync(e->fit_rows_h.data(), e->fit_row_n, sizeof(int32_t) * e->fit_rows_h.size(), hipMemcpyDeviceToHost, e->stream));
+    return TW_OK;
+}
 int fit_prepare(tw_engine* e) {
     if (e->fit_prepared) return TW_OK;
     if (e->K.fit_sort == 0) {
         if (!e->fit_runs_pending) { int rl = fit_prepare_launch(e); if (rl != TW_OK) return rl; }
         e->fit_runs_pending = false;
-        int32_t* flag = (int32_t*)e->key_acc;
-        int32_t refused = 0;
-        HIPCHK(hipMemcpyAsync(&refused, flag, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        TWCHK(fit_rows_to_host(e));
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (!refused) {
+        if (!e->fit_rows_h[(size_t)(2 * e->n_slots)]) {   // no row was refused
             e->fit_prepared = true;
-            e->fit_max_n_valid = false;
+            e->fit_rows_h_valid = true;
             return TW_OK;
         }
     }
@@ -1693,9 +1710,59 @@ int fit_prepare(tw_engine* e) {
 #endif
     hipLaunchKernelGGL(k_fit_compress, dim3((unsigned)e->n_slots), dim3(compress_threads), 0, e->stream, F);
     HIPCHK(hipGetLastError());
+    TWCHK(fit_rows_to_host(e));   // (the rare route: a wait of its own)
+    HIPCHK(hipStreamSynchronize(e->stream));
     e->fit_prepared = true;
-    e->fit_max_n_valid = false;   // (the host copy of the rows' distinct-value counts belongs to the rows prepared before)
+    e->fit_rows_h_valid = true;
     return TW_OK;
+}
+
+// The order tables of a refit (TW_FIT_ORDER).  A workgroup is one whole fit, and a fit's length goes with distinct values x
+// components: 10-30 times as long on a row of 10^4 distinct values as on one of 10^3.  The hardware hands workgroups out in index
+// order, so in grid order the long fits of the smaller counts start late and end the launch alone; longest first, the span of a
+// launch approaches work / CUs.  Every table is a full permutation of its grid -- a dead workgroup keeps its side effects
+// (k_fit_em<false> marks a fit that is not made) --: key = distinct values x count of a live block (fit_row's predicate), -1 of a dead
+// one; by key descending, then count descending, then slot ascending, so dead blocks come last in index order.
+void fit_order(const int32_t* row_uniq, const int32_t* row_n, int64_t n_slots, std::vector<int32_t>& out) {
+    out.resize((size_t)(n_slots * 2 * kMaxComp));
+    // The rows with a fit, by distinct values descending, then slot ascending: the order of the kFull launches (their key, distinct
+    // values x fit_spec_k, grows with the distinct values), and per count k the rows of that count's live blocks -- a prefix, the
+    // rows of at least k distinct values -- in the order of their keys.  The model selection's tables merge the counts' lists: the
+    // largest key next, of equal keys the larger count; a row sort and a merge of five lists instead of a sort of all blocks.
+    // (A row has a fit <=> it has samples: k_fit_runs and k_fit_compress leave row_n = row_uniq = 0 for a slot that is not scored, so
+    // fit_row's slot_scored is implied here.)
+    std::vector<int32_t> rows;
+    rows.reserve((size_t)n_slots);
+    for (int64_t q = 0; q < n_slots; q++)
+        if (row_n[q] > 0 && row_uniq[q] >= 1) rows.push_back((int32_t)q);
+    std::stable_sort(rows.begin(), rows.end(), [&](int32_t a, int32_t b) { return row_uniq[a] > row_uniq[b]; });
+    int64_t len[kMaxComp + 1];   // rows of at least k distinct values
+    for (int k = 1; k <= kMaxComp; k++)
+        len[k] = std::partition_point(rows.begin(), rows.end(), [&](int32_t q) { return row_uniq[q] >= k; }) - rows.begin();
+    const auto merge = [&](int32_t* tab, int k_min) {   // the grid of counts 5..k_min: block (5 - k) * n_slots + q
+        int64_t at = 0, pos[kMaxComp + 1] = {};
+        for (;;) {
+            int best = 0;
+            int64_t best_key = -1;
+            for (int k = kMaxComp; k >= k_min; k--) {
+                if (pos[k] >= len[k]) continue;
+                const int64_t key = (int64_t)row_uniq[rows[(size_t)pos[k]]] * k;
+                if (key > best_key) { best_key = key; best = k; }
+            }
+            if (best == 0) break;
+            tab[at++] = (int32_t)((kMaxComp - best) * n_slots + rows[(size_t)pos[best]++]);
+        }
+        for (int k = kMaxComp; k >= k_min; k--)   // the blocks without a fit, in index order
+            for (int64_t q = 0; q < n_slots; q++)
+                if (!(row_n[q] > 0 && k <= row_uniq[q])) tab[at++] = (int32_t)((kMaxComp - k) * n_slots + q);
+    };
+    merge(out.data(), 2);                                  // k_fit_seed<false>
+    merge(out.data() + n_slots * (kMaxComp - 1), 1);       // k_fit_em<false>
+    int32_t* tab = out.data() + n_slots * (2 * kMaxComp - 1);
+    int64_t at = 0;
+    for (const int32_t q : rows) tab[at++] = q;
+    for (int64_t q = 0; q < n_slots; q++)
+        if (!(row_n[q] > 0 && row_uniq[q] >= 1)) tab[at++] = (int32_t)q;
 }
 
 // The fits themselves; the tape and the slots' offsets are resident in e->fit_tape / e->fit_tape_off.
@@ -1712,6 +1779,20 @@ int fit_run(tw_engine* e) {
     HIPCHK(hipMemsetAsync(e->P.err, 0, sizeof(int32_t), e->stream));
     FitDev F = fit_dev(e);
     const int threads = e->K.coop >= 64 ? kFitThreads : e->K.coop;
+    // The order tables (fit_order), uploaded with the tapes: null = every launch in grid order
+    const int32_t *order_seed = nullptr, *order_em = nullptr, *order_row = nullptr;
+    e->fit_order_h.clear();
+    e->fit_order_host_ms = 0.0;
+    if (e->K.fit_order != 0) {
+        if (!e->fit_rows_h_valid) return fail(e, TW_ERR_STATE, "refit: the rows' counts are not on the host (fit_prepare leaves them there)");
+        const auto h0 = std::chrono::steady_clock::now();
+        fit_order(e->fit_rows_h.data() + e->n_slots, e->fit_rows_h.data(), e->n_slots, e->fit_order_h);
+        HIPCHK(hipMemcpyAsync(e->fit_order_dev, e->fit_order_h.data(), sizeof(int32_t) * e->fit_order_h.size(), hipMemcpyHostToDevice, e->stream));
+        e->fit_order_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+        order_seed = e->fit_order_dev;
+        order_em = order_seed + e->n_slots * (kMaxComp - 1);
+        order_row = order_em + e->n_slots * kMaxComp;
+    }
     // The second stream of the refit is the stream of the batch's first class, idle between the passes: every batch has one
     // (tw_load_batch), and its work is joined to the engine's stream below.  A stream of the refit's own, created in tw_create, took
     // the hardware queue that the class streams created after it would have had (the runtime deals a process' streams onto four
@@ -1736,13 +1817,17 @@ int fit_run(tw_engine* e) {
         HIPCHK(hipStreamWaitEvent(side, e->fit_fork, 0));
         FitDev S = F;
         S.full_mode = FIT_SPEC;
+        S.order = order_row;
         hipLaunchKernelGGL(k_fit_seed<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, side, S);
         hipLaunchKernelGGL(k_fit_em<true>, dim3((unsigned)e->n_slots), dim3(threads), 0, side, S);
         HIPCHK(hipEventRecord(e->fit_join, side));
     }
     // Model selection: two launches over all counts, the largest count (the longest fits) first (fit_row)
+    F.order = order_seed;
     hipLaunchKernelGGL(k_fit_seed<false>, dim3((unsigned)(e->n_slots * (kMaxComp - 1))), dim3(threads), 0, e->stream, F);
+    F.order = order_em;
     hipLaunchKernelGGL(k_fit_em<false>, dim3((unsigned)(e->n_slots * kMaxComp)), dim3(threads), 0, e->stream, F);
+    F.order = order_row;
     hipLaunchKernelGGL(k_fit_select, dim3((unsigned)((e->n_slots + 63) / 64)), dim3(64), 0, e->stream, F);
     if (spec) {   // rows that selected the count fitted ahead adopt its result (k_fit_em), the others are fitted now
         HIPCHK(hipStreamWaitEvent(e->stream, e->fit_join, 0));
@@ -1790,12 +1875,20 @@ int tw_fit_rows(tw_engine* e, int32_t* max_n) {
     HIPCHK(hipSetDevice(e->device));
     rc = fit_prepare(e);
     if (rc != TW_OK) return rc;
-    std::vector<int32_t> uniq((size_t)e->n_slots);
-    HIPCHK(hipMemcpyAsync(uniq.data(), e->fit_row_uniq, sizeof(int32_t) * e->n_slots, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->fit_max_n.assign((size_t)e->n_slots, 0);
-    for (int64_t q = 0; q < e->n_slots; q++) max_n[q] = e->fit_max_n[(size_t)q] = std::min<int32_t>(uniq[(size_t)q], kMaxComp);
-    e->fit_max_n_valid = true;
+    for (int64_t q = 0; q < e->n_slots; q++) max_n[q] = std::min<int32_t>(e->fit_rows_h[(size_t)(e->n_slots + q)], kMaxComp);   // (fit_prepare's host copy)
+    return TW_OK;
+}
+
+int tw_get_fit_order(tw_engine* e, int32_t* order_seed, int32_t* order_em, int32_t* order_row, int32_t* present) {
+    if (e == nullptr || order_seed == nullptr || order_em == nullptr || order_row == nullptr || present == nullptr) return TW_ERR_ARG;
+    if (e->state < ST_MIX) return fail(e, TW_ERR_STATE, "tw_get_fit_order: no refit has run on the resident batch");
+    *present = e->fit_order_h.empty() ? 0 : 1;
+    if (*present) {
+        const size_t ns = (size_t)e->n_slots, k = (size_t)kMaxComp;
+        std::copy_n(e->fit_order_h.data(), ns * (k - 1), order_seed);
+        std::copy_n(e->fit_order_h.data() + ns * (k - 1), ns * k, order_em);
+        std::copy_n(e->fit_order_h.data() + ns * (2 * k - 1), ns, order_row);
+    }
     return TW_OK;
 }
 
@@ -1804,14 +1897,11 @@ int tw_fit_mixtures_tape(tw_engine* e, const double* tape, int64_t tape_len, con
     int rc = fit_check_state(e, "tw_fit_mixtures_tape");
     if (rc != TW_OK) return rc;
     HIPCHK(hipSetDevice(e->device));
-    if (!e->fit_prepared || !e->fit_max_n_valid || e->fit_max_n.size() != (size_t)e->n_slots) {
-        std::vector<int32_t> tmp((size_t)e->n_slots);
-        rc = tw_fit_rows(e, tmp.data());
-        if (rc != TW_OK) return rc;
-    }
+    rc = fit_prepare(e);
+    if (rc != TW_OK) return rc;
     static const int need[kMaxComp + 1] = {0, 1, 4, 11, 21, 34};
     for (int64_t q = 0; q < e->n_slots; q++) {
-        const int m = e->fit_max_n[(size_t)q];
+        const int m = std::min<int32_t>(e->fit_rows_h[(size_t)(e->n_slots + q)], kMaxComp);
         if (m > 0 && (slot_off[q] < 0 || slot_off[q] + need[m] > tape_len))
             return fail(e, TW_ERR_ARG, "tw_fit_mixtures_tape: the tape does not hold the draws of slot " + std::to_string(q));
     }
@@ -1937,6 +2027,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 32) ms[32] = (double)e->gate_waits;                           // class stages of the last pass that were queued behind the stage gate
     for (int i = 0; i < 2 && 33 + i < n; i++) ms[33 + i] = e->cm_ms[i];   // the last tw_compare_cohorts
     for (int i = 0; i < 2 && 35 + i < n; i++) ms[35 + i] = (double)e->fit_spec_count[i];   // the last refit: rows that adopted the fit made ahead / that were fitted after the selection
+    if (n > 37) ms[37] = e->fit_order_host_ms;                            // ... and the host's time for its order tables
     return TW_OK;
 }
 

@@ -86,6 +86,7 @@ struct FitDev {
     double* spec_p;         // [n_slots][kMaxComp][3] its result, laid out like mix_p ...
     int32_t* spec_failed;   // [n_slots] ... or 1: it ended in a covariance <= 0 (an error only if the row selects that count)
     int32_t* spec_ctr;      // [2] rows of the last refit that adopted their speculative fit / that were fitted after the selection
+    const int32_t* order;   // a permutation of the launch's grid, the longest fits first (fit_order, tw_engine.hip), or null: workgroup b serves block order[b]
 };
 enum { FIT_FINAL = 0,   // k = mix_n[q], results in centres / mix_p (the refit without speculation)
        FIT_SPEC = 1,    // k = fit_spec_k(q), results in spec_centres / spec_p / spec_failed; runs beside the model selection
@@ -328,18 +329,20 @@ __device__ __forceinline__ int fit_spec_k(const FitDev& F, int64_t q) {
 }
 // Which (row, component count) a workgroup serves.  Model selection: the fits with the most components first (they run
 // longest), `skip1` leaves k = 1 out (k-means of one cluster is no work); refit: k = the selected count, or the speculative
-// one (F.full_mode; a FIT_SPEC launch runs beside k_fit_select and does not read mix_n).
+// one (F.full_mode; a FIT_SPEC launch runs beside k_fit_select and does not read mix_n).  With an order table the workgroup
+// takes the place of another block of the same grid (the longest fits get the first workgroups); nothing else changes.
 template <bool kFull>
 __device__ __forceinline__ FitRow fit_row(const FitDev& F, bool skip1) {
     FitRow R;
-    R.q = kFull ? (int64_t)blockIdx.x : (int64_t)(blockIdx.x % F.n_slots);
+    const unsigned b = F.order ? (unsigned)F.order[blockIdx.x] : blockIdx.x;
+    R.q = kFull ? (int64_t)b : (int64_t)(b % F.n_slots);
     R.adopt = false;
     if (kFull) {
         const int sk = F.full_mode != FIT_FINAL ? fit_spec_k(F, R.q) : 0;
         R.k = F.full_mode == FIT_SPEC ? sk : F.mix_n[R.q];
         R.adopt = F.full_mode == FIT_ADOPT && R.k == sk;
     } else {
-        R.k = kMaxComp - (int)(blockIdx.x / F.n_slots);
+        R.k = kMaxComp - (int)(b / F.n_slots);
     }
     const UnitDev& U = F.units[F.slot_unit[R.q]];
     R.n_all = U.n_in;

@@ -263,6 +263,16 @@ class Engine(object):
         self._check(self._lib.tw_fit_rows(self._h, _vp(m)))
         return [m[self._slot_off[k]:self._slot_off[k + 1]] for k in range(len(self.units))]
 
+    def fit_order(self):
+        """The order tables of the last refit (tw_get_fit_order): (order_seed [4 S], order_em [5 S], order_row [S]) for the batch's S
+        slots -- block (5 - count) * S + slot, or the row, that each workgroup of the refit's launches served, the longest fits first --
+        or None: the refit ran in grid order (TW_FIT_ORDER=0)."""
+        s = int(self._slot_off[-1])
+        seed, em, row = np.empty(4 * s, dtype=np.int32), np.empty(5 * s, dtype=np.int32), np.empty(s, dtype=np.int32)
+        present = ctypes.c_int32(0)
+        self._check(self._lib.tw_get_fit_order(self._h, _vp(seed), _vp(em), _vp(row), ctypes.byref(present)))
+        return (seed, em, row) if present.value else None
+
     def mixtures(self):
         """Per unit (mix_n [nslot], mix_p [nslot, 5, 3]) currently resident on the device."""
         n = np.empty(int(self._slot_off[-1]), dtype=np.int32)

@@ -268,7 +268,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * The last tw_compare_cohorts (HIP events): ms[33] ranks, pool and observed statistics, ms[34] the permutation walk (0 without one).
  * ms[35], ms[36] (counts): rows of the last refit whose final fit ran beside the model selection and was adopted (the row selected
  * the largest admissible count, min(5, #distinct)) / rows that were fitted after the selection; both 0 under TW_FIT_SPEC=0.
- * ms[37]: host wall clock the last refit spent building and queueing its order tables (tw_get_fit_order; 0 under TW_FIT_ORDER=0). */
+ * ms[37]: host wall clock the last refit spent building and queueing its order tables (tw_get_fit_order; 0 under TW_FIT_ORDER=0).
+ * The history (HIP events): ms[38] plan and ms[39] merge kernel of the last tw_history_push / tw_history_merge, ms[40] quantiles and
+ * histogram of the last tw_history_distributions, ms[41], ms[42] observed statistics and permutation walk of the last tw_history_compare. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -649,6 +651,64 @@ typedef struct {
     int64_t *perm_ge_ks, *perm_ge_u, *perm_ge_q;
 } tw_cohort_comparison;
 int tw_compare_cohorts(tw_engine *e, const tw_cmp_query *q, const tw_cohort_comparison *out, int64_t *summary4);
+
+/* ---- the distributions of batch after batch: a history on the device (csrc/tw_hist.h) -----------------------------
+ *
+ * Replaces: the pickle of latency lists the delay-culprit query writes per run and the reading of two runs' files side by
+ * side, src/query_engine/delay_culprit.py:32-97 -- yesterday's deployment against today's, a p99 over an hour of batches.
+ * tw_latency_distributions and tw_compare_cohorts cover one engine's batch; the history keeps what they work on -- every
+ * segment's values ascending, its count and its sum -- beyond the batch, for cohorts of its own, and answers the same two
+ * queries over it.  It is device state of the engine and holds copies: tw_load_batch, tw_set_span_rows, tw_stitch_traces,
+ * tw_attribute_traces, tw_set_row_groups, tw_set_row_cohorts, a new pass and whatever else drops the forest leave it alone, and
+ * none of the calls below drops or rewrites anything of the resident batch.  Only tw_history_reset and tw_destroy end it.
+ *
+ * Definitions:
+ *   history    C_h cohorts x per = 3 G + 1 segments, index h * per + m * G + g, the trace-latency segment last within a cohort
+ *              (the layout of tw_latency_distributions).  H[h, r]: the values ascending in signed order; seg_count; seg_sum in
+ *              two's complement, wrapping.  Empty after tw_create and tw_history_reset: C_h = 0 and G open.  The first push or
+ *              merge fixes G = n_groups; a later one with another n_groups is TW_ERR_ARG.
+ *   push       the source is the sorted items of the last tw_attribute_traces, exactly those tw_latency_distributions defines
+ *              (built here when they are not resident, as tw_compare_cohorts does, and left resident).  cohort_map [n_map],
+ *              n_map = the batch's n_cohorts: source cohort c goes to history cohort cohort_map[c] >= 0, -1 = not kept, NULL =
+ *              the identity.  The entries >= 0 must be distinct: a push merges two sorted runs per segment, never more.
+ *              Afterwards C_h = max(C_h, 1 + max cohort_map); cohorts nobody was pushed into hold empty segments.  For every c
+ *              with h = cohort_map[c] >= 0 and every r < per the new H[h, r] is the ascending multiset union of the old H[h, r]
+ *              and the source's segment (c, r); counts and sums are added.  Every other segment is unchanged.
+ *   merge      the same from host arrays -- a saved history, another rank's, another engine's tw_latency_distributions output:
+ *              n_cohorts_src x (3 n_groups + 1) segments, seg_off_src [n_seg + 1] (first 0, non-decreasing: checked on the host),
+ *              values_src [seg_off_src[n_seg]], every segment ascending (checked on the device before anything is merged).
+ *              Counts are the differences of the offsets, sums are taken on the device.
+ *   summary4   push, merge: items added, items held afterwards, C_h afterwards, pushes and merges since the reset.
+ *              tw_history_distributions: items held, non-empty segments, C_h, pushes and merges since the reset.
+ *              tw_history_compare: as tw_compare_cohorts.
+ *   info       out6 = C_h, G, segments (C_h * per), items held, pushes and merges since the reset, capacity of the value buffer
+ *              in items.  All 0 for an empty history (tw_history_reset frees the buffers).
+ *
+ * tw_history_distributions: the outputs, conventions and argument checks of tw_latency_distributions over the history's
+ * segments (n_seg = C_h * per, n_items = items held; out->tree_cohort is ignored); with n_q = n_edges = 0 it is the call that
+ * reads the history back.  tw_history_compare: the definitions, limits and argument checks of tw_compare_cohorts over the
+ * history's segments, pairs in [0, C_h): batch against batch.  Both run the kernels of their namesakes on a view of the history.
+ *
+ * TW_ERR_STATE: tw_history_push before a tw_attribute_traces on the current forest; the two queries on an empty history.
+ * TW_ERR_ARG: n_map != the batch's n_cohorts; a map entry below -1; two equal entries >= 0; another n_groups than the history's;
+ * n_cohorts_src < 1, n_groups < 1; offsets that do not start at 0 or decrease; a source segment that does not ascend; the
+ * argument errors of the namesakes.  TW_ERR_UNSUPPORTED: C_h * per (or the source's segments) > 2^24.  TW_ERR_DEVICE: no memory
+ * for a buffer.  A call that is refused or fails leaves the history exactly as it was: a push merges into the value buffer that
+ * is not in use (two at most; a buffer grows to at least twice its size) and the two are swapped when nothing has failed.
+ * Everything runs on the engine's stream; integers throughout but the one product probs[j] * n of the quantile index; the only
+ * atomics are the integer adds of the merge's source sums: results do not depend on scheduling.
+ * Limits: every push rewrites the whole store (16 B per item held afterwards); no tiers, no eviction, no decay; ranks merge
+ * through the host (tw_history_merge), there is no collective.  Timing: tw_get_timing slots 38..42 (HIP events, ms): 38 plan
+ * (for a merge with the source's check; the host's read of the plan's counters and the growth of a buffer, where there is one, fall
+ * between its events), 39 merge kernel -- of the last push or merge; 40 quantiles and histogram of the last
+ * tw_history_distributions; 41, 42 observed statistics and permutation walk of the last tw_history_compare. */
+int tw_history_reset(tw_engine *e);
+int tw_history_push(tw_engine *e, int32_t n_map, const int32_t *cohort_map, int64_t *summary4);
+int tw_history_merge(tw_engine *e, int32_t n_cohorts_src, int32_t n_groups, const int64_t *seg_off_src, const int64_t *values_src,
+                     const int32_t *cohort_map, int64_t *summary4);
+int tw_history_info(tw_engine *e, int64_t *out6);
+int tw_history_distributions(tw_engine *e, const tw_dist_query *q, const tw_distributions *out, int64_t *summary4);
+int tw_history_compare(tw_engine *e, const tw_cmp_query *q, const tw_cohort_comparison *out, int64_t *summary4);
 
 /* ---- traces grouped by call-graph signature (csrc/tw_sig.h) -------------------------------------------------------
  *

@@ -136,6 +136,7 @@ EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_
            "tw_assign_service", "tw_find_order", "tw_order_bound", "tw_order_stage", "tw_order_load", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
            "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles",
+           "tw_history_reset", "tw_history_push", "tw_history_merge", "tw_history_info", "tw_history_distributions", "tw_history_compare",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
            "tw_corpus_string", "tw_corpus_loop_origin", "tw_corpus_trace_names", "tw_corpus_span_table", "tw_corpus_build_units"]
 
@@ -201,6 +202,12 @@ def load(path=None):
     lib.tw_set_row_cohorts.argtypes = [vp, ctypes.c_int32, vp]
     lib.tw_latency_distributions.argtypes = [vp, ctypes.POINTER(DistQuery), ctypes.POINTER(Distributions), vp]
     lib.tw_compare_cohorts.argtypes = [vp, ctypes.POINTER(CmpQuery), ctypes.POINTER(CohortComparison), vp]
+    lib.tw_history_reset.argtypes = [vp]
+    lib.tw_history_push.argtypes = [vp, ctypes.c_int32, vp, vp]
+    lib.tw_history_merge.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
+    lib.tw_history_info.argtypes = [vp, vp]
+    lib.tw_history_distributions.argtypes = [vp, ctypes.POINTER(DistQuery), ctypes.POINTER(Distributions), vp]
+    lib.tw_history_compare.argtypes = [vp, ctypes.POINTER(CmpQuery), ctypes.POINTER(CohortComparison), vp]
     lib.tw_trace_signatures.argtypes = [vp, ctypes.POINTER(SigQuery), ctypes.POINTER(Signatures), vp]
     lib.tw_class_profiles.argtypes = [vp, ctypes.POINTER(ClassProfile), vp]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]

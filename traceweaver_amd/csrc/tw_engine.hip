@@ -28,6 +28,7 @@
 #include "tw_conf.h"
 #include "tw_dist.h"
 #include "tw_cmp.h"
+#include "tw_hist.h"
 #include "tw_sig.h"
 #include "tw_prof.h"
 #include "tw_order.h"
@@ -39,7 +40,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_COUNT = 29 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_COUNT = 37 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -261,6 +262,19 @@ struct tw_engine {
     DistKeyDev dist_key{};
     CmpDev M{};                             // tw_compare_cohorts (tw_cmp.h): scratch of a call (the pool, the per-row results); nothing of it
     int64_t cmp_rows_cap = 0, cmp_items_cap = 0;    // outlives the call but the buffers
+    // tw_history_* (tw_hist.h): the distributions of batch after batch.  Owned by the engine, not by a load: free_all leaves the
+    // history alone, only tw_history_reset and tw_destroy end it.  side[cur] holds it; a push merges into the other side and swaps.
+    struct HistSide {
+        int64_t* values = nullptr; int64_t cap = 0;                       // items
+        int64_t* off = nullptr; unsigned long long *count = nullptr, *sum = nullptr; int64_t seg_cap = 0;
+    } hist_side[2];
+    int hist_cur = 0;
+    int32_t hist_C = 0, hist_G = 0;          // C_h; G, 0 = open (fixed by the first push or merge after a reset)
+    int64_t hist_items = 0, hist_pushes = 0;
+    int64_t* hist_tile_off = nullptr; int32_t* hist_inv = nullptr; int64_t hist_plan_cap = 0 /* segments */, hist_inv_cap = 0;
+    unsigned long long* hist_counters = nullptr;
+    int64_t *hist_src_off = nullptr, *hist_src_values = nullptr; unsigned long long *hist_src_count = nullptr, *hist_src_sum = nullptr;
+    int64_t hist_src_seg_cap = 0, hist_src_cap = 0;   // the uploaded source of tw_history_merge
     SigDev G{};                             // tw_trace_signatures (tw_sig.h); sig_ready: the result of sig_q on the forest is resident, a further
     bool sig_ready = false, ref_set = false;        // call with the same query only copies; ref_set: the reference set, keyed by root row
     tw_sig_query sig_q{};
@@ -278,6 +292,7 @@ struct tw_engine {
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
     double cm_ms[2] = {0, 0};               // ranks, pool and observed statistics; the permutation walk
+    double hs_ms[5] = {0, 0, 0, 0, 0};      // history: plan (with the source check of a merge), merge; quantiles and histogram; observed statistics, permutation walk
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
     // tw_order_stage / tw_order_load (tw_order.h): the span table of a batch in partition-key order, staged once, and the buffers a
     // candidate's permuted copy is gathered into before tw_load_batch takes it device to device.  Owned by the engine, not by a
@@ -398,6 +413,8 @@ int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
      signature        sig_ready      tw_trace_signatures  <- forest, row groups.  Dropped by tw_score_traces (it rewrites the CONFIDENT
        result                                                bit that a query may select by) and by a call with another query
      class profile    prof_ready     tw_class_profiles    <- signature result, attribution
+     history          hist_C > 0     tw_history_push / tw_history_merge <- nothing: it holds copies.  Dropped by tw_history_reset and
+                                                             tw_destroy only (its buffers are not a load's: free_all leaves them)
    An API function drops what it is about to replace with one call, before it overwrites anything, and sets its own flag last, when
    everything has succeeded (tw_trace_signatures owns two items: its result and, with keep_reference, the reference set). */
 void drop_dist(tw_engine* e) { e->dist_ready = false; }
@@ -463,6 +480,22 @@ void order_unstage(tw_engine* e) {   // (the staged table of tw_order_stage: not
     }
     if (e->ord_seg) (void)hipFree(e->ord_seg);
     e->ord_seg = nullptr; e->ord_seg_cap = 0; e->ord_staged = false;
+}
+
+void hist_free(tw_engine* e) {   // (the history of tw_history_*: not a load's, free_all leaves it alone)
+    for (auto& side : e->hist_side) {
+        if (side.values) (void)hipFree(side.values);
+        if (side.off) (void)hipFree(side.off);
+        if (side.count) (void)hipFree(side.count);
+        if (side.sum) (void)hipFree(side.sum);
+        side = tw_engine::HistSide{};
+    }
+    void* rest[] = {e->hist_tile_off, e->hist_inv, e->hist_counters, e->hist_src_off, e->hist_src_values, e->hist_src_count, e->hist_src_sum};
+    for (void* q : rest)
+        if (q) (void)hipFree(q);
+    e->hist_tile_off = nullptr; e->hist_inv = nullptr; e->hist_counters = nullptr; e->hist_plan_cap = 0; e->hist_inv_cap = 0;
+    e->hist_src_off = e->hist_src_values = nullptr; e->hist_src_count = e->hist_src_sum = nullptr; e->hist_src_seg_cap = 0; e->hist_src_cap = 0;
+    e->hist_cur = 0; e->hist_C = 0; e->hist_G = 0; e->hist_items = 0; e->hist_pushes = 0;
 }
 
 void free_all(tw_engine* e) {
@@ -1178,6 +1211,7 @@ void tw_destroy(tw_engine* e) {
     (void)hipSetDevice(e->device);
     free_all(e);
     order_unstage(e);
+    hist_free(e);
     if (e->arena != nullptr) (void)hipFree(e->arena);
     for (int i = 0; i < EV_COUNT; i++)
         if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -2028,6 +2062,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 2 && 33 + i < n; i++) ms[33 + i] = e->cm_ms[i];   // the last tw_compare_cohorts
     for (int i = 0; i < 2 && 35 + i < n; i++) ms[35 + i] = (double)e->fit_spec_count[i];   // the last refit: rows that adopted the fit made ahead / that were fitted after the selection
     if (n > 37) ms[37] = e->fit_order_host_ms;                            // ... and the host's time for its order tables
+    for (int i = 0; i < 5 && 38 + i < n; i++) ms[38 + i] = e->hs_ms[i];   // the last tw_history_push / _merge (38, 39), _distributions (40), _compare (41, 42)
     return TW_OK;
 }
 
@@ -2876,55 +2911,73 @@ int dist_build(tw_engine* e) {
 
 }  // namespace
 
+namespace {
+
+// the checks of a tw_dist_query, and the query as the kernels read it
+int dist_query(tw_engine* e, const tw_dist_query* q, DistQueryDev& Q, const std::string& fn) {
+    if (q->n_q < 0 || q->n_q > kDistMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, fn + ": n_q outside [0, 32]");
+    if (q->n_edges < 0 || q->n_edges > kDistMaxEdges || (q->n_edges > 0 && q->edges == nullptr)) return fail(e, TW_ERR_ARG, fn + ": n_edges outside [0, 63]");
+    Q.n_q = q->n_q;
+    Q.n_edges = q->n_edges;
+    for (int j = 0; j < q->n_q; j++) {
+        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, fn + ": a prob outside [0, 1]");
+        Q.probs[j] = q->probs[j];
+    }
+    for (int j = 0; j < q->n_edges; j++) {
+        if (j > 0 && !(q->edges[j] > q->edges[j - 1])) return fail(e, TW_ERR_ARG, fn + ": the edges must be strictly ascending");
+        Q.edges[j] = q->edges[j];
+    }
+    return TW_OK;
+}
+
+// Quantiles, histogram and the copies to the host of the segments V views (the resident items, or the history): the scratch of the
+// two kernels is that of e->D whichever it is (freed with the batch).  Events ev, ev + 1 around the kernels; the stream is left
+// with the copies queued.
+int dist_answer(tw_engine* e, DistDev V, int64_t n_items, const DistQueryDev& Q, const tw_distributions* out, int ev) {
+    const int64_t n_seg = V.n_seg;
+    const int bins = Q.n_edges + 1;
+    const bool want_q = out != nullptr && out->quantile != nullptr && Q.n_q > 0, want_h = out != nullptr && out->hist != nullptr;
+    if ((want_q || want_h) && (e->D.quant == nullptr || n_seg > e->dist_out_cap)) {   // room for any query on these segments
+        DEV_ALLOC(e->D.quant, n_seg * kDistMaxQ); DEV_ALLOC(e->D.hist, n_seg * (kDistMaxEdges + 1));
+        e->dist_out_cap = n_seg;
+    }
+    V.quant = e->D.quant; V.hist = e->D.hist;
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads);
+    HIPCHK(hipEventRecord(e->stage_ev[ev], e->stream));
+    if (want_q) hipLaunchKernelGGL(k_dist_quantiles, dim3(flat_grid(n_seg * Q.n_q, threads)), tb, 0, e->stream, V, Q);
+    if (want_h) hipLaunchKernelGGL(k_dist_hist, dim3(flat_grid(n_seg * bins, threads)), tb, 0, e->stream, V, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->stage_ev[ev + 1], e->stream));
+    if (out != nullptr) {
+        TWCHK(copy_out(e, out->seg_count, V.seg_count, n_seg));
+        TWCHK(copy_out(e, out->seg_sum, V.seg_sum, n_seg));
+        TWCHK(copy_out(e, out->seg_off, V.seg_off, n_seg + 1));
+        TWCHK(copy_out(e, out->values, V.values, n_items));
+        if (want_q) TWCHK(copy_out(e, out->quantile, V.quant, n_seg * Q.n_q));
+        if (want_h) TWCHK(copy_out(e, out->hist, V.hist, n_seg * bins));
+    }
+    return TW_OK;
+}
+
+}  // namespace
+
 int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_distributions* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
     if (!e->attributed)
         return fail(e, TW_ERR_STATE, "tw_latency_distributions needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
                                      "whatever drops the forest drop the attribution)");
-    if (q->n_q < 0 || q->n_q > kDistMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, "tw_latency_distributions: n_q outside [0, 32]");
-    if (q->n_edges < 0 || q->n_edges > kDistMaxEdges || (q->n_edges > 0 && q->edges == nullptr))
-        return fail(e, TW_ERR_ARG, "tw_latency_distributions: n_edges outside [0, 63]");
     DistQueryDev Q{};
-    Q.n_q = q->n_q;
-    Q.n_edges = q->n_edges;
-    for (int j = 0; j < q->n_q; j++) {
-        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, "tw_latency_distributions: a prob outside [0, 1]");
-        Q.probs[j] = q->probs[j];
-    }
-    for (int j = 0; j < q->n_edges; j++) {
-        if (j > 0 && !(q->edges[j] > q->edges[j - 1])) return fail(e, TW_ERR_ARG, "tw_latency_distributions: the edges must be strictly ascending");
-        Q.edges[j] = q->edges[j];
-    }
+    TWCHK(dist_query(e, q, Q, "tw_latency_distributions"));
     const int64_t n_seg = (int64_t)(e->cohorts_set ? e->D.n_cohorts : 1) * (3 * (int64_t)e->A.n_groups + 1);
     if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_latency_distributions: more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
     HIPCHK(hipSetDevice(e->device));
     if (!e->dist_ready) TWCHK(dist_build(e));
-    DistDev& D = e->D;
     const int64_t nt = e->st_trees, n_items = e->dist_items;
-    const int bins = Q.n_edges + 1;
-    const bool want_q = out != nullptr && out->quantile != nullptr && Q.n_q > 0, want_h = out != nullptr && out->hist != nullptr;
-    if ((want_q || want_h) && (D.quant == nullptr || n_seg > e->dist_out_cap)) {   // room for any query on these segments (freed with the batch)
-        DEV_ALLOC(D.quant, n_seg * kDistMaxQ); DEV_ALLOC(D.hist, n_seg * (kDistMaxEdges + 1));
-        e->dist_out_cap = n_seg;
-    }
-    const unsigned threads = flat_threads(e);
-    const dim3 tb(threads);
-    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 3], e->stream));
-    if (want_q) hipLaunchKernelGGL(k_dist_quantiles, dim3(flat_grid(n_seg * Q.n_q, threads)), tb, 0, e->stream, D, Q);
-    if (want_h) hipLaunchKernelGGL(k_dist_hist, dim3(flat_grid(n_seg * bins, threads)), tb, 0, e->stream, D, Q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->stage_ev[SE_DIST + 4], e->stream));
+    TWCHK(dist_answer(e, e->D, n_items, Q, out, SE_DIST + 3));
     unsigned long long counters[kDistCounters];
-    HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
-    if (out != nullptr) {
-        TWCHK(copy_out(e, out->tree_cohort, D.tree_cohort, nt));
-        TWCHK(copy_out(e, out->seg_count, D.seg_count, n_seg));
-        TWCHK(copy_out(e, out->seg_sum, D.seg_sum, n_seg));
-        TWCHK(copy_out(e, out->seg_off, D.seg_off, n_seg + 1));
-        TWCHK(copy_out(e, out->values, D.values, n_items));
-        if (want_q) TWCHK(copy_out(e, out->quantile, D.quant, n_seg * Q.n_q));
-        if (want_h) TWCHK(copy_out(e, out->hist, D.hist, n_seg * bins));
-    }
+    HIPCHK(hipMemcpyAsync(counters, e->D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    if (out != nullptr) TWCHK(copy_out(e, out->tree_cohort, e->D.tree_cohort, nt));
     HIPCHK(hipStreamSynchronize(e->stream));
     TWCHK(stage_elapsed(e, SE_DIST, 3, 4, &e->ds_ms[2]));
     if (summary != nullptr) {
@@ -2934,28 +2987,26 @@ int tw_latency_distributions(tw_engine* e, const tw_dist_query* q, const tw_dist
 }
 
 /* ---- two cohorts compared: KS, rank sum, quantile shifts, permutation test (tw_cmp.h) -------------------------------- */
-int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comparison* out, int64_t* summary) {
-    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
-    if (!e->attributed)
-        return fail(e, TW_ERR_STATE, "tw_compare_cohorts needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
-                                     "whatever drops the forest drop the attribution)");
-    if (q->n_pairs < 1 || q->n_pairs > kCmpMaxPairs || q->pairs == nullptr) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_pairs outside [1, 64]");
-    const int32_t n_cohorts = e->cohorts_set ? e->D.n_cohorts : 1;
+namespace {
+
+// The comparison of the cohorts [0, n_cohorts) of the segments D views (the resident items, or the history): the checks of the
+// query, the kernels, the copies and the summary.  Events ev .. ev + 2, the two times into ms[0], ms[1].
+int cmp_run(tw_engine* e, const DistDev& D, int32_t n_cohorts, int64_t per, const tw_cmp_query* q, const tw_cohort_comparison* out, int64_t* summary,
+            const std::string& fn, int ev, double* ms, bool checks_only) {
+    if (q->n_pairs < 1 || q->n_pairs > kCmpMaxPairs || q->pairs == nullptr) return fail(e, TW_ERR_ARG, fn + ": n_pairs outside [1, 64]");
     for (int i = 0; i < q->n_pairs; i++) {
         const int32_t a = q->pairs[2 * i], b = q->pairs[2 * i + 1];
-        if (a < 0 || a >= n_cohorts || b < 0 || b >= n_cohorts) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a pair names a cohort outside [0, n_cohorts)");
-        if (a == b) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a pair compares a cohort with itself");
+        if (a < 0 || a >= n_cohorts || b < 0 || b >= n_cohorts) return fail(e, TW_ERR_ARG, fn + ": a pair names a cohort outside [0, n_cohorts)");
+        if (a == b) return fail(e, TW_ERR_ARG, fn + ": a pair compares a cohort with itself");
     }
-    if (q->n_q < 0 || q->n_q > kCmpMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_q outside [0, 8]");
+    if (q->n_q < 0 || q->n_q > kCmpMaxQ || (q->n_q > 0 && q->probs == nullptr)) return fail(e, TW_ERR_ARG, fn + ": n_q outside [0, 8]");
     for (int j = 0; j < q->n_q; j++)
-        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: a prob outside [0, 1]");
-    if (q->n_perm < 0 || q->n_perm > kCmpMaxPerm) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: n_perm outside [0, 65536]");
-    if (q->max_pool < 0) return fail(e, TW_ERR_ARG, "tw_compare_cohorts: max_pool below 0");
-    const int64_t per = 3 * (int64_t)e->A.n_groups + 1, n_seg = (int64_t)n_cohorts * per;
-    if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->dist_ready) TWCHK(dist_build(e));
-    const DistDev& D = e->D;
+        if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, fn + ": a prob outside [0, 1]");
+    if (q->n_perm < 0 || q->n_perm > kCmpMaxPerm) return fail(e, TW_ERR_ARG, fn + ": n_perm outside [0, 65536]");
+    if (q->max_pool < 0) return fail(e, TW_ERR_ARG, fn + ": max_pool below 0");
+    const int64_t n_seg = (int64_t)n_cohorts * per;
+    if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, fn + ": more than 2^24 segments (n_cohorts * (3 * n_groups + 1))");
+    if (checks_only) return TW_OK;
     // the sizes of the rows: limits, pool offsets and the summary on the host
     std::vector<unsigned long long> count((size_t)n_seg);
     HIPCHK(hipMemcpyAsync(count.data(), D.seg_count, sizeof(unsigned long long) * (size_t)n_seg, hipMemcpyDeviceToHost, e->stream));
@@ -2968,8 +3019,8 @@ int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comp
         const unsigned long long na = count[(size_t)(q->pairs[2 * pi] * per + r)], nb = count[(size_t)(q->pairs[2 * pi + 1] * per + r)];
         int64_t n = 0;
         if (na > 0 && nb > 0) {
-            if (na + nb >= (1ull << 32)) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: a row pools 2^32 values or more");
-            if (na * nb >= (1ull << 61)) return fail(e, TW_ERR_UNSUPPORTED, "tw_compare_cohorts: n_a * n_b of a row is 2^61 or more");
+            if (na + nb >= (1ull << 32)) return fail(e, TW_ERR_UNSUPPORTED, fn + ": a row pools 2^32 values or more");
+            if (na * nb >= (1ull << 61)) return fail(e, TW_ERR_UNSUPPORTED, fn + ": n_a * n_b of a row is 2^61 or more");
             n = (int64_t)(na + nb);
             both++;
             if (q->n_perm > 0 && (q->max_pool == 0 || n <= q->max_pool)) { permuted++; permuted_items += n; }
@@ -3004,7 +3055,7 @@ int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comp
     HIPCHK(hipMemsetAsync(M.ks_pos, 0xFF, sizeof(unsigned long long) * (size_t)n_rows, e->stream));
     const unsigned threads = flat_threads(e);
     const dim3 tb(threads);
-    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 0], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[ev + 0], e->stream));
     if (n_items > 0) {
         const dim3 items((unsigned)std::min<int64_t>(flat_grid(n_items, threads), 1 << 20));
         hipLaunchKernelGGL(k_cmp_rank, items, tb, 0, e->stream, D, M);
@@ -3012,13 +3063,13 @@ int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comp
     }
     hipLaunchKernelGGL(k_cmp_final, dim3(flat_grid(n_rows, threads)), tb, 0, e->stream, D, M);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 1], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[ev + 1], e->stream));
     if (permuted > 0) {
         const WaveShape per_block = wave_shape(e, n_rows * ((q->n_perm + 63) / 64), 1, kCmpWaves);
         hipLaunchKernelGGL(k_cmp_perm, per_block.grid, per_block.block, 0, e->stream, M);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(e->stage_ev[SE_CMP + 2], e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[ev + 2], e->stream));
     if (out != nullptr) {
         const size_t nr = (size_t)n_rows, nrq = nr * (size_t)q->n_q;
         TWCHK(copy_out(e, out->n_a, M.n_a, nr));
@@ -3034,9 +3085,259 @@ int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comp
         }
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, SE_CMP, i, i + 1, &e->cm_ms[i]));
+    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, ev, i, i + 1, &ms[i]));
     if (summary != nullptr) { summary[0] = both; summary[1] = permuted; summary[2] = permuted_items; summary[3] = q->n_perm; }
     return TW_OK;
+}
+
+}  // namespace
+
+int tw_compare_cohorts(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comparison* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    if (!e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_compare_cohorts needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
+                                     "whatever drops the forest drop the attribution)");
+    const int32_t n_cohorts = e->cohorts_set ? e->D.n_cohorts : 1;
+    const int64_t per = 3 * (int64_t)e->A.n_groups + 1;
+    TWCHK(cmp_run(e, e->D, n_cohorts, per, q, out, summary, "tw_compare_cohorts", SE_CMP, e->cm_ms, true));   // refused before the items are built
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->dist_ready) TWCHK(dist_build(e));
+    return cmp_run(e, e->D, n_cohorts, per, q, out, summary, "tw_compare_cohorts", SE_CMP, e->cm_ms, false);
+}
+
+/* ---- the distributions of batch after batch: a history on the device (tw_hist.h) ---------------------------------------- */
+namespace {
+
+// A buffer of the history's own (not a load's): the new one first, so that a failure leaves the old one and the history intact.
+extern "C++" {
+template <class T>
+int hist_grow(tw_engine* e, T** p, int64_t count) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)std::max<int64_t>(count, 1) * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e, TW_ERR_DEVICE, "tw_history: no device memory for " + std::to_string(count) + " elements (the history is as it was)");
+    }
+    if (*p != nullptr) (void)hipFree(*p);
+    *p = (T*)q;
+    return TW_OK;
+}
+}
+
+struct HistSource {                  // sorted segments on the device: the resident items of a batch, or an uploaded source
+    int32_t n_cohorts, n_groups;
+    const int64_t* off;
+    const unsigned long long *count, *sum;
+    const int64_t* values;
+};
+
+// The checks of a cohort map (NULL = the identity) against the history as it is; inv[h] = the source cohort that goes to history
+// cohort h, C_new = the history's cohorts afterwards.
+int hist_map(tw_engine* e, const std::string& fn, int32_t n_cohorts, int32_t n_groups, const int32_t* cohort_map, std::vector<int32_t>& inv, int32_t& C_new) {
+    if (n_groups < 1) return fail(e, TW_ERR_ARG, fn + ": n_groups must be positive");
+    if (e->hist_G != 0 && n_groups != e->hist_G)
+        return fail(e, TW_ERR_ARG, fn + ": the history holds " + std::to_string(e->hist_G) + " groups, the source " + std::to_string(n_groups) + " (tw_history_reset opens it again)");
+    std::vector<int32_t> seen;
+    int64_t top = -1;
+    for (int32_t c = 0; c < n_cohorts; c++) {
+        const int32_t h = cohort_map != nullptr ? cohort_map[c] : c;
+        if (h < -1) return fail(e, TW_ERR_ARG, fn + ": cohort_map holds an entry below -1");
+        if (h >= 0) seen.push_back(h);
+        top = std::max<int64_t>(top, h);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+        return fail(e, TW_ERR_ARG, fn + ": two cohorts of the source go to one cohort of the history (a push merges two sorted runs per segment, never more)");
+    const int64_t c_new = std::max<int64_t>(e->hist_C, top + 1), per = 3 * (int64_t)n_groups + 1;
+    if (c_new * per > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, fn + ": more than 2^24 segments in the history (C_h * (3 * n_groups + 1))");
+    C_new = (int32_t)c_new;
+    inv.assign((size_t)c_new, -1);
+    for (int32_t c = 0; c < n_cohorts; c++) {
+        const int32_t h = cohort_map != nullptr ? cohort_map[c] : c;
+        if (h >= 0) inv[(size_t)h] = c;
+    }
+    return TW_OK;
+}
+
+// Plan and merge of `src` into the side of the history that is not in use, and the swap when nothing has failed.  Events
+// SE_HIST + 0 (recorded here unless the caller has: `started`) .. + 2.
+int hist_absorb(tw_engine* e, const HistSource& src, const std::vector<int32_t>& inv, int32_t C_new, int64_t* summary, bool started) {
+    const int64_t per = 3 * (int64_t)src.n_groups + 1, n_seg = (int64_t)C_new * per, n_old = (int64_t)e->hist_C * per;
+    const tw_engine::HistSide& from = e->hist_side[e->hist_cur];
+    tw_engine::HistSide& to = e->hist_side[e->hist_cur ^ 1];
+    if (n_seg > to.seg_cap || to.off == nullptr) {
+        to.seg_cap = 0;
+        TWCHK(hist_grow(e, &to.off, n_seg + 1)); TWCHK(hist_grow(e, &to.count, n_seg)); TWCHK(hist_grow(e, &to.sum, n_seg));
+        to.seg_cap = n_seg;
+    }
+    if (n_seg > e->hist_plan_cap || e->hist_tile_off == nullptr) {
+        e->hist_plan_cap = 0;
+        TWCHK(hist_grow(e, &e->hist_tile_off, n_seg + 1));
+        e->hist_plan_cap = n_seg;
+    }
+    if (C_new > e->hist_inv_cap || e->hist_inv == nullptr) {
+        e->hist_inv_cap = 0;
+        TWCHK(hist_grow(e, &e->hist_inv, (int64_t)C_new));
+        e->hist_inv_cap = C_new;
+    }
+    if (e->hist_counters == nullptr) TWCHK(hist_grow(e, &e->hist_counters, (int64_t)kHistCounters));
+    HistDev H{};
+    H.per = per; H.n_seg = n_seg; H.n_old = n_old;
+    H.old_off = from.off; H.old_count = from.count; H.old_sum = from.sum; H.old_values = from.values;
+    H.inv = e->hist_inv;
+    H.src_off = src.off; H.src_count = src.count; H.src_sum = src.sum; H.src_values = src.values;
+    H.new_off = to.off; H.new_count = to.count; H.new_sum = to.sum;
+    H.tile_off = e->hist_tile_off; H.counters = e->hist_counters;
+    if (!started) HIPCHK(hipEventRecord(e->stage_ev[SE_HIST + 0], e->stream));
+    if (C_new > 0) HIPCHK(hipMemcpyAsync(e->hist_inv, inv.data(), sizeof(int32_t) * (size_t)C_new, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(e->hist_counters, 0, sizeof(unsigned long long) * kHistCounters, e->stream));
+    hipLaunchKernelGGL(k_hist_plan, dim3(1), dim3(flat_threads(e)), 0, e->stream, H);
+    HIPCHK(hipGetLastError());
+    unsigned long long counters[kHistCounters];
+    HIPCHK(hipMemcpyAsync(counters, e->hist_counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t added = (int64_t)counters[0], held = (int64_t)counters[1], n_tiles = (int64_t)counters[2];
+    if (held > to.cap || to.values == nullptr) {   // geometric: at least twice what this side held
+        const int64_t cap = std::max<int64_t>(std::max<int64_t>(held, 2 * to.cap), 1);
+        to.cap = 0;
+        TWCHK(hist_grow(e, &to.values, cap));
+        to.cap = cap;
+    }
+    H.new_values = to.values;
+    HIPCHK(hipEventRecord(e->stage_ev[SE_HIST + 1], e->stream));
+    if (n_tiles > 0) {
+        const unsigned threads = e->K.coop >= 64 ? (unsigned)kHistThreads : (unsigned)e->K.coop;
+        hipLaunchKernelGGL(k_hist_merge, dim3((unsigned)std::min<int64_t>(n_tiles, 1 << 24)), dim3(threads), 0, e->stream, H, n_tiles);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_HIST + 2], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, SE_HIST, i, i + 1, &e->hs_ms[i]));
+    // nothing has failed: the other side is the history now
+    e->hist_cur ^= 1;
+    e->hist_C = C_new; e->hist_G = src.n_groups; e->hist_items = held; e->hist_pushes++;
+    if (summary != nullptr) { summary[0] = added; summary[1] = held; summary[2] = C_new; summary[3] = e->hist_pushes; }
+    return TW_OK;
+}
+
+// the history as the quantile, histogram and comparison kernels read it
+DistDev hist_view(const tw_engine* e) {
+    const tw_engine::HistSide& side = e->hist_side[e->hist_cur];
+    DistDev V{};
+    V.n_cohorts = e->hist_C;
+    V.n_seg = (int64_t)e->hist_C * (3 * (int64_t)e->hist_G + 1);
+    V.seg_count = side.count; V.seg_sum = side.sum; V.seg_off = side.off; V.values = side.values;
+    V.items_cap = side.cap;
+    return V;
+}
+
+int need_history(tw_engine* e, const char* fn) {
+    if (e->hist_C > 0) return TW_OK;
+    return fail(e, TW_ERR_STATE, std::string(fn) + " on an empty history (tw_history_push or tw_history_merge first; tw_history_reset empties it)");
+}
+
+}  // namespace
+
+int tw_history_reset(tw_engine* e) {
+    if (e == nullptr) return TW_ERR_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    hist_free(e);
+    return TW_OK;
+}
+
+int tw_history_push(tw_engine* e, int32_t n_map, const int32_t* cohort_map, int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (!e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_history_push needs a tw_attribute_traces call on the current forest (a new tw_stitch_traces, new row groups and "
+                                     "whatever drops the forest drop the attribution)");
+    const int32_t n_cohorts = e->cohorts_set ? e->D.n_cohorts : 1, G = e->A.n_groups;
+    if (n_map != n_cohorts) return fail(e, TW_ERR_ARG, "tw_history_push: n_map must be the batch's n_cohorts (" + std::to_string(n_cohorts) + ")");
+    std::vector<int32_t> inv;
+    int32_t C_new = 0;
+    TWCHK(hist_map(e, "tw_history_push", n_cohorts, G, cohort_map, inv, C_new));
+    if ((int64_t)n_cohorts * (3 * (int64_t)G + 1) > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_history_push: more than 2^24 segments in the batch (n_cohorts * (3 * n_groups + 1))");
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->dist_ready) TWCHK(dist_build(e));
+    const HistSource src{n_cohorts, G, e->D.seg_off, e->D.seg_count, e->D.seg_sum, e->D.values};
+    return hist_absorb(e, src, inv, C_new, summary, false);
+}
+
+int tw_history_merge(tw_engine* e, int32_t n_cohorts_src, int32_t n_groups, const int64_t* seg_off_src, const int64_t* values_src, const int32_t* cohort_map,
+                     int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (n_cohorts_src < 1 || seg_off_src == nullptr) return fail(e, TW_ERR_ARG, "tw_history_merge: n_cohorts_src must be positive, seg_off_src given");
+    std::vector<int32_t> inv;
+    int32_t C_new = 0;
+    TWCHK(hist_map(e, "tw_history_merge", n_cohorts_src, n_groups, cohort_map, inv, C_new));
+    const int64_t n_seg = (int64_t)n_cohorts_src * (3 * (int64_t)n_groups + 1);
+    if (n_seg > kDistMaxSeg) return fail(e, TW_ERR_UNSUPPORTED, "tw_history_merge: more than 2^24 segments in the source (n_cohorts_src * (3 * n_groups + 1))");
+    if (seg_off_src[0] != 0) return fail(e, TW_ERR_ARG, "tw_history_merge: seg_off_src must start at 0");
+    for (int64_t s = 0; s < n_seg; s++)
+        if (seg_off_src[s + 1] < seg_off_src[s]) return fail(e, TW_ERR_ARG, "tw_history_merge: seg_off_src must not decrease");
+    const int64_t n_items = seg_off_src[n_seg];
+    if (n_items > 0 && values_src == nullptr) return fail(e, TW_ERR_ARG, "tw_history_merge: no values_src for " + std::to_string(n_items) + " items");
+    HIPCHK(hipSetDevice(e->device));
+    if (n_seg > e->hist_src_seg_cap || e->hist_src_off == nullptr) {
+        e->hist_src_seg_cap = 0;
+        TWCHK(hist_grow(e, &e->hist_src_off, n_seg + 1)); TWCHK(hist_grow(e, &e->hist_src_count, n_seg)); TWCHK(hist_grow(e, &e->hist_src_sum, n_seg));
+        e->hist_src_seg_cap = n_seg;
+    }
+    if (n_items > e->hist_src_cap || e->hist_src_values == nullptr) {
+        e->hist_src_cap = 0;
+        TWCHK(hist_grow(e, &e->hist_src_values, n_items));
+        e->hist_src_cap = std::max<int64_t>(n_items, 1);
+    }
+    if (e->hist_counters == nullptr) TWCHK(hist_grow(e, &e->hist_counters, (int64_t)kHistCounters));
+    HIPCHK(hipMemcpyAsync(e->hist_src_off, seg_off_src, sizeof(int64_t) * ((size_t)n_seg + 1), hipMemcpyHostToDevice, e->stream));
+    if (n_items > 0) HIPCHK(hipMemcpyAsync(e->hist_src_values, values_src, sizeof(int64_t) * (size_t)n_items, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(e->hist_src_sum, 0, sizeof(unsigned long long) * (size_t)n_seg, e->stream));
+    HIPCHK(hipMemsetAsync(e->hist_counters, 0, sizeof(unsigned long long) * kHistCounters, e->stream));
+    // every segment ascending, checked before anything is merged; the counts and the sums beside it
+    HIPCHK(hipEventRecord(e->stage_ev[SE_HIST + 0], e->stream));
+    const HistSrcDev S{n_seg, n_items, e->hist_src_off, e->hist_src_values, e->hist_src_count, e->hist_src_sum, e->hist_counters};
+    const unsigned threads = flat_threads(e);
+    hipLaunchKernelGGL(k_hist_source, dim3((unsigned)std::min<int64_t>(flat_grid(std::max(n_items, n_seg), threads), 1 << 20)), dim3(threads), 0, e->stream, S);
+    HIPCHK(hipGetLastError());
+    unsigned long long counters[kHistCounters];
+    HIPCHK(hipMemcpyAsync(counters, e->hist_counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (counters[3] != 0) return fail(e, TW_ERR_ARG, "tw_history_merge: a segment of values_src does not ascend");
+    const HistSource src{n_cohorts_src, n_groups, e->hist_src_off, e->hist_src_count, e->hist_src_sum, e->hist_src_values};
+    return hist_absorb(e, src, inv, C_new, summary, true);
+}
+
+int tw_history_info(tw_engine* e, int64_t* out6) {
+    if (e == nullptr || out6 == nullptr) return TW_ERR_ARG;
+    out6[0] = e->hist_C; out6[1] = e->hist_G; out6[2] = (int64_t)e->hist_C * (e->hist_G > 0 ? 3 * (int64_t)e->hist_G + 1 : 0);
+    out6[3] = e->hist_items; out6[4] = e->hist_pushes; out6[5] = e->hist_side[e->hist_cur].cap;
+    return TW_OK;
+}
+
+int tw_history_distributions(tw_engine* e, const tw_dist_query* q, const tw_distributions* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    TWCHK(need_history(e, "tw_history_distributions"));
+    DistQueryDev Q{};
+    TWCHK(dist_query(e, q, Q, "tw_history_distributions"));
+    HIPCHK(hipSetDevice(e->device));
+    const DistDev V = hist_view(e);
+    TWCHK(dist_answer(e, V, e->hist_items, Q, out, SE_HIST + 3));
+    std::vector<unsigned long long> count((size_t)V.n_seg);
+    HIPCHK(hipMemcpyAsync(count.data(), V.seg_count, sizeof(unsigned long long) * (size_t)V.n_seg, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    TWCHK(stage_elapsed(e, SE_HIST, 3, 4, &e->hs_ms[2]));
+    if (summary != nullptr) {
+        int64_t filled = 0;
+        for (unsigned long long c : count) filled += c != 0 ? 1 : 0;
+        summary[0] = e->hist_items; summary[1] = filled; summary[2] = e->hist_C; summary[3] = e->hist_pushes;
+    }
+    return TW_OK;
+}
+
+int tw_history_compare(tw_engine* e, const tw_cmp_query* q, const tw_cohort_comparison* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    TWCHK(need_history(e, "tw_history_compare"));
+    HIPCHK(hipSetDevice(e->device));
+    return cmp_run(e, hist_view(e), e->hist_C, 3 * (int64_t)e->hist_G + 1, q, out, summary, "tw_history_compare", SE_HIST + 5, e->hs_ms + 3, false);
 }
 
 /* ---- traces grouped by call-graph signature (tw_sig.h) --------------------------------------------------------------- */

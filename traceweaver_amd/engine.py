@@ -586,9 +586,12 @@ class Engine(object):
         the quantile shifts Q_b - Q_a at `probs` (at most 8) and, with `permutations` > 0 (at most 65536), how many permutations
         of the pooled values are at least as extreme in each of them (`seed` selects the draws; rows of more than `max_pool`
         pooled values, when it is > 0, are not permuted).  Returns traces.CohortComparison."""
+        return self._compare(self._lib.tw_compare_cohorts, int(getattr(self, "_n_groups", 0)), pairs, probs, permutations, seed, max_pool)
+
+    def _compare(self, call, G, pairs, probs, permutations, seed, max_pool):
+        """tw_compare_cohorts / tw_history_compare: the query, the output arrays of n_pairs * (3 G + 1) rows, the call."""
         from .traces import CohortComparison
 
-        G = int(getattr(self, "_n_groups", 0))
         pa = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
         n_rows = min(len(pa), _ffi.TW_CMP_MAX_PAIRS) * (3 * G + 1)
@@ -601,7 +604,7 @@ class Engine(object):
         ge_q = np.full((n_rows, nq), -1, dtype=np.int64)
         summary = np.zeros(4, dtype=np.int64)
         out = _ffi.CohortComparison(*([_vp(x) for x in one] + [_vp(shift) if shift.size else None, _vp(ge_ks), _vp(ge_u), _vp(ge_q) if ge_q.size else None]))
-        self._check(self._lib.tw_compare_cohorts(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        self._check(call(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
         return CohortComparison(one[0], one[1], one[2], one[3], one[4], shift, ge_ks, ge_u, ge_q, summary, pa, pr, G, n_perm)
 
     def compare_timing(self):
@@ -609,6 +612,85 @@ class Engine(object):
         ms = np.zeros(35, dtype=np.float64)
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 35))
         return dict(zip(("observed", "permutations"), ms[33:35].tolist()))
+
+    # ---- the history: distributions kept across batches (tw_history_*, csrc/tw_hist.h) ----
+    def history_reset(self):
+        """Empties the history (tw_history_reset): no cohorts, the number of groups open again."""
+        self._check(self._lib.tw_history_reset(self._h))
+
+    def history_push(self, cohort_map=None):
+        """Merges the sorted items of the last attribute() -- those distributions() returns -- into the history on the device
+        (tw_history_push): the batch's cohort c goes to history cohort cohort_map[c] (-1 = not kept, None = the identity; the
+        entries >= 0 distinct).  The history survives loads, new row maps, stitches and passes; only history_reset() and close()
+        end it.  Returns summary4: items added, items held, cohorts of the history, pushes and merges since the reset."""
+        summary = np.zeros(4, dtype=np.int64)
+        if cohort_map is None:
+            n_map, m = int(getattr(self, "_n_cohorts", 1)), None
+        else:
+            m = np.ascontiguousarray(cohort_map, dtype=np.int32).ravel()
+            n_map = len(m)
+        self._check(self._lib.tw_history_push(self._h, n_map, _vp(m) if m is not None and len(m) else None, _vp(summary)))
+        return summary
+
+    def history_merge(self, source, cohort_map=None):
+        """The same from the host (tw_history_merge): `source` is a traces.LatencyDistributions (another engine's, or a history
+        read back) or a tuple (n_cohorts, n_groups, seg_off, values) as traces.read_history_npz returns.  Every segment must
+        ascend (checked on the device before anything is merged)."""
+        if hasattr(source, "seg_off"):
+            source = (source.n_cohorts, source.n_groups, source.seg_off, source.values)
+        C, G = int(source[0]), int(source[1])
+        off = np.ascontiguousarray(source[2], dtype=np.int64).ravel()
+        values = np.ascontiguousarray(source[3], dtype=np.int64).ravel()
+        if C < 1 or G < 1 or len(off) != C * (3 * G + 1) + 1 or (len(off) and len(values) != int(off[-1])):
+            raise ValueError("history_merge: seg_off and values do not match n_cohorts * (3 * n_groups + 1) segments")
+        m = None if cohort_map is None else np.ascontiguousarray(cohort_map, dtype=np.int32).ravel()
+        if m is not None and len(m) != C:
+            raise ValueError("history_merge: cohort_map does not match the source's cohorts")
+        summary = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.tw_history_merge(self._h, C, G, _vp(off), _vp(values) if len(values) else None, _vp(m) if m is not None else None, _vp(summary)))
+        return summary
+
+    def history_info(self):
+        """tw_history_info: cohorts, groups, segments, items, pushes (and merges) since the reset, capacity in items; all 0 for an
+        empty history."""
+        out = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_history_info(self._h, _vp(out)))
+        return dict(zip(("cohorts", "groups", "segments", "items", "pushes", "capacity"), out.tolist()))
+
+    def history_distributions(self, probs=(0.5, 0.9, 0.95, 0.99), edges=None, values=True):
+        """distributions() over the history (tw_history_distributions): per history cohort, metric and group the sorted values of
+        everything pushed so far, counts, sums, quantiles and a histogram.  With probs=() and no edges it reads the history back.
+        Returns traces.LatencyDistributions (tree_cohort empty; summary = items, non-empty segments, cohorts, pushes)."""
+        from .traces import LatencyDistributions
+
+        info = self.history_info()
+        C, G, n_seg = info["cohorts"], info["groups"], info["segments"]
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        ed = np.ascontiguousarray(() if edges is None else edges, dtype=np.int64).ravel()
+        q = _ffi.DistQuery(len(pr), _vp(pr) if len(pr) else ctypes.c_void_p(0), len(ed), _vp(ed) if len(ed) else ctypes.c_void_p(0))
+        nq, bins = min(len(pr), _ffi.TW_DIST_MAX_Q), min(len(ed), _ffi.TW_DIST_MAX_EDGES) + 1
+        seg_count, seg_sum = np.zeros(n_seg, dtype=np.int64), np.zeros(n_seg, dtype=np.int64)
+        seg_off = np.zeros(n_seg + 1, dtype=np.int64)
+        quantile = np.zeros((n_seg, nq), dtype=np.int64)
+        hist = np.zeros((n_seg, bins), dtype=np.int64)
+        held = np.empty(info["items"] if values else 0, dtype=np.int64)
+        summary = np.zeros(4, dtype=np.int64)
+        out = _ffi.Distributions(None, _vp(seg_count) if n_seg else None, _vp(seg_sum) if n_seg else None, _vp(seg_off), _vp(held) if len(held) else None,
+                                 _vp(quantile) if quantile.size else None, _vp(hist) if hist.size else None)
+        self._check(self._lib.tw_history_distributions(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        return LatencyDistributions(np.zeros(0, dtype=np.int32), seg_count, seg_sum, seg_off, held, quantile, hist, summary, C, G, pr, ed)
+
+    def history_compare(self, pairs=((0, 1),), probs=(0.5, 0.95, 0.99), permutations=0, seed=0, max_pool=0):
+        """compare_cohorts() over the history (tw_history_compare): pairs of history cohorts -- batch against batch.  Returns
+        traces.CohortComparison."""
+        return self._compare(self._lib.tw_history_compare, self.history_info()["groups"], pairs, probs, permutations, seed, max_pool)
+
+    def history_timing(self):
+        """The history on the device (HIP events, ms): plan and merge of the last history_push() / history_merge(); quantiles
+        and histogram of the last history_distributions(); observed statistics and permutation walk of the last history_compare()."""
+        ms = np.zeros(43, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 43))
+        return dict(zip(("plan", "merge", "quantiles", "observed", "permutations"), ms[38:43].tolist()))
 
     def signatures(self, mode="levels", need_flags=1, skip_flags=0, keep_reference=False, compare=False):
         """The trees of the last stitch() grouped by call-graph signature (tw_trace_signatures): per eligible tree (flags hold

@@ -117,6 +117,15 @@ def parse_args(argv=None):
     ap.add_argument("--compare_pairs", type=q, default="0,1", help="--compare_out: the pairs of cohorts a,b, separated by semicolons (0,1;0,2)")
     ap.add_argument("--permutations", type=int, default=0, help="--compare_out: permutations per compared segment, at most 65536 (0: no test)")
     ap.add_argument("--compare_seed", type=int, default=0, help="--compare_out: the seed of the permutations")
+    ap.add_argument("--history", type=q, default=None,
+                    help="--latency_out: keep this run's distributions in a store across runs (tw_history_push): the file is read into "
+                         "the device history if it exists (tw_history_merge), the run's sorted values are merged in on the device and the "
+                         "store is written back.  The store's services must be this run's.  Default: off, nothing changes")
+    ap.add_argument("--history_cohort", type=int, default=0, help="--history: the run's cohort c goes to cohort K + c of the store (default 0)")
+    ap.add_argument("--history_compare_out", type=q, default=None,
+                    help="--history: compare cohorts of the store pair by pair on the device (tw_history_compare: one run against another), "
+                         "with --compare_pairs, --permutations, --compare_seed and --quantiles read as for --compare_out, and write the "
+                         "result to this .npz")
     ap.add_argument("--signatures_out", type=q, default=None,
                     help="group the traces by call-graph signature on the device (per level the services seen there, the reference's "
                          "AssignCGSignature / FindUniqueCGs): the signatures of the true traces are kept as the reference set, those of "
@@ -212,6 +221,20 @@ def unsupported(args):
         problems.append("--compare_seed below 0")
     if args.compare_out and len(quantiles_of(args) or ()) > 8:
         problems.append("--compare_out with more than 8 --quantiles")
+    if args.history and not args.latency_out:
+        problems.append("--history without --latency_out (it keeps that run's distributions)")
+    if args.history_cohort < 0 or (args.history_cohort != 0 and not args.history):
+        problems.append("--history_cohort below 0 or without --history")
+    if args.history_compare_out and not (args.history and args.latency_out):
+        problems.append("--history_compare_out without --history and --latency_out (it compares cohorts of that store)")
+    if args.history_compare_out and pairs_of(args) is None:
+        problems.append("--compare_pairs %s (up to 64 pairs a,b of different cohorts, separated by semicolons)" % args.compare_pairs)
+    if args.history_compare_out and not 0 <= args.permutations <= 65536:
+        problems.append("--permutations outside [0, 65536]")
+    if args.history_compare_out and args.compare_seed < 0:
+        problems.append("--compare_seed below 0")
+    if args.history_compare_out and len(quantiles_of(args) or ()) > 8:
+        problems.append("--history_compare_out with more than 8 --quantiles")
     if args.signatures_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--signatures_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.profiles_out and (10 not in requested(args) or args.cache_rate > 0):
@@ -448,6 +471,35 @@ def comparison_line(c, i, g, name):
         c.superiority()[r], " (p = %.4f)" % c.p_value("u")[r] if tested else "")
 
 
+def history_out(args, eng, d, names, culprit):
+    """--history / --history_compare_out: the store read into the device history, the run's distributions `d` (resident on the
+    device) pushed into it, the store written back, and cohorts of it compared."""
+    from . import traces
+
+    cohorts = []
+    if os.path.exists(args.history):
+        source, group_names, cohorts = traces.read_history_npz(args.history)
+        if group_names != [str(x) for x in names]:
+            raise SystemExit("--history %s: the store holds the services %s, this run %s" % (args.history, ", ".join(group_names), ", ".join(str(x) for x in names)))
+        eng.history_reset()
+        eng.history_merge(source)
+    added = eng.history_push([args.history_cohort + c for c in range(d.n_cohorts)])
+    h = eng.history_distributions((), None)
+    cohorts = cohorts + [str(c) for c in range(len(cohorts), h.n_cohorts)]
+    traces.write_history_npz(args.history, h, names, cohorts)
+    print("History: %d values added to cohort%s %s, %d held in %d cohorts" % (
+        added[0], "s" if d.n_cohorts > 1 else "", ", ".join(str(args.history_cohort + c) for c in range(d.n_cohorts)), h.n_items, h.n_cohorts))
+    if args.history_compare_out:
+        pairs = pairs_of(args)
+        if max(max(p) for p in pairs) >= h.n_cohorts:
+            raise SystemExit("--compare_pairs %s: the store %s holds %d cohorts" % (args.compare_pairs, args.history, h.n_cohorts))
+        c = eng.history_compare(pairs, quantiles_of(args), args.permutations, args.compare_seed)
+        traces.write_comparison_npz(args.history_compare_out, c, names)
+        print("History comparison: %d pairs, %d segments with spans in both, %d permutations of %d" % (len(pairs), c.summary[0], c.summary[3], c.summary[1]))
+        for i in range(len(pairs) if culprit >= 0 else 0):
+            print("History: " + comparison_line(c, i, culprit, names[culprit]))
+
+
 def attribute_out(args, eng, st, corpus, table):
     """--attribute_out / --latency_out: the delay-culprit query on the forest just stitched, groups by service, and the
     distributions behind its answer."""
@@ -478,6 +530,8 @@ def attribute_out(args, eng, st, corpus, table):
         print("Cohort comparison: %d pairs, %d segments with spans in both, %d permutations of %d" % (len(pairs), c.summary[0], c.summary[3], c.summary[1]))
         for i in range(len(pairs) if a.culprit >= 0 else 0):
             print(comparison_line(c, i, a.culprit, names[a.culprit]))
+    if args.history:
+        history_out(args, eng, d, names, a.culprit)
     if args.verbose:
         eng.stitch(truth=True)
         b = eng.attribute(**query)

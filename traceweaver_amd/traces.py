@@ -598,6 +598,75 @@ def write_distributions_npz(path, distributions, names):
             probs=d.probs, edges=d.edges, **{k: getattr(d, k) for k in LatencyDistributions.FIELDS})
 
 
+def history_host(parts, probs=(), edges=None):
+    """What the history holds after Engine.history_push / history_merge of `parts`, in turn, on an empty history
+    (tw_history_push, tw_history_distributions), restated with numpy and Python integers, for the tests.  parts: a list of
+    (LatencyDistributions, cohort_map); cohort_map [n_cohorts of the part] names the history cohort a cohort of the part goes to,
+    -1 = not kept, None = the identity.  Returns a LatencyDistributions of C_h = 1 + the largest entry cohorts: every segment
+    the sorted concatenation of what was pushed into it; tree_cohort is empty; summary = items, non-empty segments, C_h, parts."""
+    if not parts:
+        raise ValueError("history_host: no parts")
+    G = parts[0][0].n_groups
+    per = 3 * G + 1
+    maps = []
+    for d, cohort_map in parts:
+        m = list(range(d.n_cohorts)) if cohort_map is None else [int(x) for x in cohort_map]
+        kept = [h for h in m if h >= 0]
+        if d.n_groups != G or len(m) != d.n_cohorts or min(m + [0]) < -1 or len(set(kept)) != len(kept):
+            raise ValueError("history_host: a part does not fit (groups, the length of its map, an entry below -1 or a repeated one)")
+        maps.append(m)
+    C = max([0] + [1 + h for m in maps for h in m])
+    items = [[] for _ in range(C * per)]
+    for (d, _), m in zip(parts, maps):
+        for c, h in enumerate(m):
+            if h >= 0:
+                for r in range(per):
+                    s = c * per + r
+                    items[h * per + r].extend(int(v) for v in d.values[int(d.seg_off[s]):int(d.seg_off[s + 1])])
+    probs = np.asarray(probs, dtype=np.float64).ravel()
+    edges = np.asarray(() if edges is None else edges, dtype=np.int64).ravel()
+    n_seg = len(items)
+    items = [sorted(x) for x in items]
+    seg_count = np.array([len(x) for x in items], dtype=np.int64)
+    seg_sum = np.array([((sum(x) + (1 << 63)) % (1 << 64)) - (1 << 63) for x in items], dtype=np.int64)     # two's complement, wrapping
+    seg_off = np.concatenate([[0], np.cumsum(seg_count)]).astype(np.int64)
+    values = np.array([v for x in items for v in x], dtype=np.int64)
+    quantile = np.full((n_seg, len(probs)), EMPTY, dtype=np.int64)
+    hist = np.zeros((n_seg, len(edges) + 1), dtype=np.int64)
+    for s, x in enumerate(items):
+        for j, p in enumerate(probs.tolist()):
+            if x:
+                quantile[s, j] = x[min(len(x) - 1, int(p * float(len(x))))]
+        if x:
+            hist[s] = np.bincount(np.searchsorted(edges, np.array(x, dtype=np.int64), side="right"), minlength=len(edges) + 1)
+    summary = [len(values), int((seg_count > 0).sum()), C, len(parts)]
+    return LatencyDistributions(np.zeros(0, dtype=np.int32), seg_count, seg_sum, seg_off, values, quantile, hist, summary, C, G, probs, edges)
+
+
+def write_history_npz(path, history, group_names, cohort_names=None):
+    """A history read back (Engine.history_distributions) as one .npz: seg_off, values, C_h, G and the names of the groups and
+    of the cohorts (default: their numbers).  read_history_npz gives what Engine.history_merge takes."""
+    h = history
+    cohorts = [str(c) for c in range(h.n_cohorts)] if cohort_names is None else [str(x) for x in cohort_names]
+    if len(cohorts) != h.n_cohorts or len(group_names) != h.n_groups:
+        raise ValueError("write_history_npz: the names do not match the history's cohorts and groups")
+    with open(path, "wb") as f:
+        np.savez_compressed(f, C_h=np.int64(h.n_cohorts), G=np.int64(h.n_groups), seg_off=np.asarray(h.seg_off, dtype=np.int64),
+                            values=np.asarray(h.values, dtype=np.int64), group_names=np.array([str(x) for x in group_names]),
+                            cohort_names=np.array(cohorts))
+
+
+def read_history_npz(path):
+    """-> ((n_cohorts, n_groups, seg_off, values), group_names, cohort_names): the first is an argument of Engine.history_merge."""
+    with np.load(path) as z:
+        C, G = int(z["C_h"]), int(z["G"])
+        seg_off, values = z["seg_off"].astype(np.int64), z["values"].astype(np.int64)
+        group_names, cohort_names = [str(x) for x in z["group_names"].tolist()], [str(x) for x in z["cohort_names"].tolist()]
+    if len(seg_off) != C * (3 * G + 1) + 1 or len(values) != int(seg_off[-1]) or len(group_names) != G or len(cohort_names) != C:
+        raise ValueError("%s: not a history (the arrays do not match C_h and G)" % path)
+    return (C, G, seg_off, values), group_names, cohort_names
+
+
 class CohortComparison(object):
     """Pairs of cohorts compared segment by segment (include/traceweaver_amd.h has the definitions): row = pair * (3 G + 1) + m * G +
     g compares A = segment (a, m, g) with B = segment (b, m, g) of pairs[pair] = (a, b).  n_a, n_b [n_rows]; ks_gap = #{A <= x} n_b

@@ -270,7 +270,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * the largest admissible count, min(5, #distinct)) / rows that were fitted after the selection; both 0 under TW_FIT_SPEC=0.
  * ms[37]: host wall clock the last refit spent building and queueing its order tables (tw_get_fit_order; 0 under TW_FIT_ORDER=0).
  * The history (HIP events): ms[38] plan and ms[39] merge kernel of the last tw_history_push / tw_history_merge, ms[40] quantiles and
- * histogram of the last tw_history_distributions, ms[41], ms[42] observed statistics and permutation walk of the last tw_history_compare. */
+ * histogram of the last tw_history_distributions, ms[41], ms[42] observed statistics and permutation walk of the last tw_history_compare.
+ * The class catalogue (HIP events): ms[43] hash and lookup, ms[44] scan, append, insert and any rehash, ms[45] accumulate of the
+ * last tw_class_history_push / tw_class_history_merge. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -832,6 +834,83 @@ typedef struct {
     int64_t *class_counted, *class_latency, *class_path_time, *class_top_entry;
 } tw_class_profile;
 int tw_class_profiles(tw_engine *e, const tw_class_profile *out, int64_t *summary6);
+
+/* ---- the classes of batch after batch: a catalogue on the device (csrc/tw_chist.h) --------------------------------
+ *
+ * Replaces: FindUniqueCGs / PreparePerCGData run over a whole directory of traces (alibaba-analysis/analysis.py:214-221,
+ * 233-292).  tw_trace_signatures and tw_class_profiles cover one engine's batch, and their classes are numbered per batch;
+ * the catalogue gives classes ids that hold across batches and figures that add up across them: did a call graph appear
+ * that was never seen, which shapes became more frequent, where does a shape spend its time over all the batches.  It is
+ * device state that outlives loads, stitches, passes and queries, as the history does: none of the calls below drops or
+ * rewrites anything of the resident batch.  Only tw_class_history_reset and tw_destroy end it.  Everything is integer.
+ *
+ * Definitions:
+ *   catalogue  empty after tw_create and tw_class_history_reset.  The first push or merge fixes mode (0 levels, 1 edges)
+ *              and G = n_groups; a later one with another mode or n_groups is TW_ERR_ARG.  It holds C classes; class k owns
+ *              the entries cat_off[k] .. cat_off[k + 1]) of cat_entries, four int32 (level, cg, g, count) in signature
+ *              order: the layout of class_off / class_entries.  Two classes are the same iff their entry sequences are
+ *              equal entry by entry; a hash of the entries buckets the classes, the comparison of the entries decides.
+ *   class ids  a source class whose signature the catalogue holds has that class' id; the source classes it does not hold
+ *              get C_before + (the number of such classes with a smaller source index).  An id never changes afterwards:
+ *              ids depend on the order of the calls and on nothing else.
+ *   per class  (int64) from the signature result, what & 1: trees, latency_sum (wrapping), latency_min / latency_max
+ *              (INT64_MAX / INT64_MIN while trees == 0).  From the class profile, what & 2: counted and latency (its
+ *              class_counted, class_latency).  Book-keeping: first_epoch = min and last_epoch = max of the epochs, seen = the
+ *              number of pushes and merges whose source held the class.  epoch is a label of the caller's (a batch number, a
+ *              timestamp) of which the engine only takes minima and maxima.
+ *   per entry  (int64, what & 2) the nine fields of tw_class_profile -- rows, span_time, span_min, span_max, self_time,
+ *              path_time, path_rows, path_trees, offset -- added, or combined by min / max, at cat_off[id] + j for entry j of
+ *              the source class: the entries of equal signatures line up.
+ *   derived    on read: class_path_time and class_top_entry by the rule of tw_class_profiles (the largest accumulated
+ *              path_time among the class' entries with path_rows > 0, ties to the smallest index, -1 if there is none), with
+ *              the catalogue's global entry indices.
+ *   push       the source is the resident signature result and, with what & 2, the resident class profile.  what in {1, 2, 3};
+ *              with 2 only the profile's figures are added (two attributions of one forest are pushed without counting its
+ *              trees twice).  Every class of the source is held afterwards, whatever what is; its seen is incremented and its
+ *              epochs are updated.  class_map [the batch's classes] = the catalogue ids.  summary6 = new classes, classes
+ *              held, new entries, entries held, pushes and merges since the reset, classes of the source.
+ *   match      class_map only, -1 for a class the catalogue does not hold (every class on an empty catalogue, TW_OK); it
+ *              changes nothing (a catalogue of the other mode or of other groups holds none of them: -1 everywhere).  With
+ *              tree_class of the signature result it names the traces whose shape was never seen.
+ *              summary6 as a push would give it, [0] and [2] = the classes and entries not held, [1] and [3] as they are.
+ *   merge      a push from host arrays: a saved catalogue, another rank's, another engine's signatures and profile.  The
+ *              source is the struct tw_class_history_get fills, with n_classes, n_entries, mode, n_groups set.  A figure
+ *              pointer that is NULL adds nothing (zeros, the identities of min and max); first_epoch / last_epoch / seen NULL
+ *              = the epoch argument and 1.  class_path_time and class_top_entry are not read.  The host checks that class_off
+ *              starts at 0, does not decrease and ends at n_entries; the device, before anything is changed, that every
+ *              class' entries ascend strictly by (level, cg, g), count >= 1, 0 <= level < 2^16, 0 <= g < G, cg in [-1, G)
+ *              in mode 1 and 0 in mode 0, and that no two source classes have equal signatures.
+ *   get        with out == NULL only summary6 (the sizes, as tw_class_history_info); a second call copies.  Every pointer
+ *              of out may be NULL; class_off has C + 1 elements, class_entries 4 * entries, the per-class arrays C, the
+ *              per-entry arrays `entries` elements.  The scalars of out are not written.
+ *   info       out6 = C, entries, pushes and merges since the reset, mode, G, the hash table's capacity in slots; all 0 for
+ *              an empty catalogue (tw_class_history_reset frees the buffers).
+ *
+ * TW_ERR_STATE: push or match without a resident signature result; what & 2 without a resident class profile; get on an
+ * empty catalogue.  TW_ERR_ARG: what outside {1, 2, 3}; another mode or n_groups than the catalogue's; the source errors
+ * above.  TW_ERR_UNSUPPORTED: more than 2^31 - 1 classes or entries (2^20 groups, as the signatures).  TW_ERR_DEVICE: no
+ * memory.  A call that is refused or fails leaves the catalogue exactly as it was -- the store grows by copying and the
+ * counts are set last; a merge that finds two equal source classes after they claimed slots refills the table from the
+ * store.  Results do not depend on scheduling (where the table put a class does; that is never returned).
+ * TW_SIG_HASH_BITS truncates this hash too: with 2 every class shares one of four buckets and the comparison alone
+ * separates them.  No eviction; ranks merge through the host.  Timing: tw_get_timing slots 43..45 of the last push or merge
+ * (HIP events, ms): 43 hash and lookup (with the source check of a merge), 44 scan, append, insert and any growth and
+ * rehash, 45 accumulate. */
+typedef struct {
+    int64_t n_classes, n_entries;   /* read by tw_class_history_merge only */
+    int32_t mode, n_groups;
+    int64_t *class_off;
+    int32_t *class_entries;
+    int64_t *trees, *latency_sum, *latency_min, *latency_max, *counted, *latency, *first_epoch, *last_epoch, *seen;
+    int64_t *rows, *span_time, *span_min, *span_max, *self_time, *path_time, *path_rows, *path_trees, *offset;
+    int64_t *class_path_time, *class_top_entry;
+} tw_class_catalogue;
+int tw_class_history_reset(tw_engine *e);
+int tw_class_history_push(tw_engine *e, int32_t what, int64_t epoch, int32_t *class_map, int64_t *summary6);
+int tw_class_history_match(tw_engine *e, int32_t *class_map, int64_t *summary6);
+int tw_class_history_merge(tw_engine *e, const tw_class_catalogue *src, int64_t epoch, int32_t *class_map, int64_t *summary6);
+int tw_class_history_info(tw_engine *e, int64_t *out6);
+int tw_class_history_get(tw_engine *e, const tw_class_catalogue *out, int64_t *summary6);
 
 /* Replaces: the sweep of BuildDistributions (traceweaver_v3.py:120-169).  The spans of one service merged in start
  * order (stable: incoming spans first, then the endpoints in order): start / dur [n], ep [n] (0 = incoming span,

@@ -124,6 +124,14 @@ class ClassProfile(ctypes.Structure):
         "class_counted", "class_latency", "class_path_time", "class_top_entry")]
 
 
+class ClassCatalogue(ctypes.Structure):
+    _fields_ = [("n_classes", ctypes.c_int64), ("n_entries", ctypes.c_int64), ("mode", ctypes.c_int32), ("n_groups", ctypes.c_int32)] + [
+        (k, ctypes.c_void_p) for k in (
+            "class_off", "class_entries", "trees", "latency_sum", "latency_min", "latency_max", "counted", "latency", "first_epoch", "last_epoch",
+            "seen", "rows", "span_time", "span_min", "span_max", "self_time", "path_time", "path_rows", "path_trees", "offset", "class_path_time",
+            "class_top_entry")]
+
+
 TW_TREE_CONFIDENT = 8
 TW_CONF_MAX_EDGES = 15
 TW_DIST_MAX_Q = 32
@@ -137,6 +145,7 @@ EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
            "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles",
            "tw_history_reset", "tw_history_push", "tw_history_merge", "tw_history_info", "tw_history_distributions", "tw_history_compare",
+           "tw_class_history_reset", "tw_class_history_push", "tw_class_history_match", "tw_class_history_merge", "tw_class_history_info", "tw_class_history_get",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
            "tw_corpus_string", "tw_corpus_loop_origin", "tw_corpus_trace_names", "tw_corpus_span_table", "tw_corpus_build_units"]
 
@@ -208,6 +217,12 @@ def load(path=None):
     lib.tw_history_info.argtypes = [vp, vp]
     lib.tw_history_distributions.argtypes = [vp, ctypes.POINTER(DistQuery), ctypes.POINTER(Distributions), vp]
     lib.tw_history_compare.argtypes = [vp, ctypes.POINTER(CmpQuery), ctypes.POINTER(CohortComparison), vp]
+    lib.tw_class_history_reset.argtypes = [vp]
+    lib.tw_class_history_push.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, vp, vp]
+    lib.tw_class_history_match.argtypes = [vp, vp, vp]
+    lib.tw_class_history_merge.argtypes = [vp, ctypes.POINTER(ClassCatalogue), ctypes.c_int64, vp, vp]
+    lib.tw_class_history_info.argtypes = [vp, vp]
+    lib.tw_class_history_get.argtypes = [vp, ctypes.POINTER(ClassCatalogue), vp]
     lib.tw_trace_signatures.argtypes = [vp, ctypes.POINTER(SigQuery), ctypes.POINTER(Signatures), vp]
     lib.tw_class_profiles.argtypes = [vp, ctypes.POINTER(ClassProfile), vp]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]

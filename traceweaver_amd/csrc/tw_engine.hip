@@ -31,6 +31,7 @@
 #include "tw_hist.h"
 #include "tw_sig.h"
 #include "tw_prof.h"
+#include "tw_chist.h"
 #include "tw_order.h"
 
 using namespace tw;
@@ -40,7 +41,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_COUNT = 37 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_CHIST = 37, SE_COUNT = 41 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8 + 4
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -275,6 +276,12 @@ struct tw_engine {
     unsigned long long* hist_counters = nullptr;
     int64_t *hist_src_off = nullptr, *hist_src_values = nullptr; unsigned long long *hist_src_count = nullptr, *hist_src_sum = nullptr;
     int64_t hist_src_seg_cap = 0, hist_src_cap = 0;   // the uploaded source of tw_history_merge
+    // tw_class_history_* (tw_chist.h): the call-graph classes of batch after batch.  Owned by the engine like the history: free_all
+    // leaves the catalogue alone, only tw_class_history_reset and tw_destroy end it.  CH.C / CH.E: classes and entries held.
+    ChistDev CH{};
+    int32_t ch_mode = 0, ch_G = 0;          // G, 0 = empty (mode and G are fixed by the first push or merge after a reset)
+    int64_t ch_pushes = 0, ch_src_cap = 0 /* source classes the scratch holds */;
+    void* ch_up = nullptr; size_t ch_up_bytes = 0;   // the uploaded source of tw_class_history_merge
     SigDev G{};                             // tw_trace_signatures (tw_sig.h); sig_ready: the result of sig_q on the forest is resident, a further
     bool sig_ready = false, ref_set = false;        // call with the same query only copies; ref_set: the reference set, keyed by root row
     tw_sig_query sig_q{};
@@ -293,6 +300,7 @@ struct tw_engine {
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
     double cm_ms[2] = {0, 0};               // ranks, pool and observed statistics; the permutation walk
     double hs_ms[5] = {0, 0, 0, 0, 0};      // history: plan (with the source check of a merge), merge; quantiles and histogram; observed statistics, permutation walk
+    double ch_ms[3] = {0, 0, 0};            // class catalogue: hash and lookup; scan, append, insert and any rehash; accumulate
     double host_ms[2] = {0, 0};             // host wall clock of the last pass: submitting the first enumeration / the whole tw_run_pass call
     // tw_order_stage / tw_order_load (tw_order.h): the span table of a batch in partition-key order, staged once, and the buffers a
     // candidate's permuted copy is gathered into before tw_load_batch takes it device to device.  Owned by the engine, not by a
@@ -415,6 +423,9 @@ int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
      class profile    prof_ready     tw_class_profiles    <- signature result, attribution
      history          hist_C > 0     tw_history_push / tw_history_merge <- nothing: it holds copies.  Dropped by tw_history_reset and
                                                              tw_destroy only (its buffers are not a load's: free_all leaves them)
+     class catalogue  ch_G > 0       tw_class_history_push / tw_class_history_merge <- nothing: it holds copies.  Dropped by
+                                                             tw_class_history_reset and tw_destroy only (buffers of its own, as the
+                                                             history's; no drop_* function touches it)
    An API function drops what it is about to replace with one call, before it overwrites anything, and sets its own flag last, when
    everything has succeeded (tw_trace_signatures owns two items: its result and, with keep_reference, the reference set). */
 void drop_dist(tw_engine* e) { e->dist_ready = false; }
@@ -496,6 +507,15 @@ void hist_free(tw_engine* e) {   // (the history of tw_history_*: not a load's, 
     e->hist_tile_off = nullptr; e->hist_inv = nullptr; e->hist_counters = nullptr; e->hist_plan_cap = 0; e->hist_inv_cap = 0;
     e->hist_src_off = e->hist_src_values = nullptr; e->hist_src_count = e->hist_src_sum = nullptr; e->hist_src_seg_cap = 0; e->hist_src_cap = 0;
     e->hist_cur = 0; e->hist_C = 0; e->hist_G = 0; e->hist_items = 0; e->hist_pushes = 0;
+}
+
+void chist_free(tw_engine* e) {   // (the catalogue of tw_class_history_*: not a load's, free_all leaves it alone)
+    ChistDev& H = e->CH;
+    void* all[] = {H.table, H.off, H.entries, H.hash, H.stamp, H.cls, H.cell, H.src_hash, H.src_id, H.new_src, H.chunk_sum, H.counters, e->ch_up};
+    for (void* q : all)
+        if (q) (void)hipFree(q);
+    H = ChistDev{};
+    e->ch_mode = 0; e->ch_G = 0; e->ch_pushes = 0; e->ch_src_cap = 0; e->ch_up = nullptr; e->ch_up_bytes = 0;
 }
 
 void free_all(tw_engine* e) {
@@ -1212,6 +1232,7 @@ void tw_destroy(tw_engine* e) {
     free_all(e);
     order_unstage(e);
     hist_free(e);
+    chist_free(e);
     if (e->arena != nullptr) (void)hipFree(e->arena);
     for (int i = 0; i < EV_COUNT; i++)
         if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -2062,6 +2083,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 2 && 33 + i < n; i++) ms[33 + i] = e->cm_ms[i];   // the last tw_compare_cohorts
     for (int i = 0; i < 2 && 35 + i < n; i++) ms[35 + i] = (double)e->fit_spec_count[i];   // the last refit: rows that adopted the fit made ahead / that were fitted after the selection
     if (n > 37) ms[37] = e->fit_order_host_ms;                            // ... and the host's time for its order tables
+    for (int i = 0; i < 3 && 43 + i < n; i++) ms[43 + i] = e->ch_ms[i];   // the last tw_class_history_push / _merge
     for (int i = 0; i < 5 && 38 + i < n; i++) ms[38 + i] = e->hs_ms[i];   // the last tw_history_push / _merge (38, 39), _distributions (40), _compare (41, 42)
     return TW_OK;
 }
@@ -3404,9 +3426,9 @@ int tw_trace_signatures(tw_engine* e, const tw_sig_query* q, const tw_signatures
         TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, D.hkey_a, D.hkey_b, D.val_a, D.val_b, (size_t)nt, 0u, 64u, e->stream); }));
         hipLaunchKernelGGL(k_sig_rep, trees, tb, 0, e->stream, S, D, nt);
         const int64_t n_chunks = (nt + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
-        hipLaunchKernelGGL(k_sig_scan_sums, dim3((unsigned)n_chunks), tb, 0, e->stream, D, nt);
-        hipLaunchKernelGGL(k_sig_scan_chunks, dim3(1), tb, 0, e->stream, D, n_chunks);
-        hipLaunchKernelGGL(k_sig_scan_write, dim3((unsigned)n_chunks), tb, 0, e->stream, D, nt);
+        hipLaunchKernelGGL(k_sig_scan_sums<SigScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, SigScan{D}, nt);
+        hipLaunchKernelGGL(k_sig_scan_chunks<SigScan>, dim3(1), tb, 0, e->stream, SigScan{D}, n_chunks);
+        hipLaunchKernelGGL(k_sig_scan_write<SigScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, SigScan{D}, nt);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(counters, D.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -3520,6 +3542,367 @@ int tw_class_profiles(tw_engine* e, const tw_class_profile* out, int64_t* summar
     } else if (out != nullptr) {
         HIPCHK(hipStreamSynchronize(e->stream));
     }
+    return TW_OK;
+}
+
+/* ---- the classes of batch after batch: a catalogue on the device (tw_chist.h) -------------------------------------------- */
+namespace {
+
+// Buffers of the catalogue's own (not a load's).  A group of arrays grows together: every new array first, then the copies, then the
+// old ones are freed, so that a failure leaves the catalogue intact.
+struct ChistNew {
+    std::vector<void*> got;
+    ~ChistNew() { for (void* q : got) (void)hipFree(q); }   // (whatever was not adopted)
+};
+void* chist_new(tw_engine* e, ChistNew& N, int64_t bytes) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)std::max<int64_t>(bytes, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        fail(e, TW_ERR_DEVICE, "tw_class_history: no device memory for " + std::to_string(bytes) + " bytes (the catalogue is as it was)");
+        return nullptr;
+    }
+    N.got.push_back(q);
+    return q;
+}
+#define CHIST_NEW(ptr, type, count)                                                    \
+    do {                                                                               \
+        (ptr) = (type*)chist_new(e, N, (int64_t)sizeof(type) * (int64_t)(count));      \
+        if ((ptr) == nullptr) return TW_ERR_DEVICE;                                    \
+    } while (0)
+
+// Room for `classes` classes and `entries` entries: the store's arrays at least double.
+int chist_reserve(tw_engine* e, int64_t classes, int64_t entries) {
+    ChistDev& H = e->CH;
+    if (H.off == nullptr || classes > H.cls_cap) {
+        const int64_t cap = std::max<int64_t>(std::max<int64_t>(classes, 2 * H.cls_cap), kChistSlots / 2);
+        ChistNew N;
+        int64_t *off, *cls; unsigned long long *hash, *stamp;
+        CHIST_NEW(off, int64_t, cap + 1); CHIST_NEW(hash, unsigned long long, cap); CHIST_NEW(stamp, unsigned long long, cap);
+        CHIST_NEW(cls, int64_t, (int64_t)kChistClassCols * cap);
+        HIPCHK(hipMemsetAsync(off, 0, sizeof(int64_t), e->stream));
+        if (H.off != nullptr) {
+            HIPCHK(hipMemcpyAsync(off, H.off, sizeof(int64_t) * (size_t)(H.C + 1), hipMemcpyDeviceToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(hash, H.hash, sizeof(unsigned long long) * (size_t)H.C, hipMemcpyDeviceToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(stamp, H.stamp, sizeof(unsigned long long) * (size_t)H.C, hipMemcpyDeviceToDevice, e->stream));
+            for (int c = 0; c < kChistClassCols; c++)
+                HIPCHK(hipMemcpyAsync(cls + (int64_t)c * cap, H.cls + (int64_t)c * H.cls_cap, sizeof(int64_t) * (size_t)H.C, hipMemcpyDeviceToDevice, e->stream));
+        }
+        HIPCHK(hipStreamSynchronize(e->stream));
+        N.got = {H.off, H.hash, H.stamp, H.cls};   // the old ones go
+        H.off = off; H.hash = hash; H.stamp = stamp; H.cls = cls; H.cls_cap = cap;
+    }
+    if (H.entries == nullptr || entries > H.ent_cap) {
+        const int64_t cap = std::max<int64_t>(std::max<int64_t>(entries, 2 * H.ent_cap), kChistSlots);
+        ChistNew N;
+        int32_t* ent; int64_t* cell;
+        CHIST_NEW(ent, int32_t, 4 * cap); CHIST_NEW(cell, int64_t, (int64_t)kProfCols * cap);
+        if (H.entries != nullptr) {
+            HIPCHK(hipMemcpyAsync(ent, H.entries, sizeof(int32_t) * 4 * (size_t)H.E, hipMemcpyDeviceToDevice, e->stream));
+            for (int c = 0; c < kProfCols; c++)
+                HIPCHK(hipMemcpyAsync(cell + (int64_t)c * cap, H.cell + (int64_t)c * H.ent_cap, sizeof(int64_t) * (size_t)H.E, hipMemcpyDeviceToDevice, e->stream));
+        }
+        HIPCHK(hipStreamSynchronize(e->stream));
+        N.got = {H.entries, H.cell};
+        H.entries = ent; H.cell = cell; H.ent_cap = cap;
+    }
+    return TW_OK;
+}
+
+// the table emptied and refilled from the classes held (a grown table; a refused merge that had claimed slots)
+int chist_rehash(tw_engine* e) {
+    ChistDev& H = e->CH;
+    HIPCHK(hipMemsetAsync(H.table, 0, sizeof(unsigned long long) * (size_t)H.slots, e->stream));
+    const unsigned threads = flat_threads(e);
+    if (H.C > 0) hipLaunchKernelGGL(k_chist_insert, dim3(flat_grid(H.C, threads)), dim3(threads), 0, e->stream, H, (int64_t)0, H.C, 0);
+    HIPCHK(hipGetLastError());
+    return TW_OK;
+}
+
+// A table of at least two slots per class for `classes` classes: it at least doubles and is refilled from the classes held.
+int chist_table(tw_engine* e, int64_t classes) {
+    ChistDev& H = e->CH;
+    int64_t want = kChistSlots;
+    while (want < 2 * classes) want *= 2;
+    if (H.table != nullptr && want <= H.slots) return TW_OK;
+    want = std::max<int64_t>(want, 2 * H.slots);
+    ChistNew N;
+    unsigned long long* table;
+    CHIST_NEW(table, unsigned long long, want);
+    N.got = {H.table};
+    H.table = table; H.slots = want;
+    TWCHK(chist_rehash(e));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return TW_OK;
+}
+
+int chist_scratch(tw_engine* e, int64_t classes) {
+    ChistDev& H = e->CH;
+    ChistNew N;
+    if (H.counters == nullptr) {
+        CHIST_NEW(H.counters, unsigned long long, kChistCounters);
+        N.got.clear();
+    }
+    if (H.src_hash == nullptr || classes > e->ch_src_cap) {
+        const int64_t cap = std::max<int64_t>(classes, 2 * e->ch_src_cap);
+        unsigned long long *sh, *cs; int32_t *si, *ns;
+        CHIST_NEW(sh, unsigned long long, cap); CHIST_NEW(si, int32_t, cap); CHIST_NEW(ns, int32_t, cap); CHIST_NEW(cs, unsigned long long, cap / kSigScanItems + 2);
+        N.got = {H.src_hash, H.src_id, H.new_src, H.chunk_sum};
+        H.src_hash = sh; H.src_id = si; H.new_src = ns; H.chunk_sum = cs; e->ch_src_cap = cap;
+    }
+    return TW_OK;
+}
+
+int chist_fits(tw_engine* e, const std::string& fn, int32_t mode, int32_t n_groups) {
+    if (mode != 0 && mode != 1) return fail(e, TW_ERR_ARG, fn + ": mode outside {0 levels, 1 edges}");
+    if (n_groups < 1) return fail(e, TW_ERR_ARG, fn + ": n_groups must be positive");
+    if ((int64_t)n_groups > ((int64_t)1 << kSigGroupBits)) return fail(e, TW_ERR_UNSUPPORTED, fn + ": more than 2^20 groups");
+    if (e->ch_G != 0 && (mode != e->ch_mode || n_groups != e->ch_G))
+        return fail(e, TW_ERR_ARG, fn + ": the catalogue holds classes of mode " + std::to_string(e->ch_mode) + " over " + std::to_string(e->ch_G) + " groups, the source is of mode " +
+                                       std::to_string(mode) + " over " + std::to_string(n_groups) + " (tw_class_history_reset opens it again)");
+    return TW_OK;
+}
+
+// Hash, lookup and the scan's sums over the misses; new_classes / new_entries: what the catalogue does not hold.  Changes nothing
+// that is returned (mark: the hits are marked with the call's serial number, and two source classes that hit one class are refused).
+int chist_find(tw_engine* e, const std::string& fn, const ChistSrc& S, bool mark, int64_t& new_classes, int64_t& new_entries) {
+    ChistDev& H = e->CH;
+    const unsigned threads = flat_threads(e);
+    const int64_t nc = S.n_classes;
+    H.serial++;
+    H.hash_bits = e->K.sig_hash_bits;
+    HIPCHK(hipMemsetAsync(H.counters, 0, sizeof(unsigned long long) * kChistCounters, e->stream));
+    unsigned long long counters[kChistCounters] = {0, 0, 0, 0};
+    if (nc > 0) {
+        const WaveShape per_class = wave_shape(e, nc, kChistPack, kChistWaves);
+        hipLaunchKernelGGL(k_chist_lookup, per_class.grid, per_class.block, 0, e->stream, S, H, mark ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 1], e->stream));
+    if (nc > 0) {
+        const int64_t n_chunks = (nc + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
+        const ChistScan V{S, H};
+        hipLaunchKernelGGL(k_sig_scan_sums<ChistScan>, dim3((unsigned)n_chunks), dim3(threads), 0, e->stream, V, nc);
+        hipLaunchKernelGGL(k_sig_scan_chunks<ChistScan>, dim3(1), dim3(threads), 0, e->stream, V, n_chunks);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(counters, H.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (counters[2] != 0) return fail(e, TW_ERR_ARG, fn + ": two classes of the source have equal signatures (the catalogue is as it was)");
+    new_classes = (int64_t)(counters[0] >> 32);
+    new_entries = (int64_t)(counters[0] & 0xffffffffull);
+    return TW_OK;
+}
+
+void chist_summary(const tw_engine* e, int64_t new_classes, int64_t new_entries, int64_t held_classes, int64_t held_entries, int64_t src_classes, int64_t* summary) {
+    if (summary == nullptr) return;
+    summary[0] = new_classes; summary[1] = held_classes; summary[2] = new_entries; summary[3] = held_entries; summary[4] = e->ch_pushes; summary[5] = src_classes;
+}
+
+// A push or a merge of the source S (on the device).  Events SE_CHIST + 0 (recorded by the caller) .. + 3.
+int chist_absorb(tw_engine* e, const std::string& fn, const ChistSrc& S, int what, bool merge, int32_t* class_map, int64_t* summary) {
+    ChistDev& H = e->CH;
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads);
+    const int64_t nc = S.n_classes, ne = S.n_entries;
+    int64_t new_classes = 0, new_entries = 0;
+    TWCHK(chist_find(e, fn, S, true, new_classes, new_entries));
+    if (H.C + new_classes > (int64_t)INT32_MAX || H.E + new_entries > (int64_t)INT32_MAX)
+        return fail(e, TW_ERR_UNSUPPORTED, fn + ": more than 2^31 - 1 classes or entries in the catalogue (it is as it was)");
+    TWCHK(chist_reserve(e, H.C + new_classes, H.E + new_entries));
+    TWCHK(chist_table(e, H.C + new_classes));
+    if (new_classes > 0) {
+        const int64_t n_chunks = (nc + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
+        const ChistScan V{S, H};
+        hipLaunchKernelGGL(k_sig_scan_write<ChistScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, V, nc);
+        hipLaunchKernelGGL(k_chist_append, dim3(std::min(flat_grid(std::max(new_classes, new_entries), threads), 1u << 20)), tb, 0, e->stream, S, H, new_classes, new_entries);
+        hipLaunchKernelGGL(k_chist_insert, dim3(flat_grid(new_classes, threads)), tb, 0, e->stream, H, H.C, H.C + new_classes, merge ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        if (merge) {   // (the classes of a signature result differ by construction)
+            unsigned long long counters[kChistCounters];
+            HIPCHK(hipMemcpyAsync(counters, H.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            if (counters[2] != 0) {   // the new classes have claimed slots: the table again from the classes held
+                TWCHK(chist_rehash(e));
+                HIPCHK(hipStreamSynchronize(e->stream));
+                return fail(e, TW_ERR_ARG, fn + ": two classes of the source have equal signatures (the catalogue is as it was)");
+            }
+        }
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 2], e->stream));
+    const int64_t n_work = std::max<int64_t>(nc, (what & 2) != 0 ? ne : 0);
+    if (n_work > 0) {
+        hipLaunchKernelGGL(k_chist_accumulate, dim3(std::min(flat_grid(n_work, threads), 1u << 20)), tb, 0, e->stream, S, H, what);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 3], e->stream));
+    if (class_map != nullptr && nc > 0) HIPCHK(hipMemcpyAsync(class_map, H.src_id, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_CHIST, i, i + 1, &e->ch_ms[i]));
+    H.C += new_classes; H.E += new_entries;
+    e->ch_mode = S.mode; e->ch_G = S.n_groups; e->ch_pushes++;
+    chist_summary(e, new_classes, new_entries, H.C, H.E, nc, summary);
+    return TW_OK;
+}
+
+// the resident signature result (and, with what & 2, the resident class profile) as a source
+int chist_resident(tw_engine* e, const std::string& fn, int what, ChistSrc& S) {
+    if (!e->sig_ready)
+        return fail(e, TW_ERR_STATE, fn + " needs the result of a tw_trace_signatures call (tw_score_traces, new row groups and whatever drops the forest drop it)");
+    if ((what & 2) != 0 && !e->prof_ready)
+        return fail(e, TW_ERR_STATE, fn + ": what & 2 needs the result of a tw_class_profiles call on the resident signature result and attribution");
+    S = ChistSrc{};
+    S.n_classes = e->sig_summary[1]; S.n_entries = e->sig_summary[3];
+    S.off = e->G.class_off; S.entries = e->G.class_entries;
+    if ((what & 1) != 0) { S.cls[0] = e->G.class_trees; S.cls[1] = e->G.class_sum; S.cls[2] = e->G.class_min; S.cls[3] = e->G.class_max; }
+    if ((what & 2) != 0) {
+        S.cls[4] = e->F.class_counted; S.cls[5] = e->F.class_latency;
+        for (int c = 0; c < kProfCols; c++) S.cell[c] = (const int64_t*)e->F.cells + (int64_t)c * S.n_entries;
+    }
+    S.mode = e->sig_q.mode; S.n_groups = e->A.n_groups;
+    return TW_OK;
+}
+
+}  // namespace
+
+int tw_class_history_reset(tw_engine* e) {
+    if (e == nullptr) return TW_ERR_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    chist_free(e);
+    return TW_OK;
+}
+
+int tw_class_history_push(tw_engine* e, int32_t what, int64_t epoch, int32_t* class_map, int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (what < 1 || what > 3) return fail(e, TW_ERR_ARG, "tw_class_history_push: what outside {1 signatures, 2 profile, 3 both}");
+    ChistSrc S;
+    TWCHK(chist_resident(e, "tw_class_history_push", what, S));
+    S.epoch = epoch;
+    TWCHK(chist_fits(e, "tw_class_history_push", S.mode, S.n_groups));
+    HIPCHK(hipSetDevice(e->device));
+    TWCHK(chist_scratch(e, S.n_classes));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 0], e->stream));
+    return chist_absorb(e, "tw_class_history_push", S, what, false, class_map, summary);
+}
+
+int tw_class_history_match(tw_engine* e, int32_t* class_map, int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    ChistSrc S;
+    TWCHK(chist_resident(e, "tw_class_history_match", 1, S));
+    HIPCHK(hipSetDevice(e->device));
+    if (e->ch_G != 0 && (S.mode != e->ch_mode || S.n_groups != e->ch_G)) {   // classes of another mode or other groups: none is held
+        for (int64_t c = 0; class_map != nullptr && c < S.n_classes; c++) class_map[c] = -1;
+        chist_summary(e, S.n_classes, S.n_entries, e->CH.C, e->CH.E, S.n_classes, summary);
+        return TW_OK;
+    }
+    TWCHK(chist_scratch(e, S.n_classes));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 0], e->stream));
+    int64_t new_classes = 0, new_entries = 0;
+    TWCHK(chist_find(e, "tw_class_history_match", S, false, new_classes, new_entries));
+    if (class_map != nullptr && S.n_classes > 0) HIPCHK(hipMemcpyAsync(class_map, e->CH.src_id, sizeof(int32_t) * (size_t)S.n_classes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    chist_summary(e, new_classes, new_entries, e->CH.C, e->CH.E, S.n_classes, summary);
+    return TW_OK;
+}
+
+int tw_class_history_merge(tw_engine* e, const tw_class_catalogue* src, int64_t epoch, int32_t* class_map, int64_t* summary) {
+    if (e == nullptr || src == nullptr) return TW_ERR_ARG;
+    const std::string fn = "tw_class_history_merge";
+    const int64_t nc = src->n_classes, ne = src->n_entries;
+    if (nc < 0 || ne < 0 || src->class_off == nullptr) return fail(e, TW_ERR_ARG, fn + ": n_classes and n_entries must not be negative, class_off given");
+    if (nc > (int64_t)INT32_MAX || ne > (int64_t)INT32_MAX) return fail(e, TW_ERR_UNSUPPORTED, fn + ": more than 2^31 - 1 classes or entries in the source");
+    TWCHK(chist_fits(e, fn, src->mode, src->n_groups));
+    if (src->class_off[0] != 0) return fail(e, TW_ERR_ARG, fn + ": class_off must start at 0");
+    for (int64_t c = 0; c < nc; c++)
+        if (src->class_off[c + 1] < src->class_off[c]) return fail(e, TW_ERR_ARG, fn + ": class_off must not decrease");
+    if (src->class_off[nc] != ne) return fail(e, TW_ERR_ARG, fn + ": class_off must end at n_entries");
+    if (ne > 0 && src->class_entries == nullptr) return fail(e, TW_ERR_ARG, fn + ": no class_entries for " + std::to_string(ne) + " entries");
+    HIPCHK(hipSetDevice(e->device));
+    TWCHK(chist_scratch(e, nc));
+    // the source in one upload buffer: the offsets, the entries, then the figures that are given
+    const int64_t* cls[kChistClassCols] = {src->trees, src->latency_sum, src->latency_min, src->latency_max, src->counted, src->latency,
+                                           src->first_epoch, src->last_epoch, src->seen};
+    const int64_t* cell[kProfCols] = {src->rows, src->span_time, src->span_min, src->span_max, src->self_time, src->path_time, src->path_rows, src->path_trees,
+                                      src->offset};
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    size_t bytes = pad(sizeof(int64_t) * ((size_t)nc + 1)) + pad(sizeof(int32_t) * 4 * (size_t)ne);
+    for (const int64_t* p : cls) bytes += p != nullptr ? pad(sizeof(int64_t) * (size_t)nc) : 0;
+    for (const int64_t* p : cell) bytes += p != nullptr ? pad(sizeof(int64_t) * (size_t)ne) : 0;
+    if (e->ch_up == nullptr || bytes > e->ch_up_bytes) {
+        ChistNew N;
+        void* up = chist_new(e, N, (int64_t)bytes);
+        if (up == nullptr) return TW_ERR_DEVICE;
+        N.got = {e->ch_up};
+        e->ch_up = up; e->ch_up_bytes = bytes;
+    }
+    char* at = (char*)e->ch_up;
+    const auto upload = [&](const void* host, size_t b) -> const void* {
+        const void* dev = at;
+        if (b > 0 && hipMemcpyAsync(at, host, b, hipMemcpyHostToDevice, e->stream) != hipSuccess) return nullptr;
+        at += pad(b);
+        return dev;
+    };
+    ChistSrc S{};
+    S.n_classes = nc; S.n_entries = ne; S.epoch = epoch; S.mode = src->mode; S.n_groups = src->n_groups;
+    S.off = (const int64_t*)upload(src->class_off, sizeof(int64_t) * ((size_t)nc + 1));
+    S.entries = (const int32_t*)upload(src->class_entries, sizeof(int32_t) * 4 * (size_t)ne);
+    bool sent = S.off != nullptr && S.entries != nullptr;
+    for (int c = 0; c < kChistClassCols; c++)
+        if (cls[c] != nullptr) { S.cls[c] = (const int64_t*)upload(cls[c], sizeof(int64_t) * (size_t)nc); sent = sent && S.cls[c] != nullptr; }
+    for (int c = 0; c < kProfCols; c++)
+        if (cell[c] != nullptr) { S.cell[c] = (const int64_t*)upload(cell[c], sizeof(int64_t) * (size_t)ne); sent = sent && S.cell[c] != nullptr; }
+    if (!sent) { (void)hipGetLastError(); return fail(e, TW_ERR_DEVICE, fn + ": the upload of the source failed (the catalogue is as it was)"); }
+    // the source's entries, checked before anything is changed
+    HIPCHK(hipMemsetAsync(e->CH.counters, 0, sizeof(unsigned long long) * kChistCounters, e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_CHIST + 0], e->stream));
+    if (ne > 0) {
+        const unsigned threads = flat_threads(e);
+        hipLaunchKernelGGL(k_chist_check, dim3(flat_grid(ne, threads)), dim3(threads), 0, e->stream, S, e->CH.counters);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long counters[kChistCounters];
+    HIPCHK(hipMemcpyAsync(counters, e->CH.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (counters[1] != 0)
+        return fail(e, TW_ERR_ARG, fn + ": an entry of the source is out of range (level, cg, g, count) or a class' entries do not ascend strictly by (level, cg, g)");
+    return chist_absorb(e, fn, S, 3, true, class_map, summary);
+}
+
+int tw_class_history_info(tw_engine* e, int64_t* out6) {
+    if (e == nullptr || out6 == nullptr) return TW_ERR_ARG;
+    const bool held = e->ch_G != 0;
+    out6[0] = held ? e->CH.C : 0; out6[1] = held ? e->CH.E : 0; out6[2] = e->ch_pushes; out6[3] = held ? e->ch_mode : 0; out6[4] = e->ch_G;
+    out6[5] = held ? e->CH.slots : 0;
+    return TW_OK;
+}
+
+int tw_class_history_get(tw_engine* e, const tw_class_catalogue* out, int64_t* summary) {
+    if (e == nullptr) return TW_ERR_ARG;
+    if (e->ch_G == 0) return fail(e, TW_ERR_STATE, "tw_class_history_get on an empty catalogue (tw_class_history_push or tw_class_history_merge first; tw_class_history_reset empties it)");
+    if (summary != nullptr) TWCHK(tw_class_history_info(e, summary));
+    if (out == nullptr) return TW_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const ChistDev& H = e->CH;
+    const size_t nc = (size_t)H.C, ne = (size_t)H.E;
+    int64_t* cls[kChistClassCols] = {out->trees, out->latency_sum, out->latency_min, out->latency_max, out->counted, out->latency, out->first_epoch, out->last_epoch,
+                                     out->seen};
+    int64_t* cell[kProfCols] = {out->rows, out->span_time, out->span_min, out->span_max, out->self_time, out->path_time, out->path_rows, out->path_trees, out->offset};
+    TWCHK(copy_out(e, out->class_off, H.off, nc + 1));
+    if (ne > 0) TWCHK(copy_out(e, out->class_entries, H.entries, 4 * ne));
+    for (int c = 0; c < kChistClassCols && nc > 0; c++) TWCHK(copy_out(e, cls[c], H.cls + (int64_t)c * H.cls_cap, nc));
+    for (int c = 0; c < kProfCols && ne > 0; c++) TWCHK(copy_out(e, cell[c], H.cell + (int64_t)c * H.ent_cap, ne));
+    if (nc > 0 && (out->class_path_time != nullptr || out->class_top_entry != nullptr)) {
+        ChistNew N;   // (freed when the call returns)
+        int64_t* derived;
+        CHIST_NEW(derived, int64_t, 2 * (int64_t)nc);
+        const unsigned threads = flat_threads(e);
+        hipLaunchKernelGGL(k_chist_derive, dim3(flat_grid((int64_t)nc, threads)), dim3(threads), 0, e->stream, H, derived, derived + nc);
+        HIPCHK(hipGetLastError());
+        TWCHK(copy_out(e, out->class_path_time, derived, nc));
+        TWCHK(copy_out(e, out->class_top_entry, derived + nc, nc));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
     return TW_OK;
 }
 

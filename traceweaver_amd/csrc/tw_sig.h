@@ -281,72 +281,91 @@ __global__ void __launch_bounds__(256) k_sig_rep(StitchDev S, SigDev D, int64_t 
 }
 
 // Exclusive scan of (1, entries) over the reps in tree order, packed as classes << 32 | entries, in the manner of k_stitch_scan_*.
+// The three kernels take the view V they scan over (tw_chist.h scans the classes a catalogue does not hold with them): V.packed(t)
+// is item t's value, 0 = not counted; V.chunks() the per-workgroup sums [chunks + 1]; V.total(run) gets the sum over all items;
+// V.emit(t, run) the sum over the items before a counted item t.
 __device__ __forceinline__ unsigned long long sig_packed(const SigDev& D, int64_t t) {
     return D.rep[t] == (int32_t)t ? ((1ull << 32) | (unsigned long long)(uint32_t)D.tree_ent[t]) : 0ull;
 }
-__device__ __forceinline__ unsigned long long sig_thread_sum(const SigDev& D, int64_t first, int64_t n_trees) {
+struct SigScan {
+    SigDev D;
+    __device__ __forceinline__ unsigned long long packed(int64_t t) const { return sig_packed(D, t); }
+    __device__ __forceinline__ unsigned long long* chunks() const { return D.chunk_sum; }
+    __device__ __forceinline__ void total(unsigned long long run) const {
+        D.counters[6] = run;
+        D.class_off[run >> 32] = (int64_t)(run & 0xffffffffull);   // the end of the last class' entries
+    }
+    __device__ __forceinline__ void emit(int64_t t, unsigned long long run) const {
+        const int64_t c = (int64_t)(run >> 32);
+        D.tree_class[t] = (int32_t)c;
+        D.class_rep[c] = (int32_t)t;
+        D.class_off[c] = (int64_t)(run & 0xffffffffull);
+        D.class_trees[c] = 0;
+        D.class_sum[c] = 0;
+        D.class_min[c] = INT64_MAX;
+        D.class_max[c] = INT64_MIN;
+    }
+};
+template <class V>
+__device__ __forceinline__ unsigned long long sig_thread_sum(const V& v, int64_t first, int64_t n) {
     unsigned long long sum = 0;
     for (int k = 0; k < kSigScanItems; k++)
-        if (first + k < n_trees) sum += sig_packed(D, first + k);
+        if (first + k < n) sum += v.packed(first + k);
     return sum;
 }
 
-__global__ void __launch_bounds__(256) k_sig_scan_sums(SigDev D, int64_t n_trees) {
+template <class V>
+__global__ void __launch_bounds__(256) k_sig_scan_sums(V v, int64_t n) {
     __shared__ unsigned long long sh[256];
     const int64_t first = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * kSigScanItems;
-    sh[threadIdx.x] = sig_thread_sum(D, first, n_trees);
+    sh[threadIdx.x] = sig_thread_sum(v, first, n);
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long total = 0;
         for (int t = 0; t < (int)blockDim.x; t++) total += sh[t];
-        D.chunk_sum[blockIdx.x] = total;
+        v.chunks()[blockIdx.x] = total;
     }
 }
 
-__global__ void __launch_bounds__(256) k_sig_scan_chunks(SigDev D, int64_t n_chunks) {
+template <class V>
+__global__ void __launch_bounds__(256) k_sig_scan_chunks(V v, int64_t n_chunks) {
     __shared__ unsigned long long sh[256];
+    unsigned long long* chunk_sum = v.chunks();
     const int64_t per = (n_chunks + blockDim.x - 1) / blockDim.x;
     const int64_t lo = stitch_min((int64_t)threadIdx.x * per, n_chunks), hi = stitch_min(lo + per, n_chunks);
     unsigned long long sum = 0;
-    for (int64_t c = lo; c < hi; c++) sum += D.chunk_sum[c];
+    for (int64_t c = lo; c < hi; c++) sum += chunk_sum[c];
     sh[threadIdx.x] = sum;
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long run = 0;
-        for (int t = 0; t < (int)blockDim.x; t++) { const unsigned long long v = sh[t]; sh[t] = run; run += v; }
-        D.counters[6] = run;
-        D.class_off[run >> 32] = (int64_t)(run & 0xffffffffull);   // the end of the last class' entries
+        for (int t = 0; t < (int)blockDim.x; t++) { const unsigned long long x = sh[t]; sh[t] = run; run += x; }
+        v.total(run);
     }
     __syncthreads();
     unsigned long long run = sh[threadIdx.x];
-    for (int64_t c = lo; c < hi; c++) { const unsigned long long v = D.chunk_sum[c]; D.chunk_sum[c] = run; run += v; }
+    for (int64_t c = lo; c < hi; c++) { const unsigned long long x = chunk_sum[c]; chunk_sum[c] = run; run += x; }
 }
 
-__global__ void __launch_bounds__(256) k_sig_scan_write(SigDev D, int64_t n_trees) {
+template <class V>
+__global__ void __launch_bounds__(256) k_sig_scan_write(V v, int64_t n) {
     __shared__ unsigned long long sh[256];
     const int64_t first = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * kSigScanItems;
-    sh[threadIdx.x] = sig_thread_sum(D, first, n_trees);
+    sh[threadIdx.x] = sig_thread_sum(v, first, n);
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long run = 0;
-        for (int t = 0; t < (int)blockDim.x; t++) { const unsigned long long v = sh[t]; sh[t] = run; run += v; }
+        for (int t = 0; t < (int)blockDim.x; t++) { const unsigned long long x = sh[t]; sh[t] = run; run += x; }
     }
     __syncthreads();
-    unsigned long long run = D.chunk_sum[blockIdx.x] + sh[threadIdx.x];
+    unsigned long long run = v.chunks()[blockIdx.x] + sh[threadIdx.x];
     for (int k = 0; k < kSigScanItems; k++) {
         const int64_t t = first + k;
-        if (t >= n_trees) break;
-        const unsigned long long v = sig_packed(D, t);
-        if (v != 0) {
-            const int64_t c = (int64_t)(run >> 32);
-            D.tree_class[t] = (int32_t)c;
-            D.class_rep[c] = (int32_t)t;
-            D.class_off[c] = (int64_t)(run & 0xffffffffull);
-            D.class_trees[c] = 0;
-            D.class_sum[c] = 0;
-            D.class_min[c] = INT64_MAX;
-            D.class_max[c] = INT64_MIN;
-            run += v;
+        if (t >= n) break;
+        const unsigned long long x = v.packed(t);
+        if (x != 0) {
+            v.emit(t, run);
+            run += x;
         }
     }
 }

@@ -752,6 +752,94 @@ class Engine(object):
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 31))
         return dict(zip(("sweep", "classes", "copies"), ms[28:31].tolist()))
 
+    # ---- the class catalogue: call-graph classes kept across batches (tw_class_history_*, csrc/tw_chist.h) ----
+    def class_history_reset(self):
+        """Empties the class catalogue (tw_class_history_reset): no classes, mode and number of groups open again."""
+        self._check(self._lib.tw_class_history_reset(self._h))
+
+    def class_history_push(self, what=3, epoch=0):
+        """Adds the classes of the last signatures() -- and, with what & 2, the figures of the last class_profiles() -- to the
+        catalogue on the device (tw_class_history_push): a class whose signature the catalogue holds keeps that class' id, the
+        others are appended in the batch's order.  what: 1 the signature result's trees and latencies, 2 the profile's figures
+        only, 3 both -- which falls back to 1 when no profile is resident.  epoch: a label of the caller's, kept as first / last
+        epoch per class.  The catalogue survives loads, new row maps, stitches and passes; only class_history_reset() and
+        close() end it.  Returns (class_map [the batch's classes] = catalogue ids, summary6 = new classes, classes held, new
+        entries, entries held, pushes and merges since the reset, classes of the batch)."""
+        off = getattr(self, "_sig_resident", (0, np.zeros(1, dtype=np.int64), None))[1]
+        class_map = np.full(max(len(off) - 1, 1), -1, dtype=np.int32)
+        summary = np.zeros(6, dtype=np.int64)
+        rc = self._lib.tw_class_history_push(self._h, int(what), int(epoch), _vp(class_map), _vp(summary))
+        if rc == -4 and int(what) == 3 and b"what & 2" in self._lib.tw_last_error(self._h):   # the default without a resident profile
+            rc = self._lib.tw_class_history_push(self._h, 1, int(epoch), _vp(class_map), _vp(summary))
+        self._check(rc)
+        return class_map[:int(summary[5])].copy(), summary
+
+    def class_history_match(self):
+        """The catalogue ids of the classes of the last signatures(), -1 for a class the catalogue does not hold
+        (tw_class_history_match); changes nothing.  With TraceSignatures.tree_class it names the traces of a shape never seen."""
+        off = getattr(self, "_sig_resident", (0, np.zeros(1, dtype=np.int64), None))[1]
+        class_map = np.full(max(len(off) - 1, 1), -1, dtype=np.int32)
+        summary = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_class_history_match(self._h, _vp(class_map), _vp(summary)))
+        return class_map[:int(summary[5])].copy()
+
+    def class_history_merge(self, source, epoch=0):
+        """A push from the host (tw_class_history_merge).  source: a traces.ClassHistory -- a catalogue read back, another
+        engine's, one of traces.read_class_history_npz, or ClassHistory.from_batch(signatures, profiles or None, n_groups) of
+        another engine's batch.  Figures that are None add nothing.  The source's entries are checked on the device before
+        anything changes.  Returns (class_map, summary6) as class_history_push()."""
+        from .traces import ClassHistory
+
+        src = source
+        nc, ne = src.n_classes, src.n_entries
+        off = np.ascontiguousarray(src.class_off, dtype=np.int64).ravel()
+        entries = np.ascontiguousarray(src.class_entries, dtype=np.int32).reshape(-1, 4)
+        if len(off) != nc + 1:
+            raise ValueError("class_history_merge: class_off does not match the source's classes")
+        figures = []
+        for k, n in [(k, nc) for k in ClassHistory.CLASS_FIELDS] + [(k, ne) for k in ClassHistory.ENTRY_FIELDS]:
+            a = getattr(src, k)
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.int64).ravel()
+            if a is not None and len(a) != n:
+                raise ValueError("class_history_merge: %s does not match the source's classes and entries" % k)
+            figures.append(a)
+        ptr = lambda a: None if a is None or a.size == 0 else _vp(a)                    # noqa: E731
+        cat = _ffi.ClassCatalogue(nc, len(entries), int(src.mode), int(src.n_groups), _vp(off), ptr(entries), *([ptr(a) for a in figures] + [None, None]))
+        class_map = np.full(max(nc, 1), -1, dtype=np.int32)
+        summary = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_class_history_merge(self._h, ctypes.byref(cat), int(epoch), _vp(class_map), _vp(summary)))
+        return class_map[:nc].copy(), summary
+
+    def class_history_info(self):
+        """tw_class_history_info: classes, entries, pushes (and merges) since the reset, mode, groups, capacity of the hash table
+        in slots; all 0 for an empty catalogue."""
+        out = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_class_history_info(self._h, _vp(out)))
+        return dict(zip(("classes", "entries", "pushes", "mode", "groups", "capacity"), out.tolist()))
+
+    def class_history(self):
+        """The catalogue read back (tw_class_history_get: a call for the sizes, a call that copies).  Returns traces.ClassHistory."""
+        from .traces import ClassHistory
+
+        sizes = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_class_history_get(self._h, None, _vp(sizes)))
+        nc, ne = int(sizes[0]), int(sizes[1])
+        off = np.zeros(nc + 1, dtype=np.int64)
+        entries = np.zeros((ne, 4), dtype=np.int32)
+        per_class = [np.zeros(nc, dtype=np.int64) for _ in ClassHistory.CLASS_FIELDS]
+        per_entry = [np.zeros(ne, dtype=np.int64) for _ in ClassHistory.ENTRY_FIELDS]
+        derived = [np.zeros(nc, dtype=np.int64) for _ in range(2)]
+        cat = _ffi.ClassCatalogue(0, 0, 0, 0, *[_vp(a) if a.size else None for a in [off, entries] + per_class + per_entry + derived])
+        self._check(self._lib.tw_class_history_get(self._h, ctypes.byref(cat), None))
+        return ClassHistory(off, entries, *(per_class + per_entry + derived), mode=int(sizes[3]), n_groups=int(sizes[4]))
+
+    def class_history_timing(self):
+        """The last class_history_push() / class_history_merge() on the device (HIP events, ms): hash and lookup; scan, append,
+        insert and any rehash; accumulate."""
+        ms = np.zeros(46, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 46))
+        return dict(zip(("lookup", "insert", "accumulate"), ms[43:46].tolist()))
+
     # ------------------------------------------------------------------------------------------
     def baseline(self, kind):
         """The reference's FCFS ("FCFS", algorithms/fcfs.py) or vPath ("vPath", algorithms/vpath.py; needs set_truth) on the

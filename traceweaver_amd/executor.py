@@ -139,6 +139,13 @@ def parse_args(argv=None):
                          "shape which the delay-culprit query selects (--query_percentile, --query_after), for the predicted and for the "
                          "true traces; write both to this .npz and print the largest classes with the call that holds most of their "
                          "critical path.  Needs --stitch_out's conditions")
+    ap.add_argument("--class_history", type=q, default=None,
+                    help="--profiles_out or --signatures_out: keep this run's call graphs in a catalogue across runs "
+                         "(tw_class_history_push): the file is read into the device catalogue if it exists (tw_class_history_merge), the "
+                         "predicted traces' classes are matched against it (which shapes are new), added on the device -- with "
+                         "--profiles_out their profiles too -- and the store is written back.  The store's services and signature mode "
+                         "must be this run's.  Default: off, nothing changes")
+    ap.add_argument("--class_history_epoch", type=int, default=0, help="--class_history: the label of this run (first / last epoch per call graph)")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
                          "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
@@ -239,6 +246,10 @@ def unsupported(args):
         problems.append("--signatures_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.profiles_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--profiles_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.class_history and not (args.profiles_out or args.signatures_out):
+        problems.append("--class_history without --profiles_out or --signatures_out (it keeps that run's call graphs)")
+    if args.class_history_epoch != 0 and not args.class_history:
+        problems.append("--class_history_epoch without --class_history")
     if args.profiles_out and not 0.0 <= args.query_percentile < 1.0:
         problems.append("--query_percentile outside [0, 1)")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
@@ -384,12 +395,35 @@ def signatures_out(args, eng, corpus, table, pass_, has_truth=True):
     traces.write_signatures_npz(args.signatures_out, names, pred, true)
     print("Call graphs (%s): %d among %d whole traces%s" % (args.signature_mode, pred.n_classes, pred.n_eligible,
                                                            "; true traces: %d among %d" % (true.n_classes, true.n_eligible) if true is not None else ""))
+    if args.class_history and not args.profiles_out:
+        class_history_out(args, eng, names, 1)
     if true is not None:
         print("Shape accuracy: %d of %d whole traces have the call graph of the true trace" % (pred.summary[5], pred.summary[4]))
     for row in pred.table(names)[:3 if not args.verbose else None]:
         print("  %6d traces, mean %.1f us (min %d, max %d): %s" % (
             row["trees"], row["mean_latency"], row["min_latency"], row["max_latency"],
             " | ".join("L%d %s%s x%d" % (lv, "%s>" % cg if cg is not None else "", g, k) for lv, cg, g, k in row["signature"]) or "(no service)"))
+
+
+def class_history_out(args, eng, names, what):
+    """--class_history: the store read into the device catalogue, the classes of the predicted forest (resident on the device, with
+    what = 3 their profile too) matched against it and pushed, the catalogue written back."""
+    from . import traces
+
+    names = [str(x) for x in names]
+    if os.path.exists(args.class_history):
+        store, group_names = traces.read_class_history_npz(args.class_history)
+        if group_names != names:
+            raise SystemExit("--class_history %s: the store holds the services %s, this run %s" % (args.class_history, ", ".join(group_names), ", ".join(names)))
+        if traces.SIGNATURE_MODES[store.mode] != args.signature_mode:
+            raise SystemExit("--class_history %s: the store holds %s signatures, this run %s" % (args.class_history, traces.SIGNATURE_MODES[store.mode], args.signature_mode))
+        eng.class_history_reset()
+        eng.class_history_merge(store)
+    new = int((eng.class_history_match() < 0).sum())
+    _, summary = eng.class_history_push(what, args.class_history_epoch)
+    c = eng.class_history()
+    traces.write_class_history_npz(args.class_history, c, names)
+    print("Class history: %d call graphs in this run, %d of them new; %d held over %d traces" % (summary[5], new, c.n_classes, int(c.trees.sum())))
 
 
 def profiles_out(args, eng, corpus, table, pass_, has_truth=True):
@@ -410,6 +444,8 @@ def profiles_out(args, eng, corpus, table, pass_, has_truth=True):
         sides.append(eng.class_profiles())
     pred, true = sides[-1], sides[0] if has_truth else None
     traces.write_profiles_npz(args.profiles_out, names, pred, true)
+    if args.class_history:
+        class_history_out(args, eng, names, 3)
     print("Class profiles (%s): %d traces of %d call graphs counted, %d rows in %d entries%s" % (
         args.signature_mode, pred.summary[0], pred.summary[1], pred.summary[2], pred.summary[3],
         "; true traces: %d of %d" % (true.summary[0], true.summary[1]) if true is not None else ""))

@@ -1149,3 +1149,216 @@ def write_profiles_npz(path, names, pred, true=None):
             out.update({prefix + k: getattr(p, k) for k in ClassProfiles.FIELDS + ("class_off", "class_entries")})
     with open(path, "wb") as f:
         np.savez_compressed(f, **out)
+
+
+INT64_MAX, INT64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
+
+
+def _wrap64(x):
+    """A Python integer as the int64 the device's wrapping sum holds."""
+    return ((int(x) + (1 << 63)) % (1 << 64)) - (1 << 63)
+
+
+class ClassHistory(object):
+    """The class catalogue (include/traceweaver_amd.h has the definitions): call-graph classes whose ids hold across batches.
+    Class k owns class_entries[class_off[k]:class_off[k + 1]], rows (level, caller group, group, count).  Per class (int64):
+    trees, latency_sum, latency_min / latency_max (INT64_MAX / INT64_MIN without a tree) of the signature results pushed;
+    counted, latency of the class profiles pushed; first_epoch, last_epoch, seen (the pushes and merges whose source held the
+    class).  Per entry (int64): PROFILE_ENTRY_FIELDS, added up (span_min / span_max: the least and the greatest).  Derived:
+    class_path_time, class_top_entry (the catalogue's global index of the entry with the largest path_time among those with a
+    row on the path, -1 none).  A figure that is None (a source of Engine.class_history_merge only) adds nothing."""
+
+    CLASS_FIELDS = ("trees", "latency_sum", "latency_min", "latency_max", "counted", "latency", "first_epoch", "last_epoch", "seen")
+    ENTRY_FIELDS = PROFILE_ENTRY_FIELDS
+    DERIVED_FIELDS = ("class_path_time", "class_top_entry")
+    FIELDS = ("class_off", "class_entries") + CLASS_FIELDS + ENTRY_FIELDS + DERIVED_FIELDS
+
+    def __init__(self, class_off, class_entries, trees=None, latency_sum=None, latency_min=None, latency_max=None, counted=None, latency=None,
+                 first_epoch=None, last_epoch=None, seen=None, rows=None, span_time=None, span_min=None, span_max=None, self_time=None,
+                 path_time=None, path_rows=None, path_trees=None, offset=None, class_path_time=None, class_top_entry=None, mode=0, n_groups=0):
+        self.class_off = np.asarray(class_off, dtype=np.int64)
+        self.class_entries = np.asarray(class_entries, dtype=np.int32).reshape(-1, 4)
+        given = dict(locals())
+        for k in self.CLASS_FIELDS + self.ENTRY_FIELDS + self.DERIVED_FIELDS:
+            setattr(self, k, None if given[k] is None else np.asarray(given[k], dtype=np.int64))
+        self.mode, self.n_groups = int(mode), int(n_groups)
+
+    n_classes = property(lambda self: len(self.class_off) - 1)
+    n_entries = property(lambda self: len(self.class_entries))
+
+    @classmethod
+    def from_batch(cls, signatures, profiles, n_groups):
+        """One batch as a source of Engine.class_history_merge / a part's figures: a TraceSignatures and, or None, the
+        ClassProfiles that belongs to it."""
+        s, p = signatures, profiles
+        extra = {} if p is None else dict({f: getattr(p, f) for f in PROFILE_ENTRY_FIELDS}, counted=p.class_counted, latency=p.class_latency)
+        return cls(s.class_off, s.class_entries, s.class_trees, s.class_latency_sum, s.class_latency_min, s.class_latency_max, mode=s.mode,
+                   n_groups=n_groups, **extra)
+
+    def entries(self, k):
+        """The signature of class k: an [n, 4] view of class_entries."""
+        k = int(k)
+        if not 0 <= k < self.n_classes:
+            raise IndexError(k)
+        return self.class_entries[int(self.class_off[k]):int(self.class_off[k + 1])]
+
+    def signature(self, k):
+        """... as a tuple of (level, caller group, group, count) tuples."""
+        return tuple(tuple(int(x) for x in row) for row in self.entries(k))
+
+    def profile(self, k):
+        """The aggregate trace of class k over everything pushed: its entries in signature order, each a dict of the entry's global
+        index, (level, caller, group, count) and ENTRY_FIELDS."""
+        out = []
+        for i in range(int(self.class_off[int(k)]), int(self.class_off[int(k) + 1])):
+            lv, cg, g, n = (int(x) for x in self.class_entries[i])
+            row = {"entry": i, "class": int(k), "level": lv, "caller": cg, "group": g, "count": n}
+            row.update({f: int(getattr(self, f)[i]) for f in self.ENTRY_FIELDS})
+            out.append(row)
+        return out
+
+    def figures(self, k):
+        """The per-class figures of class k, the derived ones and its entries' figures (lists in signature order), as a dict -- the
+        top entry as its position within the class, so that catalogues which number their classes differently compare equal."""
+        k = int(k)
+        a, b = int(self.class_off[k]), int(self.class_off[k + 1])
+        out = {f: int(getattr(self, f)[k]) for f in self.CLASS_FIELDS + ("class_path_time",)}
+        top = int(self.class_top_entry[k])
+        out["top_entry"] = top - a if top >= 0 else -1
+        out.update({f: [int(x) for x in getattr(self, f)[a:b]] for f in self.ENTRY_FIELDS})
+        return out
+
+    def by_signature(self):
+        """{signature tuple: figures(k)}: what two catalogues are compared through where their ids legitimately differ."""
+        return {self.signature(k): self.figures(k) for k in range(self.n_classes)}
+
+    def table(self, names=None):
+        """One dict per class, sorted by trees descending (ties: the id): id, trees, share of all trees, mean / min / max latency
+        (None without a tree), first / last epoch, seen, top_entry (global index, -1 none) with top = its (level, caller,
+        service) and top_share = its share of the class' path time, and the signature with the groups' names (the caller None in
+        mode "levels")."""
+        name = lambda g: g if names is None or g < 0 else names[g]                      # noqa: E731
+        total = max(int(np.asarray(self.trees).sum()), 1)
+        rows = []
+        for k in sorted(range(self.n_classes), key=lambda k: (-int(self.trees[k]), k)):
+            n, i, path = int(self.trees[k]), int(self.class_top_entry[k]), int(self.class_path_time[k])
+            sig = [(lv, name(cg) if self.mode == 1 else None, name(g), c) for lv, cg, g, c in self.signature(k)]
+            row = {"id": k, "trees": n, "share": float(n) / total, "mean_latency": float(self.latency_sum[k]) / n if n else None,
+                   "min_latency": int(self.latency_min[k]) if n else None, "max_latency": int(self.latency_max[k]) if n else None,
+                   "first_epoch": int(self.first_epoch[k]), "last_epoch": int(self.last_epoch[k]), "seen": int(self.seen[k]), "top_entry": i, "top": None,
+                   "top_share": 0.0, "signature": sig}
+            if i >= 0:
+                lv, cg, g, _ = (int(x) for x in self.class_entries[i])
+                row.update({"top": (lv, name(cg) if self.mode == 1 else None, name(g)), "top_share": float(self.path_time[i]) / path if path else 0.0})
+            rows.append(row)
+        return rows
+
+    def same_as(self, other):
+        return self.mode == other.mode and all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def class_history_host(parts):
+    """What the class catalogue holds after Engine.class_history_push / class_history_merge of `parts`, in turn, on an empty
+    catalogue, restated with a dict keyed by the signature tuple and Python integers, for the tests.  parts: a list of (source,
+    profiles, what, epoch); source is a TraceSignatures (profiles: the ClassProfiles that belongs to it, or None; what as
+    tw_class_history_push takes it) or a ClassHistory (a merge: profiles and what are not read, every figure that is not None is
+    added; first_epoch / last_epoch / seen None = epoch and 1).  The first part fixes the mode -- and, from a ClassHistory, the
+    number of groups the entries are checked against.  Raises ValueError for what the device refuses with TW_ERR_ARG."""
+    ids, sigs, cls, cells = {}, [], [], []
+    mode, G = None, None
+    for src, prof, what, epoch in parts:
+        merge = isinstance(src, ClassHistory)
+        if not merge and what not in (1, 2, 3):
+            raise ValueError("class_history_host: what outside {1, 2, 3}")
+        if mode is not None and src.mode != mode:
+            raise ValueError("class_history_host: a part of another mode")
+        if merge:
+            if src.n_groups < 1 or (G is not None and src.n_groups != G):
+                raise ValueError("class_history_host: a part of another number of groups")
+            off = [int(x) for x in src.class_off]
+            if off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] != src.n_entries:
+                raise ValueError("class_history_host: class_off does not start at 0, decreases or does not end at the entries")
+            seen_sigs = set()
+            for k in range(src.n_classes):
+                sig = src.signature(k)
+                keys = [e[:3] for e in sig]
+                ok = all(a < b for a, b in zip(keys, keys[1:])) and all(
+                    0 <= lv < (1 << 16) and 0 <= g < src.n_groups and c >= 1 and (-1 <= cg < src.n_groups if src.mode == 1 else cg == 0) for lv, cg, g, c in sig)
+                if not ok or sig in seen_sigs:
+                    raise ValueError("class_history_host: an entry out of range, entries that do not ascend or two equal classes in a source")
+                seen_sigs.add(sig)
+            G = src.n_groups
+        mode = src.mode
+        get = (lambda f: getattr(src, f)) if merge else (lambda f: None)
+        if not merge:
+            per_class = {}
+            if what & 1:
+                per_class.update(trees=src.class_trees, latency_sum=src.class_latency_sum, latency_min=src.class_latency_min, latency_max=src.class_latency_max)
+            if what & 2:
+                per_class.update(counted=prof.class_counted, latency=prof.class_latency)
+            get = lambda f: per_class.get(f) if f in ClassHistory.CLASS_FIELDS else (getattr(prof, f) if what & 2 else None)   # noqa: E731
+        for k in range(src.n_classes):
+            sig = src.signature(k)
+            if sig not in ids:
+                ids[sig] = len(sigs)
+                sigs.append(sig)
+                cls.append(dict(trees=0, latency_sum=0, latency_min=INT64_MAX, latency_max=INT64_MIN, counted=0, latency=0, first_epoch=INT64_MAX,
+                                last_epoch=INT64_MIN, seen=0))
+                cells.append([{f: INT64_MAX if f == "span_min" else INT64_MIN if f == "span_max" else 0 for f in PROFILE_ENTRY_FIELDS} for _ in sig])
+            c = cls[ids[sig]]
+            for f in ("trees", "latency_sum", "counted", "latency"):
+                if get(f) is not None:
+                    c[f] += int(get(f)[k])
+            if get("latency_min") is not None:
+                c["latency_min"] = min(c["latency_min"], int(get("latency_min")[k]))
+            if get("latency_max") is not None:
+                c["latency_max"] = max(c["latency_max"], int(get("latency_max")[k]))
+            first, last, seen = (get(f) if merge else None for f in ("first_epoch", "last_epoch", "seen"))
+            c["first_epoch"] = min(c["first_epoch"], int(epoch) if first is None else int(first[k]))
+            c["last_epoch"] = max(c["last_epoch"], int(epoch) if last is None else int(last[k]))
+            c["seen"] += 1 if seen is None else int(seen[k])
+            for j in range(len(sig)):
+                i, cell = int(src.class_off[k]) + j, cells[ids[sig]][j]
+                for f in PROFILE_ENTRY_FIELDS:
+                    if get(f) is not None:
+                        v = int(get(f)[i])
+                        cell[f] = min(cell[f], v) if f == "span_min" else max(cell[f], v) if f == "span_max" else cell[f] + v
+    if mode is None:
+        raise ValueError("class_history_host: no parts")
+    off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    entries = np.array([e for s in sigs for e in s], dtype=np.int32).reshape(-1, 4)
+    per_class = [np.array([_wrap64(c[f]) for c in cls], dtype=np.int64) for f in ClassHistory.CLASS_FIELDS]
+    per_entry = [np.array([_wrap64(cell[f]) for cs in cells for cell in cs], dtype=np.int64) for f in PROFILE_ENTRY_FIELDS]
+    path_time, path_rows = per_entry[5], per_entry[6]
+    class_path_time, class_top = np.zeros(len(sigs), dtype=np.int64), np.full(len(sigs), -1, dtype=np.int64)
+    for k in range(len(sigs)):
+        a, b = int(off[k]), int(off[k + 1])
+        class_path_time[k] = _wrap64(sum(int(x) for x in path_time[a:b]))
+        on = [i for i in range(a, b) if path_rows[i] != 0]
+        if on:
+            class_top[k] = min(on, key=lambda i: (-int(path_time[i]), i))
+    return ClassHistory(off, entries, *(per_class + per_entry + [class_path_time, class_top]), mode=mode, n_groups=0 if G is None else G)
+
+
+def write_class_history_npz(path, catalogue, group_names):
+    """A catalogue read back (Engine.class_history) as one .npz: the arrays of ClassHistory.FIELDS, the mode and the names of the
+    groups.  read_class_history_npz gives what Engine.class_history_merge takes."""
+    c = catalogue
+    if len(group_names) != c.n_groups:
+        raise ValueError("write_class_history_npz: the names do not match the catalogue's groups")
+    with open(path, "wb") as f:
+        np.savez_compressed(f, mode=np.array(SIGNATURE_MODES[c.mode]), n_groups=np.int64(c.n_groups), group_names=np.array([str(x) for x in group_names]),
+                            **{k: getattr(c, k) for k in ClassHistory.FIELDS})
+
+
+def read_class_history_npz(path):
+    """-> (ClassHistory, group_names): the first is an argument of Engine.class_history_merge."""
+    with np.load(path) as z:
+        mode, G = SIGNATURE_MODES.index(str(z["mode"])), int(z["n_groups"])
+        names = [str(x) for x in z["group_names"].tolist()]
+        c = ClassHistory(*[z[k] for k in ClassHistory.FIELDS], mode=mode, n_groups=G)
+    sizes = [len(getattr(c, k)) for k in ClassHistory.CLASS_FIELDS + ClassHistory.DERIVED_FIELDS] + [len(c.class_off) - 1]
+    if len(names) != G or set(sizes) != {c.n_classes} or {len(getattr(c, k)) for k in ClassHistory.ENTRY_FIELDS} != {c.n_entries} or \
+            (len(c.class_off) and int(c.class_off[-1]) != c.n_entries):
+        raise ValueError("%s: not a class catalogue (the arrays do not match its classes, entries and groups)" % path)
+    return c, names

@@ -272,7 +272,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * The history (HIP events): ms[38] plan and ms[39] merge kernel of the last tw_history_push / tw_history_merge, ms[40] quantiles and
  * histogram of the last tw_history_distributions, ms[41], ms[42] observed statistics and permutation walk of the last tw_history_compare.
  * The class catalogue (HIP events): ms[43] hash and lookup, ms[44] scan, append, insert and any rehash, ms[45] accumulate of the
- * last tw_class_history_push / tw_class_history_merge. */
+ * last tw_class_history_push / tw_class_history_merge.
+ * The last tw_filter_traces (HIP events): ms[46] the tree kernel (rows, clauses, terms, the bit), ms[47] the list of the matched
+ * trees (count, scan, write), ms[48] the copies to the host. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -834,6 +836,91 @@ typedef struct {
     int64_t *class_counted, *class_latency, *class_path_time, *class_top_entry;
 } tw_class_profile;
 int tw_class_profiles(tw_engine *e, const tw_class_profile *out, int64_t *summary6);
+
+/* ---- traces selected by a predicate: a flag bit every stage reads (csrc/tw_filt.h) ------------------------------------
+ *
+ * Extends: the reference's one hard-coded query (src/query_engine/delay_culprit.py:19-28: whole traces, the slowest X %,
+ * started after Y), which is all that the stages above select by.  tw_score_traces already writes one bit
+ * (TW_TREE_CONFIDENT) into the device forest's tree_flags that every later stage can select by through need_flags; this is
+ * the general form: a predicate over the stitched trees, evaluated on the device, whose result is bit TW_TREE_MATCH.  One
+ * call makes tw_attribute_traces, tw_latency_distributions, tw_compare_cohorts, tw_history_push, tw_trace_signatures,
+ * tw_class_profiles and tw_class_history_push work on "the traces that match" (need_flags | TW_TREE_MATCH).
+ *
+ * Definitions (integer microseconds; a row with end < start counts as end = start, as in the attribution; sums wrap in two's
+ * complement):
+ *   query       n_clauses <= TW_FILT_MAX_CLAUSES clauses, each in one of TW_FILT_MAX_TERMS terms: the predicate is the OR over
+ *               the terms that have a clause of the AND over the term's clauses.
+ *   value       of clause j on tree t, by subject:
+ *                 0 LATENCY  tree_latency[t]
+ *                 1 ROWS     tree_off[t + 1] - tree_off[t]
+ *                 2 START    row_start of the root
+ *                 3 CLASS    tree_class[t] of the resident signature result (-1 for a tree that result did not class)
+ *                 4 GROUP    over the tree's rows with row_group == group (group -1: with row_group >= 0) the reduction
+ *                            (0 sum, 1 min, 2 max) of the metric: 0 the count, 1 the duration, 2 self_time, 3 path_time, 4 the
+ *                            count of those rows that are on the critical path (the rows tw_attribute_traces counts in
+ *                            group_path_rows).  Metrics 0 and 4 are sums.
+ *                 5 EDGE     the same over the tree's signature items of one edge: the server rows with row_group == group
+ *                            whose cg == caller, cg exactly as mode 1 of tw_trace_signatures defines it (the row_group of
+ *                            the nearest server ancestor, -1 if there is none or its group is -1).  Metrics 0 (count) and 1
+ *                            (duration).
+ *               A sum over no rows is 0.  A min or max over no rows is no value: clause_value holds INT64_MIN and the clause
+ *               does not hold, negated or not.  group, caller, metric and reduce are read for GROUP and EDGE only.
+ *               clause_value is written for every tree, eligible or not.
+ *   holds       lo <= value <= hi, then negated when negate != 0.
+ *   eligible    flags hold every bit of need_flags and none of skip_flags, as in the attribution (the flags as they are
+ *               before the call: a query may name TW_TREE_MATCH and so narrow the last match).
+ *   match       an eligible tree matches iff n_clauses == 0 or every clause of some term that has one holds.  A tree that is
+ *               not eligible never matches and is counted nowhere.
+ *   effect      bit 4 (TW_TREE_MATCH) of the device forest's tree_flags is cleared and rewritten for every tree.  Before the
+ *               first call it is never set; a new tw_stitch_traces makes a new forest without it, and the tree_flags that
+ *               call returns never show it.  tw_score_traces keeps it (it masks its own bit only).  One bit: a second
+ *               filter replaces the first.
+ *   outputs     tree_match [n_trees]; match_trees: the matched trees in ascending order, summary6[1] of them (room for
+ *               n_trees); clause_value [n_trees][n_clauses]; clause_trees [n_clauses]: eligible trees on which the clause
+ *               holds; term_trees [TW_FILT_MAX_TERMS]: eligible trees on which every clause of the term holds, 0 for a term
+ *               without a clause.  `out` and any array may be NULL.
+ *   summary6    eligible trees, matched trees, the sum / the minimum (INT64_MAX without a match) / the maximum (INT64_MIN
+ *               without one) of tree_latency over the matched trees, the rows of the matched trees.
+ *
+ * TW_ERR_STATE: before a stitch or before tw_set_row_groups (an EDGE clause needs no more than that: the forest and the
+ * groups, where tw_trace_signatures refuses without them); a clause of metric 2, 3 or 4 without a resident attribution; a
+ * CLASS clause without a resident signature result.  TW_ERR_ARG: n_clauses outside [0, 16]; a term, subject, metric or reduce
+ * out of range; a group outside [-1, n_groups) (EDGE: [0, n_groups)) or a caller outside [-1, n_groups); lo > hi; a reduce
+ * other than sum on metric 0 or 4.  A refused call leaves the bit and everything resident as it was.
+ * Residency: the call reads first and drops afterwards -- the attribution (with the distribution items and the class profile)
+ * and the signature result (with the class profile) only where the query they were made with named the bit (need_flags |
+ * skip_flags holds TW_TREE_MATCH); a result whose query does not name the bit cannot depend on it and stays.  The history
+ * and the class catalogue hold copies and are untouched.
+ * Limits: 16 clauses in 8 terms; no clause on a cohort, a decision margin or a catalogue id; no witness row; one bit; one
+ * engine's batch and the selected assignment.  Results do not depend on scheduling: no floating point; the atomics are
+ * integer adds, minima, maxima and ors of which only the result is read, and the list of the matched trees is written by a
+ * scan, not by a cursor.  Timing: tw_get_timing slots 46..48 (the tree kernel; the list; the copies; HIP events, ms). */
+#define TW_TREE_MATCH 16
+#define TW_FILT_MAX_CLAUSES 16
+#define TW_FILT_MAX_TERMS 8
+typedef struct {
+    int32_t term;      /* 0 .. TW_FILT_MAX_TERMS-1: the conjunction this clause belongs to */
+    int32_t subject;   /* 0 LATENCY, 1 ROWS, 2 START, 3 CLASS, 4 GROUP, 5 EDGE */
+    int32_t group;     /* GROUP: g in [0, G), or -1 = every row with row_group >= 0.  EDGE: the callee g in [0, G) */
+    int32_t caller;    /* EDGE: cg in [-1, G) */
+    int32_t metric;    /* GROUP: 0 rows, 1 span (duration), 2 self_time, 3 path_time, 4 rows on the critical path.  EDGE: 0 rows, 1 span */
+    int32_t reduce;    /* 0 sum, 1 min, 2 max (metric 0 and 4: sum only) */
+    int32_t negate;
+    int64_t lo, hi;    /* the clause holds iff lo <= value <= hi, then negated */
+} tw_filter_clause;
+typedef struct {
+    uint32_t need_flags, skip_flags;
+    int32_t n_clauses;
+    const tw_filter_clause *clauses;
+} tw_filter_query;
+typedef struct {
+    uint8_t *tree_match;      /* [n_trees] */
+    int32_t *match_trees;     /* [n_trees] capacity, summary6[1] entries written, ascending */
+    int64_t *clause_value;    /* [n_trees][n_clauses], INT64_MIN = no value */
+    int64_t *clause_trees;    /* [n_clauses] eligible trees on which the clause holds */
+    int64_t *term_trees;      /* [TW_FILT_MAX_TERMS] eligible trees on which every clause of the term holds; 0 for an unused term */
+} tw_filter_result;
+int tw_filter_traces(tw_engine *e, const tw_filter_query *q, const tw_filter_result *out, int64_t *summary6);
 
 /* ---- the classes of batch after batch: a catalogue on the device (csrc/tw_chist.h) --------------------------------
  *

@@ -31,6 +31,7 @@
 #include "tw_hist.h"
 #include "tw_sig.h"
 #include "tw_prof.h"
+#include "tw_filt.h"
 #include "tw_chist.h"
 #include "tw_order.h"
 
@@ -41,7 +42,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_CHIST = 37, SE_COUNT = 41 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8 + 4
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_CHIST = 37, SE_FILT = 41, SE_COUNT = 45 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8 + 4 + 4
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -254,6 +255,7 @@ struct tw_engine {
     bool stitched_truth = false;            // ground truth was set when the forest was stitched: its flags carry bit 2
     AttrDev A{};                            // tw_set_row_groups / tw_attribute_traces (tw_attr.h)
     bool groups_set = false, attributed = false;
+    uint32_t attr_need = 0, attr_skip = 0;  // the flags the resident attribution selected by (tw_filter_traces drops it where they name its bit)
     int64_t groups_cap = 0, attr_rows_cap = 0;
     ConfDev C{};                            // tw_get_decisions / tw_score_traces (tw_conf.h): the decisions are those of the resident pass
     int64_t conf_rows_cap = 0;
@@ -290,6 +292,8 @@ struct tw_engine {
     ProfDev F{};                            // tw_class_profiles (tw_prof.h); prof_ready: the profile of the resident signature result and the
     bool prof_ready = false;                // resident attribution is resident, a further call only copies
     int64_t prof_ent_cap = 0, prof_cls_cap = 0, prof_rows_cap = 0, prof_summary[6] = {0, 0, 0, 0, 0, 0};
+    FiltDev FL{};                           // tw_filter_traces (tw_filt.h): scratch of a call; what outlives it is bit TW_TREE_MATCH of S.tree_flags
+    int64_t filt_trees_cap = 0, filt_val_cap = 0;
     // HIP events around the parts of a stage (SE_*: a stage's first event; created by tw_create) and what tw_get_timing reports of them
     hipEvent_t stage_ev[SE_COUNT] = {};
     double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
@@ -298,6 +302,7 @@ struct tw_engine {
     double ds_ms[3] = {0, 0, 0};            // items and counts; sort, offsets and values; quantiles and histogram
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
+    double fl_ms[3] = {0, 0, 0};            // trace filter: the tree kernel; the list of the matched trees; the copies
     double cm_ms[2] = {0, 0};               // ranks, pool and observed statistics; the permutation walk
     double hs_ms[5] = {0, 0, 0, 0, 0};      // history: plan (with the source check of a merge), merge; quantiles and histogram; observed statistics, permutation walk
     double ch_ms[3] = {0, 0, 0};            // class catalogue: hash and lookup; scan, append, insert and any rehash; accumulate
@@ -421,6 +426,12 @@ int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
      signature        sig_ready      tw_trace_signatures  <- forest, row groups.  Dropped by tw_score_traces (it rewrites the CONFIDENT
        result                                                bit that a query may select by) and by a call with another query
      class profile    prof_ready     tw_class_profiles    <- signature result, attribution
+     match bit        (bit 4 of the    tw_filter_traces     <- forest, row groups: it lives in the forest's tree_flags and goes with the
+                      forest's flags)                          forest (a new stitch writes new flags without it).  A call rewrites it
+                                                             for every tree, after it has read what its clauses name, and then drops
+                                                             the attribution and the signature result where the query they were made
+                                                             with named the bit (need_flags | skip_flags & 16): a result whose query
+                                                             does not name the bit cannot depend on it and stays
      history          hist_C > 0     tw_history_push / tw_history_merge <- nothing: it holds copies.  Dropped by tw_history_reset and
                                                              tw_destroy only (its buffers are not a load's: free_all leaves them)
      class catalogue  ch_G > 0       tw_class_history_push / tw_class_history_merge <- nothing: it holds copies.  Dropped by
@@ -447,6 +458,7 @@ void drop_buffers(tw_engine* e) {
     e->D = DistDev{}; e->cohort_rows_cap = 0; e->dist_trees_cap = 0; e->dist_seg_cap = 0; e->dist_out_cap = 0; e->dist_items = 0;   // cohort labels, items
     e->G = SigDev{}; e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;   // signatures, reference set
     e->F = ProfDev{}; e->prof_ent_cap = 0; e->prof_cls_cap = 0; e->prof_rows_cap = 0;                  // class profile
+    e->FL = FiltDev{}; e->filt_trees_cap = 0; e->filt_val_cap = 0;                                     // scratch of the trace filter
     e->M = CmpDev{}; e->cmp_rows_cap = 0; e->cmp_items_cap = 0;                                        // scratch of the cohort comparison
 }
 
@@ -2084,6 +2096,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     for (int i = 0; i < 2 && 35 + i < n; i++) ms[35 + i] = (double)e->fit_spec_count[i];   // the last refit: rows that adopted the fit made ahead / that were fitted after the selection
     if (n > 37) ms[37] = e->fit_order_host_ms;                            // ... and the host's time for its order tables
     for (int i = 0; i < 3 && 43 + i < n; i++) ms[43 + i] = e->ch_ms[i];   // the last tw_class_history_push / _merge
+    for (int i = 0; i < 3 && 46 + i < n; i++) ms[46 + i] = e->fl_ms[i];   // the last tw_filter_traces
     for (int i = 0; i < 5 && 38 + i < n; i++) ms[38 + i] = e->hs_ms[i];   // the last tw_history_push / _merge (38, 39), _distributions (40), _compare (41, 42)
     return TW_OK;
 }
@@ -2706,6 +2719,7 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
             if (cols[c] != nullptr)
                 for (int64_t g = 0; g < G; g++) cols[c][g] = (int64_t)totals[(size_t)(c * G + g)];
     }
+    e->attr_need = q->need_flags; e->attr_skip = q->skip_flags;
     e->attributed = true;
     return TW_OK;
 }
@@ -3542,6 +3556,105 @@ int tw_class_profiles(tw_engine* e, const tw_class_profile* out, int64_t* summar
     } else if (out != nullptr) {
         HIPCHK(hipStreamSynchronize(e->stream));
     }
+    return TW_OK;
+}
+
+/* ---- traces selected by a predicate: a flag bit every stage reads (tw_filt.h) --------------------------------------------- */
+int tw_filter_traces(tw_engine* e, const tw_filter_query* q, const tw_filter_result* out, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    TWCHK(need_forest(e, "tw_filter_traces"));
+    if (!e->groups_set) return fail(e, TW_ERR_STATE, "tw_filter_traces before tw_set_row_groups (dropped with the row maps)");
+    const int nc = q->n_clauses;
+    if (nc < 0 || nc > TW_FILT_MAX_CLAUSES || (nc > 0 && q->clauses == nullptr)) return fail(e, TW_ERR_ARG, "tw_filter_traces: n_clauses outside [0, 16]");
+    const int32_t G = e->A.n_groups;
+    FiltQueryDev Q{};
+    Q.need_flags = q->need_flags; Q.skip_flags = q->skip_flags; Q.n_clauses = nc;
+    bool times = false, classes = false;
+    for (int j = 0; j < nc; j++) {
+        const tw_filter_clause& c = q->clauses[j];
+        const std::string at = "tw_filter_traces: clause " + std::to_string(j) + ": ";
+        if (c.term < 0 || c.term >= TW_FILT_MAX_TERMS) return fail(e, TW_ERR_ARG, at + "term outside [0, 8)");
+        if (c.subject < FILT_LATENCY || c.subject > FILT_EDGE) return fail(e, TW_ERR_ARG, at + "subject outside [0, 5]");
+        if (c.lo > c.hi) return fail(e, TW_ERR_ARG, at + "lo > hi");
+        FiltClauseDev& d = Q.c[j];
+        d.subject = c.subject; d.term = c.term; d.negate = c.negate != 0 ? 1 : 0; d.lo = c.lo; d.hi = c.hi;
+        Q.term_used |= 1u << c.term;
+        if (c.subject == FILT_CLASS) classes = true;
+        if (c.subject != FILT_GROUP && c.subject != FILT_EDGE) continue;   // (group, caller, metric and reduce are read for these two only)
+        const bool edge = c.subject == FILT_EDGE;
+        if (c.metric < 0 || c.metric > (edge ? 1 : 4)) return fail(e, TW_ERR_ARG, at + (edge ? "metric outside [0, 1] of an EDGE clause" : "metric outside [0, 4]"));
+        if (c.reduce < 0 || c.reduce > 2) return fail(e, TW_ERR_ARG, at + "reduce outside {0 sum, 1 min, 2 max}");
+        if ((c.metric == 0 || c.metric == 4) && c.reduce != 0) return fail(e, TW_ERR_ARG, at + "a count (metric 0, 4) is summed: reduce must be 0");
+        if (c.group < (edge ? 0 : -1) || c.group >= G) return fail(e, TW_ERR_ARG, at + (edge ? "group outside [0, n_groups)" : "group outside [-1, n_groups)"));
+        if (edge && (c.caller < -1 || c.caller >= G)) return fail(e, TW_ERR_ARG, at + "caller outside [-1, n_groups)");
+        d.group = c.group; d.caller = edge ? c.caller : 0; d.metric = c.metric; d.reduce = c.reduce;
+        Q.row_mask |= 1u << j;
+        if (edge) Q.cols |= FILT_COL_CALLER;
+        Q.cols |= c.metric == 1 ? FILT_COL_SPAN : c.metric == 2 ? FILT_COL_SELF : c.metric == 3 ? FILT_COL_PATH : c.metric == 4 ? FILT_COL_FLAG : 0;
+        if (c.metric >= 2) times = true;
+    }
+    if (times && !e->attributed)
+        return fail(e, TW_ERR_STATE, "tw_filter_traces: a clause on self_time, path_time or the rows on the path needs a tw_attribute_traces call on the current forest");
+    if (classes && !e->sig_ready)
+        return fail(e, TW_ERR_STATE, "tw_filter_traces: a CLASS clause needs the result of a tw_trace_signatures call (tw_score_traces, new row groups and whatever "
+                                     "drops the forest drop it)");
+    HIPCHK(hipSetDevice(e->device));
+    const StitchDev& S = e->S;
+    FiltDev& F = e->FL;
+    const int64_t nt = e->st_trees;
+    if (F.counters == nullptr) DEV_ALLOC(F.counters, kFiltCounters);   // (all of them freed with the batch)
+    if (F.tree_match == nullptr || nt > e->filt_trees_cap) {
+        DEV_ALLOC(F.tree_match, nt); DEV_ALLOC(F.match_trees, nt); DEV_ALLOC(F.chunk_sum, nt / kSigScanItems + 2);
+        e->filt_trees_cap = std::max<int64_t>(nt, 1);
+    }
+    if (F.clause_value == nullptr || nt * nc > e->filt_val_cap) {
+        DEV_ALLOC(F.clause_value, nt * nc);
+        e->filt_val_cap = std::max<int64_t>(nt * nc, 1);
+    }
+    F.row_group = e->A.row_group; F.self_time = e->A.self_time; F.path_time = e->A.path_time; F.row_flag = e->A.row_flag;
+    F.tree_class = e->G.tree_class;
+    unsigned long long counters[kFiltCounters] = {};
+    counters[kFiltMinAt] = ~0ull;   // (the least key; the greatest starts at 0)
+    HIPCHK(hipMemcpyAsync(F.counters, counters, sizeof(counters), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_FILT + 0], e->stream));
+    const WaveShape per_tree = wave_shape(e, nt, kFiltTrees, kFiltWaves);
+    if (nt > 0) hipLaunchKernelGGL(k_filt_trees, per_tree.grid, per_tree.block, 0, e->stream, S, F, Q, nt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->stage_ev[SE_FILT + 1], e->stream));
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads);
+    const int64_t n_chunks = (nt + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems);
+    if (nt > 0) {   // count, scan, list
+        hipLaunchKernelGGL(k_sig_scan_sums<FiltScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, FiltScan{F}, nt);
+        hipLaunchKernelGGL(k_sig_scan_chunks<FiltScan>, dim3(1), tb, 0, e->stream, FiltScan{F}, n_chunks);
+        hipLaunchKernelGGL(k_sig_scan_write<FiltScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, FiltScan{F}, nt);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->stage_ev[SE_FILT + 2], e->stream));
+    HIPCHK(hipMemcpyAsync(counters, F.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    // the bit is rewritten: what was selected by it goes (read first, dropped afterwards)
+    if (e->attributed && ((e->attr_need | e->attr_skip) & TW_TREE_MATCH) != 0) drop_attribution(e);
+    if (e->sig_ready && ((e->sig_q.need_flags | e->sig_q.skip_flags) & TW_TREE_MATCH) != 0) drop_sig(e);
+    const int64_t matched = (int64_t)counters[1];
+    if (summary != nullptr) {
+        summary[0] = (int64_t)counters[0]; summary[1] = matched; summary[2] = (int64_t)counters[2];
+        summary[3] = matched > 0 ? (int64_t)(counters[kFiltMinAt] ^ (1ull << 63)) : INT64_MAX;
+        summary[4] = matched > 0 ? (int64_t)(counters[kFiltMaxAt] ^ (1ull << 63)) : INT64_MIN;
+        summary[5] = (int64_t)counters[5];
+    }
+    if (out != nullptr) {
+        TWCHK(copy_out(e, out->tree_match, F.tree_match, (size_t)nt));
+        TWCHK(copy_out(e, out->match_trees, F.match_trees, (size_t)matched));
+        TWCHK(copy_out(e, out->clause_value, F.clause_value, (size_t)(nt * nc)));
+        if (out->clause_trees != nullptr)
+            for (int j = 0; j < nc; j++) out->clause_trees[j] = (int64_t)counters[kFiltClauseAt + j];
+        if (out->term_trees != nullptr)
+            for (int k = 0; k < TW_FILT_MAX_TERMS; k++) out->term_trees[k] = (int64_t)counters[kFiltTermAt + k];
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_FILT + 3], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_FILT, i, i + 1, &e->fl_ms[i]));
     return TW_OK;
 }
 

@@ -87,6 +87,13 @@ __device__ __forceinline__ unsigned long long sig_pack(int32_t level, unsigned l
     return ((unsigned long long)level << (kSigCallerBits + kSigGroupBits)) | (c << kSigGroupBits) | (unsigned long long)g;
 }
 
+// The caller group of server row r (mode 1; the EDGE clauses of tw_filt.h): the group of its nearest server ancestor, -1 without one.
+__device__ __forceinline__ int32_t sig_caller_group(const StitchDev& S, const int32_t* row_group, int32_t r) {
+    int32_t p = S.link[r];   // (the stitch refuses cycles; two hops in a valid table)
+    while (p >= 0 && S.row_kind[p] != 1) p = S.link[p];
+    return p >= 0 ? row_group[p] : -1;
+}
+
 // Level and item key of row r (k_sig_items; k_prof_rows of tw_prof.h computes a row's key again with it): kSigNone for a row that is
 // no item; `deep` is set for a server row whose level does not fit the key.
 __device__ __forceinline__ unsigned long long sig_item_key(const StitchDev& S, const SigDev& D, int32_t r, int32_t& level, bool& deep) {
@@ -99,12 +106,7 @@ __device__ __forceinline__ unsigned long long sig_item_key(const StitchDev& S, c
         if (level >= (1 << kSigLevelBits)) {
             deep = true;
         } else if (g >= 0) {
-            unsigned long long c = 1;
-            if (D.mode == 1) {
-                int32_t p = S.link[r];   // (the stitch refuses cycles; two hops in a valid table)
-                while (p >= 0 && S.row_kind[p] != 1) p = S.link[p];
-                c = p >= 0 ? (unsigned long long)(D.row_group[p] + 1) : 0ull;
-            }
+            const unsigned long long c = D.mode == 1 ? (unsigned long long)(sig_caller_group(S, D.row_group, r) + 1) : 1ull;
             key = sig_pack(level, c, g);
         }
     }

@@ -752,6 +752,35 @@ class Engine(object):
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 31))
         return dict(zip(("sweep", "classes", "copies"), ms[28:31].tolist()))
 
+    def filter_traces(self, clauses=(), need_flags=1, skip_flags=0):
+        """Selects the trees of the last stitch() by a predicate, on the device (tw_filter_traces): `clauses` are traces.clause(...)
+        tuples (or what traces.parse_filter returns), clauses of one term ANDed, the terms ORed; an eligible tree (flags hold
+        need_flags, none of skip_flags) matches when some term holds, every eligible tree with no clause at all.  The match becomes
+        bit traces.MATCH of the forest's flags on the device: attribute(need_flags=WHOLE | MATCH), signatures(need_flags=WHOLE |
+        MATCH) and what follows them then work on the matched traces.  Clauses on self / path time need the last attribute(), a
+        class clause the last signatures().  Returns traces.TraceFilter."""
+        from .traces import TraceFilter
+
+        clauses = [tuple(int(x) for x in c) for c in clauses]
+        nt, nc = max(int(getattr(self, "_n_trees", 0)), 1), len(clauses)
+        table = (_ffi.FilterClause * max(nc, 1))(*[_ffi.FilterClause(*c) for c in clauses])
+        q = _ffi.FilterQuery(int(need_flags), int(skip_flags), nc, table)
+        match = np.zeros(nt, dtype=np.uint8)
+        listed = np.empty(nt, dtype=np.int32)
+        value = np.empty((nt, nc), dtype=np.int64)
+        clause_trees, term_trees, summary = np.zeros(nc, dtype=np.int64), np.zeros(_ffi.TW_FILT_MAX_TERMS, dtype=np.int64), np.zeros(6, dtype=np.int64)
+        out = _ffi.FilterResult(*[_vp(a) for a in (match, listed, value, clause_trees, term_trees)])
+        self._check(self._lib.tw_filter_traces(self._h, ctypes.byref(q), ctypes.byref(out), _vp(summary)))
+        k = int(getattr(self, "_n_trees", 0))
+        return TraceFilter(match[:k].copy(), listed[:int(summary[1])].copy(), value[:k].copy(), clause_trees, term_trees, summary, clauses)
+
+    def filter_timing(self):
+        """The last filter_traces() on the device (HIP events, ms): the tree kernel (rows, clauses, terms, the bit); the list of the
+        matched trees; the copies."""
+        ms = np.zeros(49, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 49))
+        return dict(zip(("trees", "list", "copies"), ms[46:49].tolist()))
+
     # ---- the class catalogue: call-graph classes kept across batches (tw_class_history_*, csrc/tw_chist.h) ----
     def class_history_reset(self):
         """Empties the class catalogue (tw_class_history_reset): no classes, mode and number of groups open again."""

@@ -146,6 +146,15 @@ def parse_args(argv=None):
                          "--profiles_out their profiles too -- and the store is written back.  The store's services and signature mode "
                          "must be this run's.  Default: off, nothing changes")
     ap.add_argument("--class_history_epoch", type=int, default=0, help="--class_history: the label of this run (first / last epoch per call graph)")
+    ap.add_argument("--trace_filter", type=q, default=None,
+                    help="select the stitched traces by a predicate on the device (tw_filter_traces) before --attribute_out, --latency_out, "
+                         "--compare_out, --history, --signatures_out, --profiles_out and --class_history, which then work on the whole traces "
+                         "that match: terms separated by |, a term's clauses by &, a leading ! negates; a clause is SUBJECT followed by >=V, "
+                         "<=V, ==V or `in LO..HI` (integers, us) with SUBJECT one of latency, rows, start, class, METRIC[.REDUCE][SERVICE] or "
+                         "METRIC[.REDUCE][CALLER>SERVICE] -- METRIC one of count, span, self, path, onpath, REDUCE one of sum, min, max, "
+                         "SERVICE * = any counted service, CALLER - = no caller; e.g. 'latency>=20000 & !count[cache]>=1 | span.max[search]>=5000'.  "
+                         "At most 16 clauses in 8 terms.  Needs --stitch_out's conditions.  Default: off, nothing changes")
+    ap.add_argument("--filter_out", type=q, default=None, help="--trace_filter: write the matched traces, the clauses' values and counts to this .npz")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
                          "tuple and the best other one, per trace the weakest decision, a calibration table against ground truth), write "
@@ -252,6 +261,10 @@ def unsupported(args):
         problems.append("--class_history_epoch without --class_history")
     if args.profiles_out and not 0.0 <= args.query_percentile < 1.0:
         problems.append("--query_percentile outside [0, 1)")
+    if args.trace_filter and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--trace_filter without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.filter_out and not args.trace_filter:
+        problems.append("--filter_out without --trace_filter")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--confidence_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
     if args.confidence_out and args.fit != "device-batch":
@@ -339,6 +352,32 @@ def confidence_out(args, eng, st):
             print("    %-32s %7d whole traces, %7d exact, %8d decisions" % (span, row["trees"], row["exact"], row["decisions"]))
 
 
+def trace_filter(args, eng, names, report=False):
+    """--trace_filter on the forest just stitched (the row groups are set): the times and the classes its clauses read computed once,
+    then the filter over the whole traces.  Returns the flag the later stages add to need_flags: traces.MATCH, 0 without the option.
+    report: the predicted forest's first filter -- print the counts and write --filter_out."""
+    from . import traces
+
+    if not args.trace_filter:
+        return 0
+    try:
+        clauses = traces.parse_filter(args.trace_filter, names)
+    except ValueError as ex:
+        raise SystemExit("--trace_filter: %s" % ex)
+    if any(c[1] >= 4 and c[4] >= 2 for c in clauses):
+        eng.attribute()                                           # (of the whole traces: its query does not name the bit, the filter leaves it)
+    if any(c[1] == 3 for c in clauses):
+        eng.signatures(args.signature_mode)
+    f = eng.filter_traces(clauses, traces.WHOLE, 0)
+    if report:
+        if args.filter_out:
+            traces.write_filter_npz(args.filter_out, f, names)
+        print("Trace filter: %d of %d whole traces match %s" % (f.n_matched, f.n_eligible, traces.format_filter(clauses, names)))
+        for row in f.table([str(x) for x in names]) if args.verbose else ():
+            print("    %-8s %-48s holds on %d traces" % ("clause %d" % row["clause"] if "clause" in row else "term %d" % row["term"], row["text"], row["trees"]))
+    return traces.MATCH
+
+
 def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solved=None):
     """--stitch_out: all services in one batch, the assignments they were given, the span table's rows -> traces on the device.
     solved: the engine that still holds the batch and the pass these assignments came from (--confidence_out)."""
@@ -357,6 +396,10 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         eng.set_span_rows(*traces.rows_from_units(units, table))
         eng.set_parents(parents)
         st = eng.stitch(0)
+    if args.trace_filter:
+        group, names = traces.groups_from_table(table, corpus)
+        eng.set_row_groups(group, len(names))
+        trace_filter(args, eng, names, report=True)
     if args.attribute_out or args.latency_out:
         attribute_out(args, eng, st, corpus, table)
     if args.signatures_out:
@@ -389,9 +432,9 @@ def signatures_out(args, eng, corpus, table, pass_, has_truth=True):
     true = None
     if has_truth:
         eng.stitch(truth=True)
-        true = eng.signatures(args.signature_mode, keep_reference=True)
+        true = eng.signatures(args.signature_mode, need_flags=traces.WHOLE | trace_filter(args, eng, names), keep_reference=True)
     eng.stitch(pass_)
-    pred = eng.signatures(args.signature_mode, compare=has_truth)
+    pred = eng.signatures(args.signature_mode, need_flags=traces.WHOLE | trace_filter(args, eng, names), compare=has_truth)
     traces.write_signatures_npz(args.signatures_out, names, pred, true)
     print("Call graphs (%s): %d among %d whole traces%s" % (args.signature_mode, pred.n_classes, pred.n_eligible,
                                                            "; true traces: %d among %d" % (true.n_classes, true.n_eligible) if true is not None else ""))
@@ -439,8 +482,9 @@ def profiles_out(args, eng, corpus, table, pass_, has_truth=True):
             eng.stitch(truth=True)
         else:
             eng.stitch(pass_)
-        eng.signatures(args.signature_mode)
-        eng.attribute(percentile=args.query_percentile, start_min=args.query_after)
+        need = traces.WHOLE | trace_filter(args, eng, names)
+        eng.signatures(args.signature_mode, need_flags=need)
+        eng.attribute(percentile=args.query_percentile, start_min=args.query_after, need_flags=need)
         sides.append(eng.class_profiles())
     pred, true = sides[-1], sides[0] if has_truth else None
     traces.write_profiles_npz(args.profiles_out, names, pred, true)
@@ -547,7 +591,8 @@ def attribute_out(args, eng, st, corpus, table):
         label, cohort_names = cohort_labels(args, corpus, table, names)
         eng.set_row_cohorts(label, len(cohort_names))
     query = dict(percentile=args.query_percentile, start_min=args.query_after)
-    a = eng.attribute(need_flags=traces.WHOLE | (traces.CONFIDENT if args.query_confident else 0), **query)
+    match = traces.MATCH if args.trace_filter else 0              # (stitch_out has filtered this forest)
+    a = eng.attribute(need_flags=traces.WHOLE | (traces.CONFIDENT if args.query_confident else 0) | match, **query)
     if args.attribute_out:
         traces.write_attribution_npz(args.attribute_out, a, names, st)
         print(culprit_line(a, names))
@@ -570,7 +615,7 @@ def attribute_out(args, eng, st, corpus, table):
         history_out(args, eng, d, names, a.culprit)
     if args.verbose:
         eng.stitch(truth=True)
-        b = eng.attribute(**query)
+        b = eng.attribute(need_flags=traces.WHOLE | trace_filter(args, eng, names), **query)
         if args.attribute_out:
             print(culprit_line(b, names, "Delay culprit (true traces)"))
         if args.latency_out and b.culprit >= 0:
@@ -755,7 +800,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out or args.profiles_out:
+            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out or args.profiles_out or args.trace_filter:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
                            solved=solved)
         else:

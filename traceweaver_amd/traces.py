@@ -26,6 +26,11 @@ tree_same on the host and gives the share of traces with the true signature, `wr
 Engine.class_profiles (tw_class_profiles, csrc/tw_prof.h) joins the last two: per class and signature entry the times of the selected
 trees of that shape -- the aggregate trace of a class.  `ClassProfiles` is the result, `class_profiles_host` restates the definitions
 with dictionaries from the host results of `signatures_host` and `attribute_host`, `write_profiles_npz` stores results.
+
+Engine.filter_traces (tw_filter_traces, csrc/tw_filt.h) selects the stitched traces by a predicate and marks them with bit MATCH of
+the device forest's flags, which all of the above select by: `clause` builds a clause, `parse_filter` / `format_filter` are the
+command line's language, `TraceFilter` is the result, `filter_host` restates the definitions with loops over the rows of a tree for
+the tests, `write_filter_npz` stores a result.
 """
 import sys
 
@@ -1362,3 +1367,264 @@ def read_class_history_npz(path):
             (len(c.class_off) and int(c.class_off[-1]) != c.n_entries):
         raise ValueError("%s: not a class catalogue (the arrays do not match its classes, entries and groups)" % path)
     return c, names
+
+
+# ---- traces selected by a predicate: Engine.filter_traces (tw_filter_traces, csrc/tw_filt.h) ---------------------------------------
+MATCH = 16                           # bit of the device forest's tree_flags after Engine.filter_traces (Engine.attribute(need_flags=WHOLE | MATCH))
+FILTER_MAX_CLAUSES, FILTER_MAX_TERMS = 16, 8
+FILTER_SUBJECTS = ("latency", "rows", "start", "class", "group", "edge")
+FILTER_METRICS = ("count", "span", "self", "path", "onpath")     # of a group / edge clause: rows, duration, self_time, path_time, rows on the critical path
+FILTER_REDUCES = ("sum", "min", "max")
+NO_VALUE = INT64_MIN                 # clause_value of a min / max over no rows
+
+
+def clause(subject, lo=None, hi=None, term=0, group=-1, caller=-1, metric="count", reduce="sum", negate=False):
+    """One clause of a filter, the tuple Engine.filter_traces takes: (term, subject, group, caller, metric, reduce, negate, lo, hi).
+    subject: one of FILTER_SUBJECTS; "group" reads group (-1: every counted row), "edge" group and caller (-1: no caller); metric
+    and reduce by name (FILTER_METRICS, FILTER_REDUCES).  The clause holds where lo <= value <= hi (None: unbounded), then negated."""
+    index = lambda names, x: names.index(x) if isinstance(x, str) else int(x)
+    return (int(term), index(FILTER_SUBJECTS, subject), int(group), int(caller), index(FILTER_METRICS, metric), index(FILTER_REDUCES, reduce),
+            1 if negate else 0, INT64_MIN if lo is None else int(lo), INT64_MAX if hi is None else int(hi))
+
+
+def format_clause(c, names=None):
+    """A clause tuple in the language of parse_filter (groups by name when `names` is given, by number otherwise)."""
+    term, subject, group, caller, metric, reduce, negate, lo, hi = (int(x) for x in c)
+    name = lambda g, none: none if g < 0 else (str(g) if names is None else str(names[g]))
+    if subject < 4:
+        what = FILTER_SUBJECTS[subject]
+    else:
+        what = FILTER_METRICS[metric] + ("" if reduce == 0 else "." + FILTER_REDUCES[reduce])
+        what += "[%s]" % name(group, "*") if subject == 4 else "[%s>%s]" % (name(caller, "-"), name(group, "*"))
+    if lo == hi:
+        cmp_ = "==%d" % lo
+    elif hi == INT64_MAX:
+        cmp_ = ">=%d" % lo
+    elif lo == INT64_MIN:
+        cmp_ = "<=%d" % hi
+    else:
+        cmp_ = " in %d..%d" % (lo, hi)
+    return ("!" if negate else "") + what + cmp_
+
+
+def format_filter(clauses, names=None):
+    """Clause tuples as one expression: the terms in ascending order joined by ' | ', a term's clauses by ' & '."""
+    terms = sorted({int(c[0]) for c in clauses})
+    return " | ".join(" & ".join(format_clause(c, names) for c in clauses if int(c[0]) == k) for k in terms)
+
+
+def parse_filter(expr, names):
+    """The command line's filter language -> clause tuples.  `|` separates terms (numbered from 0), `&` the clauses of a term, a
+    leading `!` negates.  A clause is SUBJECT COMPARISON with SUBJECT one of latency, rows, start, class, METRIC[.REDUCE][SERVICE]
+    (a group clause; `*` = any counted service) or METRIC[.REDUCE][CALLER>SERVICE] (an edge clause; `-` = no caller), METRIC one of
+    count, span, self, path, onpath, REDUCE one of sum (the default), min, max, the brackets literal; COMPARISON one of >=V, <=V,
+    ==V, `in LO..HI`, integers in microseconds.  names: the groups' names (services) in group order.  ValueError names the piece
+    that is wrong: an unknown service, subject, metric or reduction, a ninth term, a seventeenth clause."""
+    import re
+
+    names = [str(x) for x in names]
+
+    def service(x, piece, star):
+        x = x.strip()
+        if x == star:
+            return -1
+        if x not in names:
+            raise ValueError("filter clause %r: unknown service %r" % (piece, x))
+        return names.index(x)
+
+    out = []
+    terms = str(expr).split("|")
+    for k, term in enumerate(terms):
+        if k >= FILTER_MAX_TERMS:
+            raise ValueError("filter term %d (%r): at most %d terms" % (k + 1, term.strip(), FILTER_MAX_TERMS))
+        for piece in term.split("&"):
+            piece = piece.strip()
+            m = re.match(r"^(!?)\s*([a-z]+)(?:\.([a-z]+))?\s*(?:\[([^\]]*)\])?\s*(>=|<=|==|in\s)\s*(.+)$", piece)
+            if m is None:
+                raise ValueError("filter clause %r: not of the form [!]SUBJECT (>=|<=|==|in) VALUE" % piece)
+            if len(out) >= FILTER_MAX_CLAUSES:
+                raise ValueError("filter clause %d (%r): at most %d clauses" % (len(out) + 1, piece, FILTER_MAX_CLAUSES))
+            neg, what, red, inside, op, value = m.groups()
+            try:
+                if op.strip() == "in":
+                    lo, hi = (int(x) for x in value.split(".."))
+                else:
+                    v = int(value)
+                    lo, hi = {">=": (v, None), "<=": (None, v), "==": (v, v)}[op]
+            except ValueError:
+                raise ValueError("filter clause %r: %r is no integer (or LO..HI after `in`)" % (piece, value.strip()))
+            if lo is not None and hi is not None and lo > hi:
+                raise ValueError("filter clause %r: LO > HI" % piece)
+            if inside is None:
+                if what not in FILTER_SUBJECTS[:4] or red is not None:
+                    raise ValueError("filter clause %r: unknown subject %r (latency, rows, start, class, or METRIC[SERVICE])" % (piece, what + ("." + red if red else "")))
+                out.append(clause(what, lo, hi, term=k, negate=bool(neg)))
+                continue
+            if what not in FILTER_METRICS:
+                raise ValueError("filter clause %r: unknown metric %r (%s)" % (piece, what, ", ".join(FILTER_METRICS)))
+            if red is not None and red not in FILTER_REDUCES:
+                raise ValueError("filter clause %r: unknown reduction %r (%s)" % (piece, red, ", ".join(FILTER_REDUCES)))
+            red = red or "sum"
+            if what in ("count", "onpath") and red != "sum":
+                raise ValueError("filter clause %r: %s is a count, it has no %s" % (piece, what, red))
+            if ">" in inside:
+                caller, callee = inside.split(">", 1)
+                if what not in ("count", "span"):
+                    raise ValueError("filter clause %r: an edge has count and span only, not %r" % (piece, what))
+                if callee.strip() == "*":
+                    raise ValueError("filter clause %r: an edge names its callee" % piece)
+                out.append(clause("edge", lo, hi, term=k, group=service(callee, piece, None), caller=service(caller, piece, "-"), metric=what, reduce=red,
+                                  negate=bool(neg)))
+            else:
+                out.append(clause("group", lo, hi, term=k, group=service(inside, piece, "*"), metric=what, reduce=red, negate=bool(neg)))
+    return out
+
+
+class TraceFilter(object):
+    """What Engine.filter_traces returns (include/traceweaver_amd.h has the definitions): tree_match uint8 [n_trees]; match_trees
+    int32, the matched trees in ascending order; clause_value int64 [n_trees, n_clauses] (NO_VALUE: a min / max over no rows);
+    clause_trees int64 [n_clauses]: eligible trees on which the clause holds; term_trees int64 [FILTER_MAX_TERMS]: eligible trees on
+    which every clause of the term holds (0 for a term without a clause); summary = eligible trees, matched trees, sum / min / max of
+    their latency (INT64_MAX / INT64_MIN without a match), their rows.  clauses (not compared by same_as): the query's tuples."""
+
+    FIELDS = ("tree_match", "match_trees", "clause_value", "clause_trees", "term_trees", "summary")
+
+    def __init__(self, tree_match, match_trees, clause_value, clause_trees, term_trees, summary, clauses=()):
+        self.tree_match, self.match_trees, self.clause_trees, self.term_trees = tree_match, match_trees, clause_trees, term_trees
+        self.clauses = [tuple(int(x) for x in c) for c in clauses]
+        self.clause_value = np.asarray(clause_value, dtype=np.int64).reshape(len(tree_match), len(self.clauses))
+        self.summary = np.asarray(summary, dtype=np.int64)
+
+    n_eligible = property(lambda self: int(self.summary[0]))
+    n_matched = property(lambda self: int(self.summary[1]))
+
+    def matched(self):
+        """The matched trees, ascending (match_trees)."""
+        return self.match_trees
+
+    def table(self, names=None):
+        """One dict per clause ({"clause", "term", "text", "trees"}) and then one per term with a clause ({"term", "text", "trees"}):
+        the eligible trees it holds on, and its text in the language of parse_filter."""
+        rows = [{"clause": j, "term": c[0], "text": format_clause(c, names), "trees": int(self.clause_trees[j])} for j, c in enumerate(self.clauses)]
+        for k in sorted({c[0] for c in self.clauses}):
+            rows.append({"term": k, "text": " & ".join(format_clause(c, names) for c in self.clauses if c[0] == k), "trees": int(self.term_trees[k])})
+        return rows
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def write_filter_npz(path, result, names):
+    """A TraceFilter as one .npz: its arrays, the clauses as an [n, 9] int64 table (the columns of clause()), the expression in
+    the language of parse_filter and the group names."""
+    out = {k: getattr(result, k) for k in TraceFilter.FIELDS}
+    out.update({"clauses": np.array(result.clauses, dtype=np.int64).reshape(-1, 9), "expression": np.array(format_filter(result.clauses, names)),
+                "group_names": np.array([str(x) for x in names])})
+    with open(path, "wb") as f:
+        np.savez_compressed(f, **out)
+
+
+def filter_host(stitched, link, row_kind, row_start, row_end, row_group, n_groups, clauses, need_flags=WHOLE, skip_flags=0, attribution=None,
+                signatures=None):
+    """What tw_filter_traces computes, restated from the definitions in plain Python, for the tests: a loop over the rows of every
+    tree per clause, dictionaries for the counts.  attribution: the host result of attribute_host on the same forest (self_time,
+    path_time; the rows on the critical path are walked again here), needed by the metrics self, path and onpath; signatures: the
+    result of signatures_host whose tree_class a class clause reads.  ValueError where the device refuses."""
+    link = [int(x) for x in link]
+    kind = [int(x) for x in row_kind]
+    group = [int(x) for x in row_group]
+    start = [int(x) for x in row_start]
+    end = [max(int(e), s) for e, s in zip(row_end, start)]
+    clauses = [tuple(int(x) for x in c) for c in clauses]
+    if len(clauses) > FILTER_MAX_CLAUSES:
+        raise ValueError("more than %d clauses" % FILTER_MAX_CLAUSES)
+    walked = None
+    for term, subject, g, cg, metric, reduce, negate, lo, hi in clauses:
+        if not (0 <= term < FILTER_MAX_TERMS and 0 <= subject <= 5 and lo <= hi):
+            raise ValueError("term, subject or bounds out of range")
+        if subject >= 4:
+            edge = subject == 5
+            if not (0 <= metric <= (1 if edge else 4) and 0 <= reduce <= 2 and (-1 if not edge else 0) <= g < n_groups and (not edge or -1 <= cg < n_groups)):
+                raise ValueError("group, caller, metric or reduce out of range")
+            if metric in (0, 4) and reduce != 0:
+                raise ValueError("a count is summed")
+            if metric >= 2 and attribution is None:
+                raise ValueError("a clause on times without an attribution")
+            if metric == 4 and walked is None:
+                children = [[] for _ in link]
+                for c, p in enumerate(link):
+                    if p >= 0:
+                        children[p].append(c)
+                _, walked = critical_paths_host(children, start, end, stitched.tree_root)
+        if subject == 3 and signatures is None:
+            raise ValueError("a class clause without signatures")
+
+    def caller_group(r):                                          # the group of the nearest server row above r, -1 without one
+        p = link[r]
+        while p >= 0:
+            if kind[p] == 1:
+                return group[p]
+            p = link[p]
+        return -1
+
+    def row_value(r, metric):
+        if metric == 0:
+            return 1
+        if metric == 1:
+            return end[r] - start[r]
+        if metric == 2:
+            return int(attribution.self_time[r])
+        if metric == 3:
+            return int(attribution.path_time[r])
+        return 1 if walked[r] else 0
+
+    nt, nc = stitched.n_trees, len(clauses)
+    flags = np.asarray(stitched.tree_flags).astype(np.int64)
+    value = np.full((nt, nc), NO_VALUE, dtype=np.int64)
+    match = np.zeros(nt, dtype=np.uint8)
+    clause_trees, term_trees = {}, {}
+    used = sorted({c[0] for c in clauses})
+    eligible = 0
+    for t in range(nt):
+        rows = [int(r) for r in stitched.tree_rows[int(stitched.tree_off[t]):int(stitched.tree_off[t + 1])]]
+        holds = []
+        for j, (term, subject, g, cg, metric, reduce, negate, lo, hi) in enumerate(clauses):
+            if subject == 0:
+                v = int(stitched.tree_latency[t])
+            elif subject == 1:
+                v = len(rows)
+            elif subject == 2:
+                v = start[int(stitched.tree_root[t])]
+            elif subject == 3:
+                v = int(signatures.tree_class[t])
+            else:
+                if subject == 4:
+                    picked = [r for r in rows if (group[r] >= 0 if g < 0 else group[r] == g)]
+                else:
+                    picked = [r for r in rows if kind[r] == 1 and group[r] == g and caller_group(r) == cg]
+                values = [row_value(r, metric) for r in picked]
+                if reduce == 0:
+                    v = _wrap64(sum(values))
+                elif not values:
+                    v = None
+                else:
+                    v = min(values) if reduce == 1 else max(values)
+            if v is not None:
+                value[t, j] = v
+            holds.append(v is not None and ((lo <= v <= hi) != bool(negate)))
+        if not ((flags[t] & need_flags) == need_flags and (flags[t] & skip_flags) == 0):
+            continue
+        eligible += 1
+        for j, h in enumerate(holds):
+            if h:
+                clause_trees[j] = clause_trees.get(j, 0) + 1
+        good = [k for k in used if all(h for h, c in zip(holds, clauses) if c[0] == k)]
+        for k in good:
+            term_trees[k] = term_trees.get(k, 0) + 1
+        match[t] = 1 if (nc == 0 or good) else 0
+    listed = [t for t in range(nt) if match[t]]
+    lat = [int(stitched.tree_latency[t]) for t in listed]
+    n_rows = sum(int(stitched.tree_off[t + 1]) - int(stitched.tree_off[t]) for t in listed)
+    summary = [eligible, len(listed), _wrap64(sum(lat)), min(lat) if lat else INT64_MAX, max(lat) if lat else INT64_MIN, n_rows]
+    return TraceFilter(match, np.array(listed, dtype=np.int32), value, np.array([clause_trees.get(j, 0) for j in range(nc)], dtype=np.int64),
+                       np.array([term_trees.get(k, 0) for k in range(FILTER_MAX_TERMS)], dtype=np.int64), summary, clauses)

@@ -274,7 +274,9 @@ int tw_get_gauss_params(tw_engine *e, double *gauss);
  * The class catalogue (HIP events): ms[43] hash and lookup, ms[44] scan, append, insert and any rehash, ms[45] accumulate of the
  * last tw_class_history_push / tw_class_history_merge.
  * The last tw_filter_traces (HIP events): ms[46] the tree kernel (rows, clauses, terms, the bit), ms[47] the list of the matched
- * trees (count, scan, write), ms[48] the copies to the host. */
+ * trees (count, scan, write), ms[48] the copies to the host.
+ * The last tw_extract_traces (HIP events): ms[49] selection, sizes and offsets, ms[50] the tree kernel; ms[51] the copies of the
+ * last tw_get_extracted. */
 int tw_get_timing(tw_engine *e, double *ms, int32_t n);
 
 /* ---- neighbours of the hot path on the same device arrays -------------------------------
@@ -921,6 +923,79 @@ typedef struct {
     int64_t *term_trees;      /* [TW_FILT_MAX_TERMS] eligible trees on which every clause of the term holds; 0 for an unused term */
 } tw_filter_result;
 int tw_filter_traces(tw_engine *e, const tw_filter_query *q, const tw_filter_result *out, int64_t *summary6);
+
+/* ---- reconstructed traces handed out as trees: exemplars, pre-order rows (csrc/tw_extr.h) -------------------------------
+ *
+ * Extends: the stages above, which answer in aggregates (culprits, distributions, classes, a match bit); the reference walks
+ * its traces on the host (src/query_engine/delay_culprit.py:30-97) and hands none out either.  tw_extract_traces selects
+ * trees of the device forest of the last tw_stitch_traces and writes them as a packed sub-forest -- every tree in pre-order
+ * with local parent indices -- which it keeps on the device; tw_get_extracted copies it out.  Two calls, because the caller
+ * cannot know the sizes beforehand: the capacities of tw_get_extracted's arrays are the sizes summary6 returned.
+ *
+ * Definitions:
+ *   eligible    tree_flags hold every bit of need_flags and none of skip_flags: the device forest's flags as they are at the
+ *               call, so TW_TREE_CONFIDENT and TW_TREE_MATCH can be named as in tw_attribute_traces.
+ *   mode 0 TOP        the eligible trees in the order `order`, the first `limit` of them (limit 0: all of them):
+ *                       order 0  by tree ascending
+ *                       order 1  slowest first: key (tree_latency descending, tree ascending)
+ *                       order 2  fastest first: key (tree_latency ascending, tree ascending)
+ *   mode 1 QUANTILES  the eligible trees sorted ascending by (tree_latency, tree), n of them; output tree j is the one at
+ *                     index min(n - 1, (int64)(probs[j] * (double)n)), the index rule of tw_latency_distributions and
+ *                     tw_compare_cohorts.  A tree chosen twice appears twice; n = 0 selects nothing.
+ *   mode 2 LIST       the trees list[0 .. n_list) in the caller's order, duplicates kept; need_flags / skip_flags are not
+ *                     applied (match_trees of a filter, one tree of a class).
+ *   children(p)  the rows c of p's tree with link[c] == p, ordered by (row_start[c], c); link is the forest's link table, the
+ *                one tw_attribute_traces returns.
+ *   pre-order    visit(p): emit p, then visit(c) for every c of children(p) in that order; a tree is visit(root).
+ *   outputs      output tree j owns the positions out_off[j] .. out_off[j + 1]; a row's local index is its position less
+ *                out_off[j].  Per output tree: sel_tree (the source tree), sel_root (its root row), sel_latency, sel_start
+ *                (row_start of the root), sel_flags (the device flags, bits 3 and 4 included); out_off has n_sel + 1 entries.
+ *                Per position: row (span-table row); parent (local index of link[row], -1 for the root, otherwise smaller
+ *                than the row's own local index); depth (the stitch's); subtree (rows of the row's subtree, itself included:
+ *                the next sibling or uncle stands at q + subtree[q]); kind (row_kind: 1 the hop above the row was observed, 2
+ *                predicted, 0 absent); group (row_group, -1 when no row groups are resident); start, end; self_time,
+ *                path_time (gathered from the resident attribution when there is one).
+ *   summary6     eligible trees (LIST: n_trees), selected trees, rows of the selected trees, rows of the largest selected
+ *                tree, selected trees taken by the single-tree route (more than 256 rows), 1 if an attribution was resident
+ *                and the times were gathered, else 0.
+ *
+ * TW_ERR_STATE: before a stitch or after anything that drops the forest; tw_get_extracted without a result, or with
+ * self_time / path_time non-NULL when the result holds no times.  TW_ERR_ARG: mode or order out of range; limit negative; a
+ * prob outside [0, 1] or not a number; n_probs outside [0, 32]; n_list outside [0, 2^20] or an id outside [0, n_trees).  A
+ * refused call leaves everything resident as it was, the last result included.  The call writes no flag and drops nothing.
+ * Residency: the result holds copies in buffers of its own; another extraction replaces it; it goes with the forest (a load,
+ * tw_scale_load, tw_set_span_rows, a pass, a new stitch).  A later tw_filter_traces or tw_score_traces does not drop it: it
+ * answers the query as the flags stood.
+ * Limits: the selected assignment only and one engine's batch; 32 probs; 2^20 list entries; no decision margins per hop (a
+ * caller gathers tw_confidence's by `row`).  A tree of more than 256 rows is taken by one wavefront on tables in global
+ * memory: rows x preceding rows / 64 steps for the sibling sums and depth x rows / 64 for the sweeps over the levels.
+ * Results do not depend on scheduling: integers only; the lists and offsets are written by scans, not by a cursor.  Timing:
+ * tw_get_timing slots 49..51 (selection, sizes and offsets; the tree kernel; the copies of tw_get_extracted; HIP events, ms). */
+#define TW_EXTR_MAX_PROBS 32
+#define TW_EXTR_MAX_LIST (1 << 20)
+typedef struct {
+    uint32_t need_flags, skip_flags;
+    int32_t mode;          /* 0 TOP, 1 QUANTILES, 2 LIST */
+    int32_t order;         /* TOP: 0 by tree, 1 slowest first, 2 fastest first */
+    int64_t limit;         /* TOP: 0 = every eligible tree */
+    int32_t n_probs;       /* QUANTILES: <= TW_EXTR_MAX_PROBS */
+    int32_t n_list;        /* LIST: <= TW_EXTR_MAX_LIST */
+    const double *probs;
+    const int32_t *list;
+} tw_extract_query;
+typedef struct {
+    int32_t *sel_tree, *sel_root;            /* [n_sel] */
+    int64_t *sel_latency, *sel_start;        /* [n_sel] */
+    uint8_t *sel_flags;                      /* [n_sel] */
+    int64_t *out_off;                        /* [n_sel + 1] */
+    int32_t *row, *parent, *depth, *subtree; /* [rows of the selected trees] */
+    uint8_t *kind;
+    int32_t *group;
+    int64_t *start, *end;
+    int64_t *self_time, *path_time;          /* only where summary6[5] was 1 */
+} tw_extracted;
+int tw_extract_traces(tw_engine *e, const tw_extract_query *q, int64_t *summary6);
+int tw_get_extracted(tw_engine *e, const tw_extracted *out);
 
 /* ---- the classes of batch after batch: a catalogue on the device (csrc/tw_chist.h) --------------------------------
  *

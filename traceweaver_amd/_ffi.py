@@ -145,6 +145,18 @@ class FilterResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("tree_match", "match_trees", "clause_value", "clause_trees", "term_trees")]
 
 
+class ExtractQuery(ctypes.Structure):
+    _fields_ = [("need_flags", ctypes.c_uint32), ("skip_flags", ctypes.c_uint32), ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("limit", ctypes.c_int64),
+                ("n_probs", ctypes.c_int32), ("n_list", ctypes.c_int32), ("probs", ctypes.POINTER(ctypes.c_double)), ("list", ctypes.POINTER(ctypes.c_int32))]
+
+
+class Extracted(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("sel_tree", "sel_root", "sel_latency", "sel_start", "sel_flags", "out_off", "row", "parent", "depth", "subtree",
+                                               "kind", "group", "start", "end", "self_time", "path_time")]
+
+
+TW_EXTR_MAX_PROBS = 32
+TW_EXTR_MAX_LIST = 1 << 20
 TW_TREE_CONFIDENT = 8
 TW_TREE_MATCH = 16
 TW_FILT_MAX_CLAUSES = 16
@@ -159,7 +171,7 @@ EXPORTS = ["tw_create", "tw_destroy", "tw_last_error", "tw_load_batch", "tw_run_
            "tw_device_buffers", "tw_set_gaps_device", "tw_set_mixtures", "tw_fit_mixtures", "tw_fit_mixtures_seeded", "tw_set_fit_seed", "tw_fit_rows", "tw_fit_mixtures_tape", "tw_get_fit_order", "tw_get_mixtures", "tw_run_pass2", "tw_get_results", "tw_get_gauss_params", "tw_get_timing",
            "tw_assign_service", "tw_find_order", "tw_order_bound", "tw_order_stage", "tw_order_load", "tw_set_truth", "tw_evaluate", "tw_measure_hbm_copy", "tw_host_alloc", "tw_host_free", "tw_build_distributions", "tw_scale_load", "tw_run_baseline", "tw_wap5_delays", "tw_wap5_parents",
            "tw_set_span_rows", "tw_set_parents", "tw_stitch_traces", "tw_set_row_groups", "tw_attribute_traces",
-           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles", "tw_filter_traces",
+           "tw_get_decisions", "tw_score_traces", "tw_set_row_cohorts", "tw_latency_distributions", "tw_compare_cohorts", "tw_trace_signatures", "tw_class_profiles", "tw_filter_traces", "tw_extract_traces", "tw_get_extracted",
            "tw_history_reset", "tw_history_push", "tw_history_merge", "tw_history_info", "tw_history_distributions", "tw_history_compare",
            "tw_class_history_reset", "tw_class_history_push", "tw_class_history_match", "tw_class_history_merge", "tw_class_history_info", "tw_class_history_get",
            "tw_corpus_create", "tw_corpus_destroy", "tw_corpus_last_error", "tw_corpus_add_files", "tw_corpus_set_callers", "tw_corpus_counts",
@@ -242,6 +254,8 @@ def load(path=None):
     lib.tw_trace_signatures.argtypes = [vp, ctypes.POINTER(SigQuery), ctypes.POINTER(Signatures), vp]
     lib.tw_class_profiles.argtypes = [vp, ctypes.POINTER(ClassProfile), vp]
     lib.tw_filter_traces.argtypes = [vp, ctypes.POINTER(FilterQuery), ctypes.POINTER(FilterResult), vp]
+    lib.tw_extract_traces.argtypes = [vp, ctypes.POINTER(ExtractQuery), vp]
+    lib.tw_get_extracted.argtypes = [vp, ctypes.POINTER(Extracted)]
     lib.tw_host_alloc.argtypes = [ctypes.c_int64, ctypes.POINTER(vp)]
     lib.tw_host_free.argtypes = [vp]
     lib.tw_host_free.restype = None

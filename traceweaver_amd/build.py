@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libtwgpu.so")
-SOURCES = ["tw_engine.hip", "tw_kernels.h", "tw_tile.h", "tw_lean.h", "tw_device.h", "tw_fit.h", "tw_eval.h", "tw_skip.h", "tw_load.h", "tw_baselines.h", "tw_stitch.h", "tw_attr.h", "tw_conf.h", "tw_dist.h", "tw_cmp.h", "tw_hist.h", "tw_sig.h", "tw_prof.h", "tw_filt.h", "tw_chist.h", "tw_order.h", "tw_ingest.cpp"]
+SOURCES = ["tw_engine.hip", "tw_kernels.h", "tw_tile.h", "tw_lean.h", "tw_device.h", "tw_fit.h", "tw_eval.h", "tw_skip.h", "tw_load.h", "tw_baselines.h", "tw_stitch.h", "tw_attr.h", "tw_conf.h", "tw_dist.h", "tw_cmp.h", "tw_hist.h", "tw_sig.h", "tw_prof.h", "tw_filt.h", "tw_extr.h", "tw_chist.h", "tw_order.h", "tw_ingest.cpp"]
 
 # -ffp-contract=off: scores are chains of plain IEEE double operations in the reference's order;
 # an FMA would change the last bit and with it the resolution of exact ties (DESIGN.md "Scores").

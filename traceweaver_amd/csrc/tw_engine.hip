@@ -32,6 +32,7 @@
 #include "tw_sig.h"
 #include "tw_prof.h"
 #include "tw_filt.h"
+#include "tw_extr.h"
 #include "tw_chist.h"
 #include "tw_order.h"
 
@@ -42,7 +43,7 @@ namespace {
 constexpr int kMaxRepairRounds = 1 << 20;
 enum { ST_EMPTY = 0, ST_LOADED = 1, ST_PASS1 = 2, ST_MIX = 3, ST_PASS2 = 4 };
 enum { EV_BEGIN = 0, EV_PARAMS, EV_ENUM0, EV_ENUM1, EV_WIN, EV_SEL, EV_REPAIR, EV_END, EV_COUNT };
-enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_CHIST = 37, SE_FILT = 41, SE_COUNT = 45 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8 + 4 + 4
+enum { SE_STITCH = 0, SE_ATTR = 5, SE_CONF = 9, SE_DIST = 13, SE_SIG = 18, SE_PROF = 22, SE_CMP = 26, SE_HIST = 29, SE_CHIST = 37, SE_FILT = 41, SE_EXTR = 45, SE_COUNT = 50 };   // stage events: 5 + 4 + 4 + 5 + 4 + 4 + 3 + 8 + 4 + 4 + 5
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -294,6 +295,9 @@ struct tw_engine {
     int64_t prof_ent_cap = 0, prof_cls_cap = 0, prof_rows_cap = 0, prof_summary[6] = {0, 0, 0, 0, 0, 0};
     FiltDev FL{};                           // tw_filter_traces (tw_filt.h): scratch of a call; what outlives it is bit TW_TREE_MATCH of S.tree_flags
     int64_t filt_trees_cap = 0, filt_val_cap = 0;
+    ExtrDev X{};                            // tw_extract_traces / tw_get_extracted (tw_extr.h); extr_ready: the result (copies in buffers of
+    bool extr_ready = false, extr_times = false;   // its own) is resident, extr_times: with the self and path times of an attribution
+    int64_t extr_sort_cap = 0, extr_sel_cap = 0, extr_rows_cap = 0, extr_pos_cap = 0, extr_sel = 0, extr_rows = 0;
     // HIP events around the parts of a stage (SE_*: a stage's first event; created by tw_create) and what tw_get_timing reports of them
     hipEvent_t stage_ev[SE_COUNT] = {};
     double st_ms[6] = {0, 0, 0, 0, 0, 0};   // whole call on the device, links, jump rounds, count + scan + scatter, group + figures; [5] = rounds
@@ -303,6 +307,7 @@ struct tw_engine {
     double sg_ms[3] = {0, 0, 0};            // items and levels; sort, run lengths and hash; classes, comparison and per-class reduction
     double pf_ms[3] = {0, 0, 0};            // the sweep over the rows; the per-tree and per-class pass; the copies
     double fl_ms[3] = {0, 0, 0};            // trace filter: the tree kernel; the list of the matched trees; the copies
+    double ex_ms[3] = {0, 0, 0};            // extraction: selection, sizes and offsets; the tree kernel; the copies of tw_get_extracted
     double cm_ms[2] = {0, 0};               // ranks, pool and observed statistics; the permutation walk
     double hs_ms[5] = {0, 0, 0, 0, 0};      // history: plan (with the source check of a merge), merge; quantiles and histogram; observed statistics, permutation walk
     double ch_ms[3] = {0, 0, 0};            // class catalogue: hash and lookup; scan, append, insert and any rehash; accumulate
@@ -432,6 +437,10 @@ int stage_elapsed(tw_engine* e, int stage, int a, int b, double* ms) {
                                                              the attribution and the signature result where the query they were made
                                                              with named the bit (need_flags | skip_flags & 16): a result whose query
                                                              does not name the bit cannot depend on it and stays
+     extracted        extr_ready     tw_extract_traces    <- forest.  Copies in buffers of its own: it answers the query as the flags, the
+       traces                                                 row groups and the attribution stood, so tw_filter_traces, tw_score_traces,
+                                                             new row groups and a new attribution leave it; another extraction
+                                                             replaces it
      history          hist_C > 0     tw_history_push / tw_history_merge <- nothing: it holds copies.  Dropped by tw_history_reset and
                                                              tw_destroy only (its buffers are not a load's: free_all leaves them)
      class catalogue  ch_G > 0       tw_class_history_push / tw_class_history_merge <- nothing: it holds copies.  Dropped by
@@ -444,7 +453,8 @@ void drop_prof(tw_engine* e) { e->prof_ready = false; }
 void drop_sig(tw_engine* e) { e->sig_ready = false; drop_prof(e); }
 void drop_ref(tw_engine* e) { e->ref_set = false; }
 void drop_attribution(tw_engine* e) { e->attributed = false; drop_dist(e); drop_prof(e); }
-void drop_forest(tw_engine* e) { e->stitched = false; drop_attribution(e); drop_sig(e); }
+void drop_extr(tw_engine* e) { e->extr_ready = false; }
+void drop_forest(tw_engine* e) { e->stitched = false; drop_attribution(e); drop_sig(e); drop_extr(e); }
 void drop_groups(tw_engine* e) { e->groups_set = false; drop_attribution(e); drop_sig(e); drop_ref(e); }
 void drop_cohorts(tw_engine* e) { e->cohorts_set = false; drop_dist(e); }
 void drop_rows(tw_engine* e) { e->rows_set = false; drop_forest(e); drop_groups(e); drop_cohorts(e); }
@@ -459,6 +469,7 @@ void drop_buffers(tw_engine* e) {
     e->G = SigDev{}; e->sig_rows_cap = 0; e->sig_trees_cap = 0; e->sig_ent_cap = 0; e->sig_ref_cap = 0;   // signatures, reference set
     e->F = ProfDev{}; e->prof_ent_cap = 0; e->prof_cls_cap = 0; e->prof_rows_cap = 0;                  // class profile
     e->FL = FiltDev{}; e->filt_trees_cap = 0; e->filt_val_cap = 0;                                     // scratch of the trace filter
+    e->X = ExtrDev{}; e->extr_sort_cap = 0; e->extr_sel_cap = 0; e->extr_rows_cap = 0; e->extr_pos_cap = 0;   // extracted traces and their scratch
     e->M = CmpDev{}; e->cmp_rows_cap = 0; e->cmp_items_cap = 0;                                        // scratch of the cohort comparison
 }
 
@@ -2097,6 +2108,7 @@ int tw_get_timing(tw_engine* e, double* ms, int32_t n) {
     if (n > 37) ms[37] = e->fit_order_host_ms;                            // ... and the host's time for its order tables
     for (int i = 0; i < 3 && 43 + i < n; i++) ms[43 + i] = e->ch_ms[i];   // the last tw_class_history_push / _merge
     for (int i = 0; i < 3 && 46 + i < n; i++) ms[46 + i] = e->fl_ms[i];   // the last tw_filter_traces
+    for (int i = 0; i < 3 && 49 + i < n; i++) ms[49 + i] = e->ex_ms[i];   // the last tw_extract_traces (49, 50) / tw_get_extracted (51)
     for (int i = 0; i < 5 && 38 + i < n; i++) ms[38 + i] = e->hs_ms[i];   // the last tw_history_push / _merge (38, 39), _distributions (40), _compare (41, 42)
     return TW_OK;
 }
@@ -2643,6 +2655,19 @@ int tw_set_row_groups(tw_engine* e, int32_t n_groups, const int32_t* row_group) 
     return TW_OK;
 }
 
+namespace {
+
+// The trees in order of (latency, tree), the eligible ones first, into V.val_b with their keys in V.key_b: the selection of the
+// attribution, which the extraction reads too (on sort buffers of its own: it needs no row groups).  Counts into V.counters[0 .. 2).
+int trees_by_latency(tw_engine* e, const AttrDev& V, const AttrQueryDev& Q, int64_t nt) {
+    const unsigned threads = flat_threads(e);
+    hipLaunchKernelGGL(k_attr_flags, dim3(flat_grid(nt, threads)), dim3(threads), 0, e->stream, e->S, V, Q, nt);
+    HIPCHK(hipGetLastError());
+    return rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, V.key_a, V.key_b, V.val_a, V.val_b, (size_t)nt, 0u, 64u, e->stream); });
+}
+
+}  // namespace
+
 int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attribution* out, int64_t* summary) {
     if (e == nullptr || q == nullptr) return TW_ERR_ARG;
     TWCHK(need_forest(e, "tw_attribute_traces"));
@@ -2662,9 +2687,7 @@ int tw_attribute_traces(tw_engine* e, const tw_attr_query* q, const tw_attributi
     HIPCHK(hipMemsetAsync(A.err, 0, sizeof(int32_t), e->stream));
     HIPCHK(hipMemsetAsync(A.totals, 0, sizeof(unsigned long long) * (size_t)(kAttrCols * G), e->stream));
     HIPCHK(hipEventRecord(e->stage_ev[SE_ATTR + 0], e->stream));
-    hipLaunchKernelGGL(k_attr_flags, trees, tb, 0, e->stream, S, A, Q, nt);
-    HIPCHK(hipGetLastError());
-    TWCHK(rocprim_call(e, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, A.key_a, A.key_b, A.val_a, A.val_b, (size_t)nt, 0u, 64u, e->stream); }));
+    TWCHK(trees_by_latency(e, A, Q, nt));
     unsigned long long counters[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(counters, A.counters, sizeof(counters), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -3656,6 +3679,172 @@ int tw_filter_traces(tw_engine* e, const tw_filter_query* q, const tw_filter_res
     HIPCHK(hipStreamSynchronize(e->stream));
     for (int i = 0; i < 3; i++) TWCHK(stage_elapsed(e, SE_FILT, i, i + 1, &e->fl_ms[i]));
     return TW_OK;
+}
+
+/* ---- reconstructed traces handed out as trees: exemplars, pre-order rows (tw_extr.h) ---------------------------------------- */
+int tw_extract_traces(tw_engine* e, const tw_extract_query* q, int64_t* summary) {
+    if (e == nullptr || q == nullptr) return TW_ERR_ARG;
+    TWCHK(need_forest(e, "tw_extract_traces"));
+    const int64_t nt = e->st_trees;
+    if (q->mode < 0 || q->mode > 2) return fail(e, TW_ERR_ARG, "tw_extract_traces: mode outside {0 TOP, 1 QUANTILES, 2 LIST}");
+    ExtrPick pick{};
+    if (q->mode == 0) {
+        if (q->order < 0 || q->order > 2) return fail(e, TW_ERR_ARG, "tw_extract_traces: order outside {0 by tree, 1 slowest first, 2 fastest first}");
+        if (q->limit < 0) return fail(e, TW_ERR_ARG, "tw_extract_traces: limit is negative (0 takes every eligible tree)");
+    } else if (q->mode == 1) {
+        if (q->n_probs < 0 || q->n_probs > TW_EXTR_MAX_PROBS || (q->n_probs > 0 && q->probs == nullptr))
+            return fail(e, TW_ERR_ARG, "tw_extract_traces: n_probs outside [0, 32]");
+        for (int j = 0; j < q->n_probs; j++)
+            if (!(q->probs[j] >= 0.0 && q->probs[j] <= 1.0)) return fail(e, TW_ERR_ARG, "tw_extract_traces: a prob outside [0, 1]");
+    } else {
+        if (q->n_list < 0 || q->n_list > TW_EXTR_MAX_LIST || (q->n_list > 0 && q->list == nullptr))
+            return fail(e, TW_ERR_ARG, "tw_extract_traces: n_list outside [0, 2^20]");
+        for (int j = 0; j < q->n_list; j++)
+            if (q->list[j] < 0 || (int64_t)q->list[j] >= nt) return fail(e, TW_ERR_ARG, "tw_extract_traces: a listed tree outside [0, n_trees)");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    drop_extr(e);   // (the result's buffers are rewritten from here on)
+    const StitchDev& S = e->S;
+    ExtrDev& X = e->X;
+    const bool by_latency = q->mode == 1 || (q->mode == 0 && q->order != 0);
+    const int64_t sel_cap = std::max<int64_t>(std::max<int64_t>(nt, q->mode == 2 ? q->n_list : 0), TW_EXTR_MAX_PROBS);
+    if (X.counters == nullptr) DEV_ALLOC(X.counters, kExtrCounters);   // (all of them freed with the batch)
+    if (X.sel_tree == nullptr || sel_cap > e->extr_sel_cap) {
+        DEV_ALLOC(X.sel_tree, sel_cap); DEV_ALLOC(X.sel_root, sel_cap); DEV_ALLOC(X.sel_latency, sel_cap); DEV_ALLOC(X.sel_start, sel_cap);
+        DEV_ALLOC(X.sel_flags, sel_cap); DEV_ALLOC(X.out_off, sel_cap + 1); DEV_ALLOC(X.chunk_sum, sel_cap / kSigScanItems + 2);
+        e->extr_sel_cap = sel_cap;
+    }
+    if (by_latency && (X.key_a == nullptr || nt > e->extr_sort_cap)) {
+        DEV_ALLOC(X.key_a, nt); DEV_ALLOC(X.key_b, nt); DEV_ALLOC(X.val_a, nt); DEV_ALLOC(X.val_b, nt);
+        e->extr_sort_cap = std::max<int64_t>(nt, 1);
+    }
+    X.row_group = e->groups_set ? e->A.row_group : nullptr;
+    const bool times = e->attributed;
+    X.self_time = times ? e->A.self_time : nullptr;
+    X.path_time = times ? e->A.path_time : nullptr;
+    const unsigned threads = flat_threads(e);
+    const dim3 tb(threads);
+    auto scan_chunks = [&](int64_t n) { return (n + (int64_t)threads * kSigScanItems - 1) / ((int64_t)threads * kSigScanItems); };
+    unsigned long long counters[kExtrCounters] = {};
+    HIPCHK(hipMemsetAsync(X.counters, 0, sizeof(counters), e->stream));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_EXTR + 0], e->stream));
+    // 1. the selected trees into sel_tree
+    int64_t n_elig = nt, n_sel = 0;
+    if (q->mode == 2) {
+        n_sel = q->n_list;
+        if (n_sel > 0) HIPCHK(hipMemcpyAsync(X.sel_tree, q->list, sizeof(int32_t) * (size_t)n_sel, hipMemcpyHostToDevice, e->stream));
+    } else if (!by_latency) {
+        const ExtrSelScan V{S, X, q->need_flags, q->skip_flags, q->limit > 0 ? q->limit : nt};
+        const int64_t n_chunks = scan_chunks(nt);
+        if (nt > 0) {
+            hipLaunchKernelGGL(k_sig_scan_sums<ExtrSelScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, V, nt);
+            hipLaunchKernelGGL(k_sig_scan_chunks<ExtrSelScan>, dim3(1), tb, 0, e->stream, V, n_chunks);
+            hipLaunchKernelGGL(k_sig_scan_write<ExtrSelScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, V, nt);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(counters, X.counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        n_elig = (int64_t)counters[0];
+        n_sel = q->limit > 0 ? std::min<int64_t>(q->limit, n_elig) : n_elig;
+    } else {
+        AttrDev V{};   // the view k_attr_flags writes through: keys, values and its counters
+        V.key_a = X.key_a; V.key_b = X.key_b; V.val_a = X.val_a; V.val_b = X.val_b; V.counters = X.counters + kExtrAttrAt;
+        const AttrQueryDev Q{0, 0, 0, q->need_flags, q->skip_flags};
+        if (nt > 0) TWCHK(trees_by_latency(e, V, Q, nt));
+        HIPCHK(hipMemcpyAsync(counters, V.counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        n_elig = (int64_t)counters[0];
+        if (q->mode == 1) {
+            n_sel = n_elig > 0 ? q->n_probs : 0;
+            pick.n = (int32_t)n_sel;
+            for (int j = 0; j < pick.n; j++) pick.at[j] = std::min<int64_t>(n_elig - 1, (int64_t)(q->probs[j] * (double)n_elig));
+            if (n_sel > 0) hipLaunchKernelGGL(k_extr_pick, dim3(1), tb, 0, e->stream, X, pick);
+        } else {
+            n_sel = q->limit > 0 ? std::min<int64_t>(q->limit, n_elig) : n_elig;
+            if (n_sel > 0 && q->order == 2) HIPCHK(hipMemcpyAsync(X.sel_tree, X.val_b, sizeof(int32_t) * (size_t)n_sel, hipMemcpyDeviceToDevice, e->stream));
+            if (n_sel > 0 && q->order == 1) hipLaunchKernelGGL(k_extr_slowest, dim3(flat_grid(n_sel, threads)), tb, 0, e->stream, X, n_elig, n_sel);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    // 2. the per-tree columns, the sizes, out_off
+    if (n_sel > 0) {
+        const int64_t n_chunks = scan_chunks(n_sel);
+        const ExtrOffScan V{S, X};
+        hipLaunchKernelGGL(k_extr_sizes, dim3(flat_grid(n_sel, threads)), tb, 0, e->stream, S, X, n_sel);
+        hipLaunchKernelGGL(k_sig_scan_sums<ExtrOffScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, V, n_sel);
+        hipLaunchKernelGGL(k_sig_scan_chunks<ExtrOffScan>, dim3(1), tb, 0, e->stream, V, n_chunks);
+        hipLaunchKernelGGL(k_sig_scan_write<ExtrOffScan>, dim3((unsigned)n_chunks), tb, 0, e->stream, V, n_sel);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(counters, X.counters, sizeof(unsigned long long) * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t n_out = n_sel > 0 ? (int64_t)counters[1] : 0, big_rows = (int64_t)counters[4];
+    HIPCHK(hipMemcpyAsync(X.out_off + n_sel, &n_out, sizeof(int64_t), hipMemcpyHostToDevice, e->stream));   // the end of the last tree
+    HIPCHK(hipEventRecord(e->stage_ev[SE_EXTR + 1], e->stream));
+    // 3. the trees
+    if (X.row == nullptr || n_out > e->extr_rows_cap) {
+        DEV_ALLOC(X.row, n_out); DEV_ALLOC(X.parent, n_out); DEV_ALLOC(X.depth, n_out); DEV_ALLOC(X.subtree, n_out); DEV_ALLOC(X.group, n_out);
+        DEV_ALLOC(X.kind, n_out); DEV_ALLOC(X.start, n_out); DEV_ALLOC(X.end, n_out); DEV_ALLOC(X.self, n_out); DEV_ALLOC(X.path, n_out);
+        e->extr_rows_cap = std::max<int64_t>(n_out, 1);
+    }
+    if (big_rows > X.big_cap) {   // tables of the trees that outgrow a wavefront's LDS
+        DEV_ALLOC(X.g_row, big_rows); DEV_ALLOC(X.g_lnk, big_rows); DEV_ALLOC(X.g_par, big_rows); DEV_ALLOC(X.g_dep, big_rows);
+        DEV_ALLOC(X.g_sub, big_rows); DEV_ALLOC(X.g_pre, big_rows);
+        X.big_cap = big_rows;
+    }
+    if (big_rows > 0 && (X.pos == nullptr || S.n_rows > e->extr_pos_cap)) {
+        DEV_ALLOC(X.pos, S.n_rows);
+        e->extr_pos_cap = S.n_rows;
+    }
+    if (n_sel > 0) {
+        const WaveShape per_tree = wave_shape(e, n_sel, kExtrTrees, kExtrWaves);
+        hipLaunchKernelGGL(k_extr_trees, per_tree.grid, per_tree.block, 0, e->stream, S, X, n_sel);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e->stage_ev[SE_EXTR + 2], e->stream));
+    unsigned long long err = 0;
+    HIPCHK(hipMemcpyAsync(&err, X.counters + 6, sizeof(err), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (err == 2) return fail(e, TW_ERR_DEVICE, "tw_extract_traces: the tables of the large trees are smaller than the trees");
+    if (err != 0) return fail(e, TW_ERR_ARG, "tw_extract_traces: a row is linked to a row outside its tree: not the forest tw_stitch_traces left behind");
+    for (int i = 0; i < 2; i++) TWCHK(stage_elapsed(e, SE_EXTR, i, i + 1, &e->ex_ms[i]));
+    if (summary != nullptr) {
+        summary[0] = n_elig; summary[1] = n_sel; summary[2] = n_out; summary[3] = n_sel > 0 ? (int64_t)counters[2] : 0;
+        summary[4] = (int64_t)counters[3]; summary[5] = times ? 1 : 0;
+    }
+    e->extr_sel = n_sel; e->extr_rows = n_out; e->extr_times = times;
+    e->extr_ready = true;
+    return TW_OK;
+}
+
+int tw_get_extracted(tw_engine* e, const tw_extracted* out) {
+    if (e == nullptr || out == nullptr) return TW_ERR_ARG;
+    if (!e->extr_ready) return fail(e, TW_ERR_STATE, "tw_get_extracted needs the result of a tw_extract_traces call (whatever drops the forest drops it)");
+    if (!e->extr_times && (out->self_time != nullptr || out->path_time != nullptr))
+        return fail(e, TW_ERR_STATE, "tw_get_extracted: the result holds no self / path times (no attribution was resident when it was made)");
+    HIPCHK(hipSetDevice(e->device));
+    const ExtrDev& X = e->X;
+    const size_t ns = (size_t)e->extr_sel, nr = (size_t)e->extr_rows;
+    HIPCHK(hipEventRecord(e->stage_ev[SE_EXTR + 3], e->stream));
+    TWCHK(copy_out(e, out->sel_tree, X.sel_tree, ns));
+    TWCHK(copy_out(e, out->sel_root, X.sel_root, ns));
+    TWCHK(copy_out(e, out->sel_latency, X.sel_latency, ns));
+    TWCHK(copy_out(e, out->sel_start, X.sel_start, ns));
+    TWCHK(copy_out(e, out->sel_flags, X.sel_flags, ns));
+    TWCHK(copy_out(e, out->out_off, X.out_off, ns + 1));
+    TWCHK(copy_out(e, out->row, X.row, nr));
+    TWCHK(copy_out(e, out->parent, X.parent, nr));
+    TWCHK(copy_out(e, out->depth, X.depth, nr));
+    TWCHK(copy_out(e, out->subtree, X.subtree, nr));
+    TWCHK(copy_out(e, out->kind, X.kind, nr));
+    TWCHK(copy_out(e, out->group, X.group, nr));
+    TWCHK(copy_out(e, out->start, X.start, nr));
+    TWCHK(copy_out(e, out->end, X.end, nr));
+    TWCHK(copy_out(e, out->self_time, X.self, nr));
+    TWCHK(copy_out(e, out->path_time, X.path, nr));
+    HIPCHK(hipEventRecord(e->stage_ev[SE_EXTR + 4], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return stage_elapsed(e, SE_EXTR, 3, 4, &e->ex_ms[2]);
 }
 
 /* ---- the classes of batch after batch: a catalogue on the device (tw_chist.h) -------------------------------------------- */

@@ -781,6 +781,37 @@ class Engine(object):
         self._check(self._lib.tw_get_timing(self._h, _vp(ms), 49))
         return dict(zip(("trees", "list", "copies"), ms[46:49].tolist()))
 
+    def extract_traces(self, mode="top", order="slowest", limit=0, probs=(), trees=None, need_flags=1, skip_flags=0):
+        """Hands out trees of the last stitch() as a packed sub-forest, built on the device (tw_extract_traces, tw_get_extracted): every
+        selected tree in pre-order with local parent indices.  mode "top": the eligible trees (flags hold need_flags, none of
+        skip_flags -- the device's flags, so traces.CONFIDENT and traces.MATCH can be named) in the order "tree" / "slowest" /
+        "fastest", the first `limit` of them (0: all); "quantiles": the trees at `probs` of the eligible trees' latency, the exemplars;
+        "list": the trees `trees` names (match_trees of a filter), in that order, flags not applied.  The self / path times of the last
+        attribute() and the row groups are gathered where resident.  Returns traces.ExtractedTraces."""
+        from .traces import EXTRACT_MODES, EXTRACT_ORDERS, ExtractedTraces, _extract_code
+
+        probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        listed = np.ascontiguousarray([] if trees is None else trees, dtype=np.int32).reshape(-1)
+        q = _ffi.ExtractQuery(int(need_flags), int(skip_flags), _extract_code(EXTRACT_MODES, mode, "mode"), _extract_code(EXTRACT_ORDERS, order, "order"),
+                              int(limit), len(probs), len(listed), probs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                              listed.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        summary = np.zeros(6, dtype=np.int64)
+        self._check(self._lib.tw_extract_traces(self._h, ctypes.byref(q), _vp(summary)))
+        n_sel, n_rows, times = int(summary[1]), int(summary[2]), bool(summary[5])
+        cols = {}
+        for k in ExtractedTraces.FIELDS[:-1]:
+            n = n_sel + 1 if k == "out_off" else n_sel if k in ExtractedTraces.TREE_FIELDS else n_rows if times or k not in ("self_time", "path_time") else 0
+            cols[k] = np.zeros(n, dtype=ExtractedTraces.DTYPES.get(k, np.int64))
+        out = _ffi.Extracted(*[_vp(cols[k]) if len(cols[k]) or k == "out_off" else None for k in ExtractedTraces.FIELDS[:-1]])
+        self._check(self._lib.tw_get_extracted(self._h, ctypes.byref(out)))
+        return ExtractedTraces(summary, **cols)
+
+    def extract_timing(self):
+        """The last extract_traces() on the device (HIP events, ms): selection, sizes and offsets; the tree kernel; the copies."""
+        ms = np.zeros(52, dtype=np.float64)
+        self._check(self._lib.tw_get_timing(self._h, _vp(ms), 52))
+        return dict(zip(("select", "trees", "copies"), ms[49:52].tolist()))
+
     # ---- the class catalogue: call-graph classes kept across batches (tw_class_history_*, csrc/tw_chist.h) ----
     def class_history_reset(self):
         """Empties the class catalogue (tw_class_history_reset): no classes, mode and number of groups open again."""

@@ -154,6 +154,16 @@ def parse_args(argv=None):
                          "METRIC[.REDUCE][CALLER>SERVICE] -- METRIC one of count, span, self, path, onpath, REDUCE one of sum, min, max, "
                          "SERVICE * = any counted service, CALLER - = no caller; e.g. 'latency>=20000 & !count[cache]>=1 | span.max[search]>=5000'.  "
                          "At most 16 clauses in 8 terms.  Needs --stitch_out's conditions.  Default: off, nothing changes")
+    ap.add_argument("--traces_out", type=q, default=None,
+                    help="extract reconstructed traces on the device (tw_extract_traces) after the other requested stages and write them into this "
+                         "directory: every trace in pre-order with its parents, with self / path times where --attribute_out or --profiles_out "
+                         "left an attribution.  Selected by one of --traces_top (default: 20), --traces_quantiles, --traces_matched among the "
+                         "whole traces of the predicted forest.  Needs --stitch_out's conditions.  Default: off, nothing changes")
+    ap.add_argument("--traces_top", type=int, default=None, help="--traces_out: the N slowest whole traces (0: all of them)")
+    ap.add_argument("--traces_quantiles", type=q, default=None, help="--traces_out: the exemplars, the traces at these quantiles of the latency, e.g. 0.5,0.99 (at most 32)")
+    ap.add_argument("--traces_matched", type=int, default=0, help="--traces_out: 1 = every trace --trace_filter matched, in tree order (needs --trace_filter)")
+    ap.add_argument("--traces_format", type=q, default="jaeger", choices=("jaeger", "npz"),
+                    help="--traces_out: jaeger = one Jaeger JSON file per trace, in the shape the corpus came in, which a trace viewer opens; npz = one traces.npz")
     ap.add_argument("--filter_out", type=q, default=None, help="--trace_filter: write the matched traces, the clauses' values and counts to this .npz")
     ap.add_argument("--confidence_out", type=q, default=None,
                     help="score the stitched traces by confidence on the GPU (tw_score_traces: per request the margin between the selected "
@@ -263,6 +273,24 @@ def unsupported(args):
         problems.append("--query_percentile outside [0, 1)")
     if args.trace_filter and (10 not in requested(args) or args.cache_rate > 0):
         problems.append("--trace_filter without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    if args.traces_out and (10 not in requested(args) or args.cache_rate > 0):
+        problems.append("--traces_out without predictor 10 or with --cache_rate > 0 (it works on the stitched traces, see --stitch_out)")
+    selectors = [k for k, on in (("--traces_top", args.traces_top is not None), ("--traces_quantiles", args.traces_quantiles is not None), ("--traces_matched", args.traces_matched)) if on]
+    if selectors and not args.traces_out:
+        problems.append("%s without --traces_out" % selectors[0])
+    if len(selectors) > 1:
+        problems.append("%s: one selector of --traces_out at a time" % " and ".join(selectors))
+    if args.traces_top is not None and args.traces_top < 0:
+        problems.append("--traces_top is negative")
+    if args.traces_matched and not args.trace_filter:
+        problems.append("--traces_matched 1 without --trace_filter")
+    if args.traces_quantiles is not None:
+        try:
+            probs = [float(x) for x in args.traces_quantiles.split(",")]
+            if not probs or len(probs) > 32 or not all(0.0 <= p <= 1.0 for p in probs):
+                raise ValueError
+        except ValueError:
+            problems.append("--traces_quantiles %s: 1 to 32 numbers in [0, 1], separated by commas" % args.traces_quantiles)
     if args.filter_out and not args.trace_filter:
         problems.append("--filter_out without --trace_filter")
     if args.confidence_out and (10 not in requested(args) or args.cache_rate > 0):
@@ -378,6 +406,40 @@ def trace_filter(args, eng, names, report=False):
     return traces.MATCH
 
 
+def traces_out(args, eng, corpus, table, pass_):
+    """--traces_out: reconstructed traces of the predicted forest, extracted on the device after the other stages and written as Jaeger
+    JSON or as one .npz.  The stages before it leave the predicted forest behind, except --attribute_out / --latency_out with -v
+    alone (their last stitch is the true forest): then the forest, the filter and the query are made again."""
+    import os
+
+    from . import traces
+
+    group, names = traces.groups_from_table(table, corpus)
+    names = [str(x) for x in names]
+    attributed = bool(args.attribute_out or args.latency_out)
+    if attributed and args.verbose and not (args.signatures_out or args.profiles_out):
+        eng.stitch(pass_)
+        match = trace_filter(args, eng, names)
+        eng.attribute(percentile=args.query_percentile, start_min=args.query_after, need_flags=traces.WHOLE | match)
+    elif not (args.trace_filter or attributed or args.signatures_out or args.profiles_out):
+        eng.set_row_groups(group, len(names))                     # (nobody has set them)
+    need = traces.WHOLE | (traces.MATCH if args.traces_matched else 0)
+    if args.traces_matched:
+        x = eng.extract_traces("top", "tree", 0, need_flags=need)
+    elif args.traces_quantiles is not None:
+        x = eng.extract_traces("quantiles", probs=[float(p) for p in args.traces_quantiles.split(",")], need_flags=need)
+    else:
+        x = eng.extract_traces("top", "slowest", 20 if args.traces_top is None else args.traces_top, need_flags=need)
+    os.makedirs(args.traces_out, exist_ok=True)
+    if args.traces_format == "npz":
+        traces.write_extracted_npz(os.path.join(args.traces_out, "traces.npz"), x, names)
+    else:
+        traces.write_jaeger(args.traces_out, x, corpus, table)
+    print("Extracted traces: %d of %d eligible, %d rows%s -> %s" % (x.n_trees, x.n_eligible, x.summary[2], ", with self and path times" if x.has_times else "", args.traces_out))
+    for j in range(min(3, x.n_trees) if args.verbose else 0):
+        print(x.render(j, names))
+
+
 def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solved=None):
     """--stitch_out: all services in one batch, the assignments they were given, the span table's rows -> traces on the device.
     solved: the engine that still holds the batch and the pass these assignments came from (--confidence_out)."""
@@ -406,6 +468,8 @@ def stitch_out(args, corpus, units, table, parents, n_traces, total, right, solv
         signatures_out(args, eng, corpus, table, 2 if solved is not None else 0)
     if args.profiles_out:
         profiles_out(args, eng, corpus, table, 2 if solved is not None else 0)
+    if args.traces_out:
+        traces_out(args, eng, corpus, table, 2 if solved is not None else 0)
     eng.close()
     if not args.stitch_out:
         return
@@ -800,7 +864,7 @@ def run(args):
                 accuracy_per_process[(METHOD, u.process_id)] = ev["accuracy"]
                 confidence[u.service] = [ev["accuracy"], r["not_best_count"], u.arrays.n_in]
             record(METHOD, [r["parent"] for r in res], {METHOD: flags[0], METHOD + "TopK": flags[1]})
-            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out or args.profiles_out or args.trace_filter:
+            if args.stitch_out or args.attribute_out or args.confidence_out or args.latency_out or args.signatures_out or args.profiles_out or args.trace_filter or args.traces_out:
                 stitch_out(args, corpus, units, table, [r["parent"] for r in res], n_traces, total, int((~flags[0].astype(bool) & seen).sum()),
                            solved=solved)
         else:

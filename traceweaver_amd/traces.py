@@ -31,6 +31,11 @@ Engine.filter_traces (tw_filter_traces, csrc/tw_filt.h) selects the stitched tra
 the device forest's flags, which all of the above select by: `clause` builds a clause, `parse_filter` / `format_filter` are the
 command line's language, `TraceFilter` is the result, `filter_host` restates the definitions with loops over the rows of a tree for
 the tests, `write_filter_npz` stores a result.
+
+Engine.extract_traces (tw_extract_traces / tw_get_extracted, csrc/tw_extr.h) hands out reconstructed traces as trees: `ExtractedTraces` is
+the result (every selected tree in pre-order with local parent indices; `render` draws one), `extract_host` restates the definitions
+with sorted() and a recursion over the children for the tests, `write_extracted_npz` stores a result and `write_jaeger` writes every
+extracted trace as a Jaeger JSON file in the shape the corpus came in.
 """
 import sys
 
@@ -1628,3 +1633,229 @@ def filter_host(stitched, link, row_kind, row_start, row_end, row_group, n_group
     summary = [eligible, len(listed), _wrap64(sum(lat)), min(lat) if lat else INT64_MAX, max(lat) if lat else INT64_MIN, n_rows]
     return TraceFilter(match, np.array(listed, dtype=np.int32), value, np.array([clause_trees.get(j, 0) for j in range(nc)], dtype=np.int64),
                        np.array([term_trees.get(k, 0) for k in range(FILTER_MAX_TERMS)], dtype=np.int64), summary, clauses)
+
+
+# ---- reconstructed traces handed out as trees: exemplars, pre-order rows (tw_extract_traces, csrc/tw_extr.h) ----
+EXTRACT_MODES = ("top", "quantiles", "list")
+EXTRACT_ORDERS = ("tree", "slowest", "fastest")
+EXTRACT_MAX_PROBS = 32               # TW_EXTR_MAX_PROBS
+EXTRACT_MAX_LIST = 1 << 20           # TW_EXTR_MAX_LIST
+EXTRACT_SINGLE_ROWS = 256            # kExtrCap of csrc/tw_extr.h: a tree of more rows is taken by the single-tree route (summary[4] counts them)
+
+
+def _extract_code(names, x, what):
+    if isinstance(x, str):
+        if x not in names:
+            raise ValueError("%s %r is none of %s" % (what, x, ", ".join(names)))
+        return names.index(x)
+    return int(x)
+
+
+class ExtractedTraces(object):
+    """What Engine.extract_traces returns (include/traceweaver_amd.h has the definitions): a packed sub-forest.  Output tree j owns the
+    positions out_off[j] .. out_off[j + 1] of the per-row columns, its rows in pre-order (children by (start, row)); per tree sel_tree
+    (the source tree), sel_root, sel_latency, sel_start, sel_flags; per row: row (span-table row), parent (local index, -1 for the
+    root, always smaller than the row's own), depth, subtree (rows of the subtree, itself included), kind (1 the hop above was
+    observed, 2 predicted, 0 absent), group (-1 without row groups), start, end, self_time / path_time (empty where the result holds
+    no times: summary[5] == 0).  summary = eligible trees, selected trees, their rows, the rows of the largest, the trees taken by the
+    single-tree route, 1 if the times are held."""
+
+    TREE_FIELDS = ("sel_tree", "sel_root", "sel_latency", "sel_start", "sel_flags")
+    ROW_FIELDS = ("row", "parent", "depth", "subtree", "kind", "group", "start", "end", "self_time", "path_time")
+    FIELDS = TREE_FIELDS + ("out_off",) + ROW_FIELDS + ("summary",)
+    DTYPES = {"sel_tree": np.int32, "sel_root": np.int32, "sel_flags": np.uint8, "row": np.int32, "parent": np.int32, "depth": np.int32,
+              "subtree": np.int32, "kind": np.uint8, "group": np.int32}       # every other field: int64
+
+    def __init__(self, summary, **columns):
+        for k in self.FIELDS[:-1]:
+            setattr(self, k, np.asarray(columns[k], dtype=self.DTYPES.get(k, np.int64)))
+        self.summary = np.asarray(summary, dtype=np.int64)
+
+    n_trees = property(lambda self: len(self.sel_tree))
+    n_eligible = property(lambda self: int(self.summary[0]))
+    has_times = property(lambda self: bool(self.summary[5]))
+
+    def __len__(self):
+        return self.n_trees
+
+    def trace(self, j):
+        """Output tree j: a dict of its columns ({"tree", "root", "latency", "start_time", "flags"} and the per-row arrays)."""
+        j = int(j)
+        if not 0 <= j < self.n_trees:
+            raise IndexError(j)
+        a, b = int(self.out_off[j]), int(self.out_off[j + 1])
+        out = {"tree": int(self.sel_tree[j]), "root": int(self.sel_root[j]), "latency": int(self.sel_latency[j]), "start_time": int(self.sel_start[j]),
+               "flags": int(self.sel_flags[j])}
+        for k in self.ROW_FIELDS:
+            col = getattr(self, k)
+            out[k] = col[a:b] if len(col) else col
+        return out
+
+    def children(self, j, i):
+        """Local indices of the children of row i of output tree j, in their order: i + 1, then from sibling to sibling by `subtree`."""
+        a = int(self.out_off[j])
+        out, c, end = [], i + 1, i + int(self.subtree[a + i])
+        while c < end:
+            out.append(c)
+            c += int(self.subtree[a + c])
+        return out
+
+    def render(self, j, names=None):
+        """Output tree j as an indented text waterfall, one line per row: the group's name (names[group]; the row number without
+        one), the start as an offset from the root's, the duration, self / path time where held, `*` on a predicted hop."""
+        t = self.trace(j)
+        lines = ["trace %d: tree %d, root row %d, %d rows, latency %d us%s" % (j, t["tree"], t["root"], len(t["row"]), t["latency"],
+                                                                                "" if t["flags"] & WHOLE else " (fragment)")]
+        for i in range(len(t["row"])):
+            g = int(t["group"][i])
+            name = str(names[g]) if names is not None and 0 <= g < len(names) else ("group %d" % g if g >= 0 else "row %d" % int(t["row"][i]))
+            text = "%s%s%s +%d us, %d us" % ("  " * (int(t["depth"][i]) + 1), "* " if int(t["kind"][i]) == 2 else "", name,
+                                             int(t["start"][i]) - t["start_time"], max(int(t["end"][i]) - int(t["start"][i]), 0))
+            if self.has_times:
+                text += " (self %d, path %d)" % (int(t["self_time"][i]), int(t["path_time"][i]))
+            lines.append(text)
+        return "\n".join(lines)
+
+    def same_as(self, other):
+        return all(np.array_equal(getattr(self, k), getattr(other, k)) for k in self.FIELDS)
+
+
+def extract_host(stitched, link, row_kind, row_start, row_end, row_group=None, mode="top", order="slowest", limit=0, probs=(), trees=None,
+                 need_flags=WHOLE, skip_flags=0, attribution=None, single_rows=EXTRACT_SINGLE_ROWS):
+    """What tw_extract_traces / tw_get_extracted compute, restated from the definitions in plain Python, for the tests: the selection
+    with sorted(), the pre-order by recursion over children().  stitched.tree_flags: the flags as the device holds them (CONFIDENT,
+    MATCH included where a query names them).  row_group None: no row groups are resident.  attribution: the host result whose self /
+    path times are gathered.  single_rows: kExtrCap of the build (summary[4] counts the selected trees beyond it).  ValueError where
+    the device returns TW_ERR_ARG."""
+    import math
+
+    mode, order = _extract_code(EXTRACT_MODES, mode, "mode"), _extract_code(EXTRACT_ORDERS, order, "order")
+    nt = stitched.n_trees
+    latency = [int(x) for x in stitched.tree_latency]
+    flags = [int(x) for x in stitched.tree_flags]
+    if mode not in (0, 1, 2):
+        raise ValueError("mode out of range")
+    eligible = [t for t in range(nt) if (flags[t] & need_flags) == need_flags and (flags[t] & skip_flags) == 0]
+    if mode == 0:
+        if order not in (0, 1, 2):
+            raise ValueError("order out of range")
+        if int(limit) < 0:
+            raise ValueError("limit is negative")
+        key = {0: lambda t: t, 1: lambda t: (-latency[t], t), 2: lambda t: (latency[t], t)}[order]
+        chosen = sorted(eligible, key=key)
+        if int(limit) > 0:
+            chosen = chosen[:int(limit)]
+        n_eligible = len(eligible)
+    elif mode == 1:
+        probs = [float(p) for p in probs]
+        if len(probs) > EXTRACT_MAX_PROBS:
+            raise ValueError("more than %d probs" % EXTRACT_MAX_PROBS)
+        if any(math.isnan(p) or p < 0.0 or p > 1.0 for p in probs):
+            raise ValueError("a prob outside [0, 1]")
+        by_latency = sorted(eligible, key=lambda t: (latency[t], t))
+        n = len(by_latency)
+        chosen = [by_latency[min(n - 1, int(p * float(n)))] for p in probs] if n else []
+        n_eligible = n
+    else:
+        chosen = [int(t) for t in ([] if trees is None else trees)]
+        if len(chosen) > EXTRACT_MAX_LIST:
+            raise ValueError("more than 2^20 listed trees")
+        if any(t < 0 or t >= nt for t in chosen):
+            raise ValueError("a listed tree outside [0, n_trees)")
+        n_eligible = nt
+    link = [int(x) for x in link]
+    start = [int(x) for x in row_start]
+    cols = {k: [] for k in ExtractedTraces.FIELDS[:-1]}
+    cols["out_off"].append(0)
+    sys.setrecursionlimit(max(sys.getrecursionlimit(), 100000))
+    largest = single = 0
+    for t in chosen:
+        rows = [int(r) for r in stitched.tree_rows[int(stitched.tree_off[t]):int(stitched.tree_off[t + 1])]]
+        root = int(stitched.tree_root[t])
+        kids = {r: [] for r in rows}
+        for c in rows:
+            if link[c] >= 0:
+                kids[link[c]].append(c)
+        local, base = {}, len(cols["row"])
+
+        def visit(p):
+            """Emits p and its subtree; returns the subtree's rows."""
+            at = len(cols["row"])
+            local[p] = at - base
+            cols["row"].append(p)
+            cols["parent"].append(-1 if p == root else local[link[p]])
+            cols["subtree"].append(0)
+            count = 1
+            for c in sorted(kids[p], key=lambda c: (start[c], c)):
+                count += visit(c)
+            cols["subtree"][at] = count
+            return count
+
+        visit(root)
+        cols["out_off"].append(len(cols["row"]))
+        largest = max(largest, len(rows))
+        single += len(rows) > single_rows
+        cols["sel_tree"].append(t)
+        cols["sel_root"].append(root)
+        cols["sel_latency"].append(latency[t])
+        cols["sel_start"].append(start[root])
+        cols["sel_flags"].append(flags[t])
+    for r in cols["row"]:
+        cols["depth"].append(int(stitched.depth[r]))
+        cols["kind"].append(int(row_kind[r]))
+        cols["group"].append(-1 if row_group is None else int(row_group[r]))
+        cols["start"].append(start[r])
+        cols["end"].append(int(row_end[r]))
+        if attribution is not None:
+            cols["self_time"].append(int(attribution.self_time[r]))
+            cols["path_time"].append(int(attribution.path_time[r]))
+    summary = [n_eligible, len(chosen), len(cols["row"]), largest, single, 1 if attribution is not None else 0]
+    return ExtractedTraces(summary, **cols)
+
+
+def write_extracted_npz(path, extracted, names):
+    """An ExtractedTraces as one .npz: its arrays and the group names."""
+    out = {k: getattr(extracted, k) for k in ExtractedTraces.FIELDS}
+    out["group_names"] = np.array([str(x) for x in names])
+    with open(path, "wb") as f:
+        np.savez_compressed(f, **out)
+
+
+def write_jaeger(directory, extracted, corpus, table=None):
+    """The extracted traces as Jaeger JSON, one file per output tree in the shape the loader reads ({"data": [{"traceID", "spans",
+    "processes"}]}): every span keeps the corpus's spanID, operationName, startTime and duration and gets a processID whose process
+    names its service; span.kind (server / client) from `kind`; a CHILD_OF reference to the local parent's span on every row but the
+    root; the tag tw.hop = observed | predicted (from `kind`), tw.self_us / tw.path_us where the times are held.  traceID =
+    "tw-" + the root's span id; a tree that was written before (a LIST with duplicates) gets the suffix -<j>.  Ground truth is not
+    consulted: the references are the reconstructed links.  Returns the paths."""
+    import json
+    import os
+
+    table = corpus.span_table() if table is None else table
+    os.makedirs(directory, exist_ok=True)
+    seen, paths = set(), []
+    for j in range(extracted.n_trees):
+        t = extracted.trace(j)
+        sid = [corpus.string(table["span_id"][r]) for r in t["row"]]
+        tid = "tw-" + sid[0]
+        if tid in seen:
+            tid += "-%d" % j
+        seen.add(tid)
+        processes, spans = {}, []
+        for i, r in enumerate(t["row"]):
+            service = corpus.string(table["service"][r])
+            pid = processes.setdefault(service, "p%d" % (len(processes) + 1))
+            kind = int(t["kind"][i])
+            p = int(t["parent"][i])
+            tags = [{"key": "span.kind", "type": "string", "value": "client" if kind == 2 else "server"},
+                    {"key": "tw.hop", "type": "string", "value": "predicted" if kind == 2 else "observed"}]
+            if extracted.has_times:
+                tags += [{"key": "tw.self_us", "type": "int64", "value": int(t["self_time"][i])}, {"key": "tw.path_us", "type": "int64", "value": int(t["path_time"][i])}]
+            spans.append({"traceID": tid, "spanID": sid[i], "operationName": corpus.string(table["op_name"][r]),
+                          "references": [] if p < 0 else [{"refType": "CHILD_OF", "traceID": tid, "spanID": sid[p]}],
+                          "startTime": int(table["start"][r]), "duration": int(table["duration"][r]), "tags": tags, "logs": [], "processID": pid, "warnings": None})
+        doc = {"data": [{"traceID": tid, "spans": spans, "processes": {pid: {"serviceName": s, "tags": []} for s, pid in processes.items()}, "warnings": None}]}
+        paths.append(os.path.join(directory, tid + ".json"))
+        with open(paths[-1], "w") as f:
+            json.dump(doc, f)
+    return paths
